@@ -3,6 +3,14 @@
 
   python bench.py --gpus N --steps K --warmup W        (N>1 from a bare shell: starts its own N rank processes; under
                                                         torch.distributed.run it is one of the ranks)
+           [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, writes the last step's outputs if --dump-outputs is given
+and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), the run's configuration and
+what the timed steps themselves tell (InvZeroPermArg retries, value_no_retry).  Everything else below is measured only with
+--full.  --dump-outputs DIR: the proof bytes of the last timed step as DIR/proof.npy (one byte per float32;
+`--workload commit`: the cap and a fixed seeded sample of the batch, 64-bit words as (high, low) 32-bit halves in float64);
+the inputs depend on the arguments alone, so two builds can be compared file by file.
 
 A "step" is one full prove() (plonk/prover.rs:228-447) of the 2^20-row dummy circuit (BASELINE.json configs[2]:
 Goldilocks, standard_recursion_config_gl with num_challenges = 3) from a MatrixWitness to ProofWithPublicInputs
@@ -10,10 +18,10 @@ bytes, constants/sigmas commitment pre-resident as after build().
 
 `value` is the proofs/s SURVEY.md 8(d) and BASELINE.md define: the witness is a (page-locked) HOST array handed over
 every step, as the drop-in boundary hands it over.  `value_hbm_resident` is the same circuit proved from a witness that
-is already resident in HBM when the timed region starts (the other boundary the task statement names); both are
+is already resident in HBM when the timed region starts (the other hand-over boundary); with --full both are
 timed the same way (W warm-up steps, barrier, exactly K steps, barrier, max over ranks) in the same run.
 
-Objects in the line:
+Objects that --full adds to the line:
   roofline      NTT pass (IFFT + LDE kernels of every commitment of a step) against the 8 TB/s HBM peak with
                 SURVEY.md 8(d)'s algorithmic bytes; durations from HIP events on the context's stream.
   roofline_alu  the dominant kernel, k_gl_merkle_leaves (Poseidon-12 leaf sponges): VALU wave-instructions per second
@@ -263,6 +271,7 @@ class ProveLeg:
         if self.inflight == 1:
             lctx, circuit, _, wit = self.lanes[0]
             self.proof = circuit.prove(wit, random_wire=self.random_wire, rng=self.rng[0], p3_repr=self.where == "vecs")
+            self.proofs = [self.proof]
             self.retries += circuit.perm_arg_retries
             self.step_log.append((time.perf_counter() - t0, circuit.perm_arg_retries))
         else:
@@ -277,7 +286,7 @@ class ProveLeg:
                 t.start()
             for t in ts:
                 t.join()
-            self.proof = out[0]
+            self.proof, self.proofs = out[0], out
             self.retries += sum(ret)
         self.proof_len = len(self.proof)
 
@@ -289,8 +298,9 @@ class ProveLeg:
         self.torch.cuda.synchronize()
         sharding.barrier()
 
-    def timed(self, steps, warmup, where):
-        """W untimed steps, then exactly K steps between barriers; returns (seconds = max over ranks, scopes, retries)."""
+    def timed(self, steps, warmup, where, profile=True):
+        """W untimed steps, then exactly K steps between barriers; returns (seconds = max over ranks, scopes, retries).
+        profile=False (a plain run): no per-scope HIP events, scopes None."""
         from plonky2_goldibear_amd import sharding
         self.set_witness(where)
         self.rng = [np.random.default_rng(1234 + self.rank * self.inflight + i) for i in range(self.inflight)]
@@ -298,7 +308,7 @@ class ProveLeg:
         for _ in range(warmup):
             self.step()
         self.retries, self.step_log = 0, []
-        if self.inflight == 1:
+        if profile and self.inflight == 1:
             self.ctx.set_profiling(True)  # per-scope HIP events; with several proofs in flight scopes overlap, so only wall time
         self.ctx.scope_reset()
         self.barrier()
@@ -309,7 +319,7 @@ class ProveLeg:
         self.barrier()
         dt = sharding.max_over_ranks(time.perf_counter() - t0)  # whole job = the slowest rank
         self.trace_marker()
-        scopes = {s: self.ctx.scope_ms(s) for s in SCOPES}
+        scopes = {s: self.ctx.scope_ms(s) for s in SCOPES} if profile else None
         self.ctx.set_profiling(False)
         return dt, scopes, self.retries
 
@@ -732,6 +742,57 @@ VECS_W = ("the reference's own layout (MatrixWitness.wire_values: Vec<Vec<F>>, i
           "numpy columns holding the field type's in-memory words, handed over every step as a table of %d pointers "
           "(gb_prove_cols, GB_INPUT_P3_REPR) and staged through the library's page-locked ring by its copy threads")
 N_WITNESSES = 16   # pinned witness seeds a leg cycles through
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of a run together
+
+
+def _exact_float(words):
+    """field words / bytes as floats that hold them exactly: 8- and 16-bit words in float32, 32-bit words in float64, a 64-bit
+    word as its (high, low) 32-bit halves along a new last axis of 2, in float64"""
+    w = np.asarray(words)
+    if w.dtype.itemsize <= 2:
+        return w.astype(np.float32)
+    if w.dtype.itemsize == 4:
+        return w.view(np.uint32).astype(np.float64)
+    u = w.view(np.uint64)
+    return np.stack([u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+
+
+def _dump_name(base, rank, world, lane=None, lanes=1):
+    return base + ("_rank%d" % rank if world > 1 else "") + ("_lane%d" % lane if lanes > 1 else "")
+
+
+def proof_outputs(proofs, rank, world):
+    """prove(): the proof bytes of every proof of the last timed step, one byte per float32"""
+    return {_dump_name("proof", rank, world, i, len(proofs)): _exact_float(np.frombuffer(p, dtype=np.uint8))
+            for i, p in enumerate(proofs)}
+
+
+def batch_outputs(b, rank, world, seed=0x5EED):
+    """from_values(): the Merkle cap, and a fixed seeded sample of what else the batch hands back - coefficients of 8 columns at
+    4096 rows, whole LDE rows (get_lde_values) at 256 positions, the leaf row and Merkle path of 16 leaves"""
+    rng = np.random.default_rng(seed)
+    n, nl = 1 << b.degree_log, 1 << (b.degree_log + b.rate_bits)
+    cols = np.sort(rng.choice(b.num_polys, size=min(8, b.num_polys), replace=False))
+    rows = np.sort(rng.choice(n, size=min(4096, n), replace=False))
+    lde_rows = np.sort(rng.choice(nl, size=min(256, nl), replace=False))
+    leaves = np.sort(rng.choice(nl, size=min(16, nl), replace=False))
+    paths = [b._leaf(int(i)) for i in leaves]
+    out = {"cap": b.merkle_tree.cap,
+           "coeffs_sample": np.stack([b.polynomial(int(c))[rows] for c in cols]),
+           "lde_rows_sample": np.stack([b.get_lde_values(int(i), 1) for i in lde_rows]),
+           "leaf_rows_sample": np.stack([r for r, _ in paths]),
+           "merkle_paths_sample": np.stack([s for _, s in paths])}
+    return {_dump_name(k, rank, world): _exact_float(v) for k, v in out.items()}
+
+
+def dump_outputs(dirname, arrays, world):
+    """this rank's arrays as DIR/<name>.npy; every rank writes about as much, so each stays under its share of the limit"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES // world:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes on this rank, more than %d" % (total, DUMP_LIMIT_BYTES // world))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def main():
@@ -764,6 +825,11 @@ def main():
     ap.add_argument("--lib-option", action="append", default=[], metavar="KEY=VALUE",
                     help="gb_ctx_set_option on every context of the run (copy_threads, lde_group, intt_group, ...), repeatable")
     ap.add_argument("--host-witness", action="store_true", help="(default since round 2; kept for old command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-scope roofline objects, the other witness placements, two proofs in "
+                         "flight, the BabyBear leg, verification / golden checks and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -820,7 +886,9 @@ def main():
         inflight = max(1, args.inflight)
         steps = args.steps
         leg = ProveLeg(args.field, log_n, args.challenges, local_rank, rank, inflight, ctx)
-        dt, scopes, retries = leg.timed(steps, args.warmup, "pinned")
+        dt, scopes, retries = leg.timed(steps, args.warmup, "pinned", profile=args.full)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, proof_outputs(leg.proofs, rank, world), world)
         if rank == 0:
             out = {
                 "metric": "proofs/s", "value": world * steps * inflight / dt, "unit": "proofs/s", "n_gpus": world, "steps": steps,
@@ -830,30 +898,32 @@ def main():
                            "cap_height": cap_height, "proofs_in_flight_per_gpu": inflight, "witness": HOST_W,
                            "sharding": "one independent circuit per GPU, no collective"},
             }
-            out.update(leg.report(steps, scopes, inflight, retries))
-            out["scopes_ms_per_step"] = {k: v[0] / steps for k, v in scopes.items() if v[1]}
-            out["verified"] = leg.verify_last()
-            if not args.no_checks:
-                out["verified_witnesses"] = "%d of %d" % (leg.verify_all_witnesses(), N_WITNESSES)   # every distinct witness, once, gb_verify
-                out["proof_sha256_matches_golden"], out["golden"] = leg.golden_check()   # == the CPU oracle prover's bytes for that witness
+            if args.full:
+                out.update(leg.report(steps, scopes, inflight, retries))
+                out["scopes_ms_per_step"] = {k: v[0] / steps for k, v in scopes.items() if v[1]}
+                out["verified"] = leg.verify_last()
+                if not args.no_checks:
+                    out["verified_witnesses"] = "%d of %d" % (leg.verify_all_witnesses(), N_WITNESSES)   # every distinct witness, once, gb_verify
+                    out["proof_sha256_matches_golden"], out["golden"] = leg.golden_check()   # == the CPU oracle prover's bytes for that witness
             out["perm_arg_retries"] = retries  # InvZeroPermArg re-runs inside the timed steps (BabyBear: ~1 in 5 proofs)
             out["value_no_retry"] = _num(leg.no_retry_rate() and world * leg.no_retry_rate())
             out["witnesses"] = "%d pinned seeds, cycled: every step proves a different witness" % N_WITNESSES
             out["affinity"] = affinity
             out["control_plane"] = control_plane
-        if world > 1:   # every rank's host footprint goes into the line (the default group is gloo: host objects)
+        # everything below is --full: a plain run is the headline leg above and nothing else
+        if args.full and world > 1:   # every rank's host footprint goes into the line (the default group is gloo: host objects)
             foot = [None] * world
             dist.all_gather_object(foot, host_footprint(leg))
             if rank == 0:
                 out["ranks_host"] = foot
-        elif rank == 0:
+        elif args.full and rank == 0:
             out["ranks_host"] = [host_footprint(leg)]
-        if not args.no_resident:
+        if args.full and not args.no_resident:
             dt2, scopes2, _ = leg.timed(steps, args.warmup, "hbm")
             if rank == 0:
                 out["value_hbm_resident"] = world * steps * inflight / dt2
                 out["ms_per_step_hbm_resident"] = dt2 / steps * 1e3
-        if not args.no_vecs:
+        if args.full and not args.no_vecs:
             dtv, scopesv, _ = leg.timed(steps, args.warmup, "vecs")
             if rank == 0:
                 out["value_vec_of_vecs"] = world * steps * inflight / dtv
@@ -862,8 +932,8 @@ def main():
                 out["scopes_ms_per_step_vec_of_vecs"] = {k: v[0] / steps for k, v in scopesv.items() if v[1]}
         leg.free()
         del leg
-        second = not args.no_inflight2 and inflight == 1   # SURVEY.md 8(d) counts a stream of independent proofs: two of them in
-        if second:                                          # flight per GPU (one host thread + one stream each), host witnesses
+        second = args.full and not args.no_inflight2 and inflight == 1   # SURVEY.md 8(d) counts a stream of independent proofs: two
+        if second:                                                       # in flight per GPU (one host thread + one stream each), host witnesses
             leg2 = ProveLeg(args.field, log_n, args.challenges, local_rank, rank, 2, ctx)
             dt3, _, _ = leg2.timed(steps, args.warmup, "pinned")
             if rank == 0:
@@ -871,7 +941,7 @@ def main():
                 out["ms_per_step_inflight2"] = dt3 / steps * 1e3    # one step = two proofs
             leg2.free()
             del leg2
-        if args.field == "goldilocks" and world == 1 and not args.no_babybear and log_n == 20:
+        if args.full and args.field == "goldilocks" and world == 1 and not args.no_babybear and log_n == 20:
             # BASELINE configs[3]: the same measurements for BabyBear + Poseidon2-16 (a 31-bit field needs num_challenges = 10)
             bleg = ProveLeg("babybear", log_n, None, local_rank, rank, inflight, ctx)
             bdt, bscopes, bret = bleg.timed(steps, args.warmup, "pinned")
@@ -902,7 +972,7 @@ def main():
                 bb["ms_per_step_inflight2"] = bdt3 / steps * 1e3
                 bleg2.free()
             out["babybear"] = bb
-        if rank == 0 and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only (the driver's contract)
+        if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only (the driver's contract)
             from oracle import oracle as _O
             cores = _O.host_cpu_share()
             bbf = args.field == "babybear"
@@ -923,8 +993,7 @@ def main():
         torch.cuda.synchronize()
 
         def step():
-            b = PolynomialBatch.from_values(ctx, dev, rate_bits, cap_height, field=ftag)
-            b.free()
+            return PolynomialBatch.from_values(ctx, dev, rate_bits, cap_height, field=ftag)
 
         def barrier():
             ctx.synchronize()
@@ -932,26 +1001,25 @@ def main():
             sharding.barrier()
 
         for _ in range(args.warmup):
-            step()
-        ctx.set_profiling(True)
+            step().free()
+        if args.full:
+            ctx.set_profiling(True)
         ctx.scope_reset()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            b = step()
+            if i + 1 < args.steps:
+                b.free()
         barrier()
         dt = sharding.max_over_ranks(time.perf_counter() - t0)
         scopes = {s: ctx.scope_ms(s) for s in SCOPES}
         ctx.set_profiling(False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, batch_outputs(b, rank, world), world)
+        b.free()
         if rank == 0:
             steps, N = args.steps, n << rate_bits
-            ntt_ms = (scopes["IFFT"][0] + scopes["FFT + blinding"][0]) / steps
-            merkle_ms = scopes["build Merkle tree"][0] / steps
-            alg_bytes = (2 + (1 << rate_bits)) * n * esz * ncols  # (2 + 2^r) n s per column
-            perms = N * (-(-ncols // 8)) + (N - (1 << cap_height))  # leaf sponge + internal nodes
-            achieved = alg_bytes / (ntt_ms * 1e-3) / 1e9 if ntt_ms else None
-            tj = _latest_profile("r*_ntt_traffic_pmc_%s.json" % args.field)
-            traffic = (tj["ifft_bytes_per_column"] + tj["lde_bytes_per_column"]) * ncols if (tj and log_n == 20) else None
             metric = "commits/s (PolynomialBatch::from_values, wires oracle of the 2^%d-row circuit)" % log_n
             out = {
                 "metric": metric, "value": world * steps / dt, "unit": "commits/s", "n_gpus": world, "steps": steps,
@@ -961,13 +1029,23 @@ def main():
                                ncols, log_n, args.field, "Poseidon2-16" if ftag else "Poseidon-12"),
                            "field": args.field, "log_n": log_n, "rate_bits": rate_bits, "cap_height": cap_height,
                            "sharding": "one independent batch per GPU, no collective"},
-                "roofline": {"bound": "hbm", "kernel": "NTT pass (IFFT + FFT + blinding scopes)", "achieved": _num(achieved),
-                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": _num(achieved / HBM_PEAK_GBS if achieved else None),
-                             "traffic": traffic, "algorithmic_bytes": alg_bytes, "ms": _num(ntt_ms)},
-                "scopes_ms_per_step": {k: v[0] / steps for k, v in scopes.items() if v[1]},
-                "merkle": {"permutations": perms, "Gperm_per_s": _num(perms / (merkle_ms * 1e-3) / 1e9 if merkle_ms else None)},
             }
-            if not args.no_cpu_baseline and world == 1:
+            if args.full:
+                ntt_ms = (scopes["IFFT"][0] + scopes["FFT + blinding"][0]) / steps
+                merkle_ms = scopes["build Merkle tree"][0] / steps
+                alg_bytes = (2 + (1 << rate_bits)) * n * esz * ncols  # (2 + 2^r) n s per column
+                perms = N * (-(-ncols // 8)) + (N - (1 << cap_height))  # leaf sponge + internal nodes
+                achieved = alg_bytes / (ntt_ms * 1e-3) / 1e9 if ntt_ms else None
+                tj = _latest_profile("r*_ntt_traffic_pmc_%s.json" % args.field)
+                traffic = (tj["ifft_bytes_per_column"] + tj["lde_bytes_per_column"]) * ncols if (tj and log_n == 20) else None
+                out.update({
+                    "roofline": {"bound": "hbm", "kernel": "NTT pass (IFFT + FFT + blinding scopes)", "achieved": _num(achieved),
+                                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": _num(achieved / HBM_PEAK_GBS if achieved else None),
+                                 "traffic": traffic, "algorithmic_bytes": alg_bytes, "ms": _num(ntt_ms)},
+                    "scopes_ms_per_step": {k: v[0] / steps for k, v in scopes.items() if v[1]},
+                    "merkle": {"permutations": perms, "Gperm_per_s": _num(perms / (merkle_ms * 1e-3) / 1e9 if merkle_ms else None)},
+                })
+            if args.full and not args.no_cpu_baseline and world == 1:
                 from oracle import oracle as _O
                 cores = _O.host_cpu_share()
                 sample = args.cpu_sample_log_n

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/ab_vecs.sh -1 0 2 4 8'
 mkdir -p gpurun_out/ab_vecs
 for t in "$@"; do
-    timeout -k 10 240 python3 bench.py --steps ${GB_AB_STEPS:-12} --warmup 3 --no-cpu-baseline --no-inflight2 --no-resident \
+    timeout -k 10 240 python3 bench.py --full --steps ${GB_AB_STEPS:-12} --warmup 3 --no-cpu-baseline --no-inflight2 --no-resident \
         --lib-option copy_threads=$t > gpurun_out/ab_vecs/bench_$t.json 2> gpurun_out/ab_vecs/bench_$t.err || exit 1
     python3 - <<PY
 import json

@@ -15,7 +15,7 @@ for v in "$@"; do
         for L in ${GB_LS_SIZES:-20 21 22}; do
             d=gpurun_out/ls/$v-$F-$L
             rm -rf $d
-            timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $d -o p -- python3 bench.py --workload commit --field $F --log-n $L --cols $C \
+            timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $d -o p -- python3 bench.py --full --workload commit --field $F --log-n $L --cols $C \
                 --steps 3 --warmup 1 --no-cpu-baseline > $d.log 2>&1 || { echo "FAILED $v $F $L" | tee -a $OUT; tail -5 $d.log | tee -a $OUT; continue; }
             python tools/rocpd_kernel_stats.py $d/p_results.db $d.csv
             python - <<PY | tee -a $OUT

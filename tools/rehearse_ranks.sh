@@ -7,7 +7,7 @@
 OUT=gpurun_out/rehearsal
 rm -rf $OUT && mkdir -p $OUT
 N=${GB_REHEARSE_RANKS:-5}
-ARGS="--steps 4 --warmup 1 --no-babybear --no-inflight2 --no-cpu-baseline --no-resident"
+ARGS="--full --steps 4 --warmup 1 --no-babybear --no-inflight2 --no-cpu-baseline --no-resident"
 echo "== $N ranks sharing one MI355X: GB_BENCH_SHARE_DEVICE=1 python3 bench.py --gpus $N $ARGS" | tee $OUT/summary.txt
 ( time GB_BENCH_SHARE_DEVICE=1 timeout -k 10 600 python3 bench.py --gpus $N $ARGS > $OUT/ranks.json 2> $OUT/ranks.err ) 2>> $OUT/summary.txt
 echo "exit code $?" | tee -a $OUT/summary.txt
