@@ -19,13 +19,18 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "bb_field.hpp"
 #include "gl_field.hpp"
 #include "kernels.hpp"
+#include "poseidon2_bb_host.hpp"
+#include "poseidon_gl_host.hpp"
 
+using gbk::BbF;
+using gbk::GlF;
 using gbk::u32;
 using gbk::u64;
 
@@ -42,21 +47,27 @@ struct ScopeAcc {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;
 };
 
-struct GlTableSet {
-    gbk::GlNttTables t{};
-    std::vector<void*> owned;
-};
-struct GlCosetSet {
-    gbk::GlCosetTables t{};
-    std::vector<void*> owned;
-};
-struct BbTableSet {
-    gbk::BbNttTables t{};
-    std::vector<void*> owned;
-};
-struct BbCosetSet {
-    gbk::BbCosetTables t{};
-    std::vector<void*> owned;
+// A context's twiddle and coset tables of one field (device form), built on first use and kept until gb_ctx_destroy
+template <class F>
+struct TableCache {
+    typedef typename F::T T;
+    typedef std::conditional_t<std::is_same<F, GlF>::value, gbk::GlNttTables, gbk::BbNttTables> Tables;
+    typedef std::conditional_t<std::is_same<F, GlF>::value, gbk::GlCosetTables, gbk::BbCosetTables> Cosets;
+    template <class X>
+    struct Owner {   // a table set and the device blocks it owns
+        X t{};
+        std::vector<void*> owned;
+    };
+    const T *tw4096_fwd = nullptr, *tw4096_inv = nullptr;
+    const T *tw4096_fwd_m = nullptr, *tw4096_inv_m = nullptr;   // Goldilocks: the same times R (Montgomery form)
+    std::vector<void*> owned;                                    // the shared 4096-point tables above
+    std::map<u32, Owner<Tables>> tables;                         // by log_n
+    std::map<std::tuple<u32, u32, T, int>, Owner<Cosets>> cosets;   // by (log_n, rate_bits, shift (device form), inverse)
+    void release() {
+        for (void* p : owned) hipFree(p);
+        for (auto& kv : tables) for (void* p : kv.second.owned) hipFree(p);
+        for (auto& kv : cosets) for (void* p : kv.second.owned) hipFree(p);
+    }
 };
 
 struct Stager;   // page-locked staging ring + copy threads for pageable host columns (below)
@@ -70,14 +81,7 @@ struct gb_ctx {
     std::string err;
     bool profiling = false;
     std::map<std::string, ScopeAcc> scopes;
-    u64* tw4096_fwd = nullptr;
-    u64* tw4096_inv = nullptr;
-    u64 *tw4096_fwd_m = nullptr, *tw4096_inv_m = nullptr;  // times R (Montgomery form)
-    std::map<u32, GlTableSet> gl_tables;                    // by log_n
-    std::map<std::tuple<u32, u32, u64, int>, GlCosetSet> gl_cosets;  // by (log_n, rate_bits, shift, inverse)
-    u32 *bb_tw4096_fwd = nullptr, *bb_tw4096_inv = nullptr;
-    std::map<u32, BbTableSet> bb_tables;
-    std::map<std::tuple<u32, u32, u32, int>, BbCosetSet> bb_cosets;  // by (log_n, rate_bits, shift (Montgomery), inverse)
+    std::tuple<TableCache<GlF>, TableCache<BbF>> tables;    // cache<F>(ctx)
     std::multimap<size_t, void*> pool;                      // freed batch blocks by size (stream-ordered reuse)
     DeviceBuf scratch;                                      // grow-only workspace
     DeviceBuf small;                                        // small gather staging (rows, siblings)
@@ -310,21 +314,28 @@ void pool_free(gb_ctx* ctx, void* p, size_t bytes) noexcept {   // (called from 
     }
 }
 
-gb_status upload(gb_ctx* ctx, const std::vector<u64>& host, u64** dev, std::vector<void*>* owned) {
+template <class F>
+TableCache<F>& cache(gb_ctx* ctx) { return std::get<TableCache<F>>(ctx->tables); }
+template <class F>
+constexpr bool is_goldilocks = std::is_same<F, GlF>::value;
+
+template <class T>
+gb_status upload(gb_ctx* ctx, const std::vector<T>& host, const T** dev, std::vector<void*>& owned) {
     void* p = nullptr;
-    HIP_TRY(ctx, hipMalloc(&p, host.size() * sizeof(u64)));
-    HIP_TRY(ctx, hipMemcpy(p, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice));
-    *dev = static_cast<u64*>(p);
-    if (owned) owned->push_back(p);
+    HIP_TRY(ctx, hipMalloc(&p, host.size() * sizeof(T)));
+    HIP_TRY(ctx, hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    *dev = static_cast<const T*>(p);
+    owned.push_back(p);
     return GB_OK;
 }
 
-std::vector<u64> powers(u64 base, size_t count) {
-    std::vector<u64> v(count);
-    u64 x = 1;
+template <class F>
+std::vector<typename F::T> powers(typename F::T base, size_t count) {
+    std::vector<typename F::T> v(count);
+    typename F::T x = F::one();
     for (size_t i = 0; i < count; i++) {
         v[i] = x;
-        x = gl::mul(x, base);
+        x = F::mul(x, base);
     }
     return v;
 }
@@ -335,82 +346,78 @@ u32 bitrev32(u32 x, u32 bits) {
     return r;
 }
 
-std::vector<u64> times_r(const std::vector<u64>& v) {   // Montgomery form of a table: x R mod p, R = 2^64 mod p
-    std::vector<u64> o(v.size());
-    for (size_t i = 0; i < v.size(); i++) o[i] = gl::to_mont_slow(v[i]);
-    return o;
+std::vector<u64> times_r(std::vector<u64> v) {   // Goldilocks' Montgomery form of a table: x R mod p, R = 2^64 mod p
+    for (u64& x : v) x = GlF::cform(x);
+    return v;
 }
 
-gb_status gl_tables_for(gb_ctx* ctx, u32 log_n, const gbk::GlNttTables** out) {
-    auto it = ctx->gl_tables.find(log_n);
-    if (it != ctx->gl_tables.end()) { *out = &it->second.t; return GB_OK; }
-    if (!ctx->tw4096_fwd) {
-        u64 w = gl::two_adic_generator(12);
-        // [0, 4096): w_4096^j.  [4096, 8192): the same powers in the order k_gl_lde_pb16's first stage reads them,
-        // T[s][m] = w_4096^(brev4(s) m), s < 16, m < 256 - a wave's 64 lanes then read 512 contiguous bytes per slot instead of
-        // gathering at stride brev4(s) (up to 60 cache lines per load instruction).
-        std::vector<u64> fwd = powers(w, 4096);
-        fwd.resize(8192);
-        for (u32 sl = 0; sl < 16; sl++)
-            for (u32 m = 0; m < 256; m++) fwd[4096 + sl * 256 + m] = fwd[(bitrev32(sl, 4) * m) & 4095];
-        gb_status s = upload(ctx, fwd, &ctx->tw4096_fwd, nullptr);
-        if (s) return s;
-        const std::vector<u64> inv = powers(gl::inv(w), 4096);
-        s = upload(ctx, inv, &ctx->tw4096_inv, nullptr);
-        if (s) return s;
-        if ((s = upload(ctx, times_r(fwd), &ctx->tw4096_fwd_m, nullptr))) return s;
-        if ((s = upload(ctx, times_r(inv), &ctx->tw4096_inv_m, nullptr))) return s;
+template <class F>
+gb_status tables_for(gb_ctx* ctx, u32 log_n, const typename TableCache<F>::Tables** out) {
+    typedef typename F::T T;
+    TableCache<F>& tc = cache<F>(ctx);
+    auto it = tc.tables.find(log_n);
+    if (it != tc.tables.end()) { *out = &it->second.t; return GB_OK; }
+    gb_status s;
+    if (!tc.tw4096_fwd) {
+        const T w = F::two_adic_generator(12);
+        std::vector<T> fwd = powers<F>(w, 4096);
+        const std::vector<T> inv = powers<F>(F::inv(w), 4096);
+        if constexpr (is_goldilocks<F>) {
+            // [0, 4096): w_4096^j.  [4096, 8192): the same powers in the order k_gl_lde_pb16's first stage reads them,
+            // T[s][m] = w_4096^(brev4(s) m), s < 16, m < 256 - a wave's 64 lanes then read 512 contiguous bytes per slot instead of
+            // gathering at stride brev4(s) (up to 60 cache lines per load instruction).
+            fwd.resize(8192);
+            for (u32 sl = 0; sl < 16; sl++)
+                for (u32 m = 0; m < 256; m++) fwd[4096 + sl * 256 + m] = fwd[(bitrev32(sl, 4) * m) & 4095];
+        }
+        if ((s = upload(ctx, fwd, &tc.tw4096_fwd, tc.owned))) return s;
+        if ((s = upload(ctx, inv, &tc.tw4096_inv, tc.owned))) return s;
+        if constexpr (is_goldilocks<F>) {
+            if ((s = upload(ctx, times_r(fwd), &tc.tw4096_fwd_m, tc.owned))) return s;
+            if ((s = upload(ctx, times_r(inv), &tc.tw4096_inv_m, tc.owned))) return s;
+        }
     }
-    GlTableSet set;
+    typename TableCache<F>::template Owner<typename TableCache<F>::Tables> set;
     set.t.log_n = log_n;
-    set.t.sub = nullptr;
-    set.t.tw16k_inv_m = nullptr;
     set.t.outer_bits = gbk::ntt_outer_bits(log_n);
     if (set.t.outer_bits) {   // the outer radix step (ntt_outer.hpp) runs smaller transforms: their tables first (std::map nodes do not move)
-        const gbk::GlNttTables* sub;
-        if (gb_status s2 = gl_tables_for(ctx, log_n - set.t.outer_bits, &sub)) return s2;
-        set.t.sub = sub;
+        if ((s = tables_for<F>(ctx, log_n - set.t.outer_bits, &set.t.sub))) return s;
     } else if (log_n > 20) {  // 2^21 / 2^22 rows: the middle inverse pass is a radix-32 / radix-64 DFT with twiddles w_{2^14}^-j
-        u64* t16;
-        if (gb_status s2 = upload(ctx, times_r(powers(gl::inv(gl::two_adic_generator(14)), (size_t)1 << 14)), &t16, &set.owned)) return s2;
-        set.t.tw16k_inv_m = t16;
+        if constexpr (!is_goldilocks<F>)
+            if (log_n == 22)   // BabyBear: the strided LDE pass of 2^22 rows works with the 2^20-row twiddles (k_bb_lde_pa16x2w)
+                if ((s = tables_for<F>(ctx, 20, &set.t.wide))) return s;
+        const std::vector<T> t16 = powers<F>(F::inv(F::two_adic_generator(14)), (size_t)1 << 14);
+        if constexpr (is_goldilocks<F>) s = upload(ctx, times_r(t16), &set.t.tw16k_inv_m, set.owned);   // Montgomery form
+        else s = upload(ctx, t16, &set.t.tw16k_inv, set.owned);
+        if (s) return s;
     }
-    set.t.tw4096_fwd = ctx->tw4096_fwd;
-    set.t.tw4096_inv = ctx->tw4096_inv;
-    set.t.tw4096_fwd_m = ctx->tw4096_fwd_m;
-    set.t.tw4096_inv_m = ctx->tw4096_inv_m;
-    u64 w = gl::two_adic_generator(log_n), wi = gl::inv(w);
-    size_t n = (size_t)1 << log_n;
-    size_t nhi = n > 1024 ? n / 1024 : 1;
-    u64 *lo_f, *hi_f, *lo_i, *hi_i;
-    gb_status s;
-    const std::vector<u64> vlo_f = powers(w, 1024), vhi_f = powers(gl::pow(w, 1024), nhi), vlo_i = powers(wi, 1024),
-                           vhi_i = powers(gl::pow(wi, 1024), nhi);
-    if ((s = upload(ctx, vlo_f, &lo_f, &set.owned))) return s;
-    if ((s = upload(ctx, vhi_f, &hi_f, &set.owned))) return s;
-    if ((s = upload(ctx, vlo_i, &lo_i, &set.owned))) return s;
-    if ((s = upload(ctx, vhi_i, &hi_i, &set.owned))) return s;
-    set.t.tw_lo_fwd = lo_f; set.t.tw_hi_fwd = hi_f; set.t.tw_lo_inv = lo_i; set.t.tw_hi_inv = hi_i;
-    set.t.n_inv = gl::inv((u64)n % gl::P);
-    set.t.tw_top_fwd = nullptr;
+    set.t.tw4096_fwd = tc.tw4096_fwd;
+    set.t.tw4096_inv = tc.tw4096_inv;
+    const T w = F::two_adic_generator(log_n), wi = F::inv(w);
+    const size_t n = (size_t)1 << log_n, nhi = n > 1024 ? n / 1024 : 1;
+    const std::vector<T> vlo_f = powers<F>(w, 1024), vhi_f = powers<F>(F::pow(w, 1024), nhi), vlo_i = powers<F>(wi, 1024),
+                         vhi_i = powers<F>(F::pow(wi, 1024), nhi);
+    if ((s = upload(ctx, vlo_f, &set.t.tw_lo_fwd, set.owned))) return s;
+    if ((s = upload(ctx, vhi_f, &set.t.tw_hi_fwd, set.owned))) return s;
+    if ((s = upload(ctx, vlo_i, &set.t.tw_lo_inv, set.owned))) return s;
+    if ((s = upload(ctx, vhi_i, &set.t.tw_hi_inv, set.owned))) return s;
+    set.t.n_inv = F::inv(F::enc(n % F::ORDER));
     if (set.t.outer_bits) {
         const u32 log_m = log_n - set.t.outer_bits;
-        std::vector<u64> top(256);
-        for (u32 j = 0; j < 256; j++) top[j] = gl::pow(w, (u64)bitrev32(j, 8) << (log_m - 8));
-        u64* t;
-        if ((s = upload(ctx, top, &t, &set.owned))) return s;
-        set.t.tw_top_fwd = t;
+        std::vector<T> top(256);
+        for (u32 j = 0; j < 256; j++) top[j] = F::pow(w, (u64)bitrev32(j, 8) << (log_m - 8));
+        if ((s = upload(ctx, top, &set.t.tw_top_fwd, set.owned))) return s;
     }
-    {
-        u64 *a, *b, *c, *d;
-        if ((s = upload(ctx, times_r(vlo_f), &a, &set.owned))) return s;
-        if ((s = upload(ctx, times_r(vhi_f), &b, &set.owned))) return s;
-        if ((s = upload(ctx, times_r(vlo_i), &c, &set.owned))) return s;
-        if ((s = upload(ctx, times_r(vhi_i), &d, &set.owned))) return s;
-        set.t.tw_lo_fwd_m = a; set.t.tw_hi_fwd_m = b; set.t.tw_lo_inv_m = c; set.t.tw_hi_inv_m = d;
-        set.t.n_inv_m = gl::to_mont_slow(set.t.n_inv);
+    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins of kernels_ntt16.hip
+        set.t.tw4096_fwd_m = tc.tw4096_fwd_m;
+        set.t.tw4096_inv_m = tc.tw4096_inv_m;
+        if ((s = upload(ctx, times_r(vlo_f), &set.t.tw_lo_fwd_m, set.owned))) return s;
+        if ((s = upload(ctx, times_r(vhi_f), &set.t.tw_hi_fwd_m, set.owned))) return s;
+        if ((s = upload(ctx, times_r(vlo_i), &set.t.tw_lo_inv_m, set.owned))) return s;
+        if ((s = upload(ctx, times_r(vhi_i), &set.t.tw_hi_inv_m, set.owned))) return s;
+        set.t.n_inv_m = GlF::cform(set.t.n_inv);
     }
-    auto res = ctx->gl_tables.emplace(log_n, std::move(set));
+    auto res = tc.tables.emplace(log_n, std::move(set));
     *out = &res.first->second.t;
     return GB_OK;
 }
@@ -429,167 +436,51 @@ gb_status ensure_big_work(gb_ctx* ctx, u32 log_n, u32 rate_bits, size_t es) {
     }
     return GB_OK;
 }
-gb_status gl_cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, u64 shift, bool inverse, const gbk::GlCosetTables** out) {
+template <class F>
+gb_status cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, typename F::T shift, bool inverse,
+                     const typename TableCache<F>::Cosets** out) {
+    typedef typename F::T T;
+    TableCache<F>& tc = cache<F>(ctx);
     auto key = std::make_tuple(log_n, rate_bits, shift, inverse ? 1 : 0);
-    auto it = ctx->gl_cosets.find(key);
-    if (it != ctx->gl_cosets.end()) {
+    auto it = tc.cosets.find(key);
+    if (it != tc.cosets.end()) {
         if (!inverse)   // (released by gb_ctx_trim)
-            if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(u64))) return sw;
+            if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(T))) return sw;
         *out = &it->second.t;
         return GB_OK;
     }
     size_t n = (size_t)1 << log_n;
     size_t nlo = n < 4096 ? n : 4096, nhi = n > 4096 ? n / 4096 : 1;
     u32 nc = 1u << rate_bits;
-    u64 wN = gl::two_adic_generator(log_n + rate_bits);
-    std::vector<u64> lo(nc * nlo), hi(nc * nhi);
+    T wN = F::two_adic_generator(log_n + rate_bits);
+    std::vector<T> lo(nc * nlo), hi(nc * nhi);
     for (u32 c = 0; c < nc; c++) {
-        u64 s = gl::mul(shift, gl::pow(wN, bitrev32(c, rate_bits)));
-        if (inverse) s = gl::inv(s);
-        std::vector<u64> pl = powers(s, nlo), ph = powers(gl::pow(s, 4096), nhi);
-        std::memcpy(&lo[c * nlo], pl.data(), nlo * sizeof(u64));
-        std::memcpy(&hi[c * nhi], ph.data(), nhi * sizeof(u64));
+        T s = F::mul(shift, F::pow(wN, bitrev32(c, rate_bits)));
+        if (inverse) s = F::inv(s);
+        std::vector<T> pl = powers<F>(s, nlo), ph = powers<F>(F::pow(s, 4096), nhi);
+        std::memcpy(&lo[c * nlo], pl.data(), nlo * sizeof(T));
+        std::memcpy(&hi[c * nhi], ph.data(), nhi * sizeof(T));
     }
-    GlCosetSet set;
+    typename TableCache<F>::template Owner<typename TableCache<F>::Cosets> set;
     set.t.rate_bits = rate_bits;
-    set.t.sub = nullptr; set.t.work = nullptr; set.t.work_bytes = nullptr;
+    gb_status s;
     // inverse tables are read as power tables only (the quotient's coset_ifft); the LDE kernels never see them
     if (const u32 K = gbk::ntt_outer_bits(log_n); K && !inverse) {   // sub-transforms of n / R rows on the shift s_c^R, R = 2^K (ntt_outer.hpp)
-        const gbk::GlCosetTables* sub;
-        if (gb_status s2 = gl_cosets_for(ctx, log_n - K, rate_bits, gl::pow(shift, (u64)1 << K), false, &sub)) return s2;
-        set.t.sub = sub;
-        if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(u64))) return sw;
+        if ((s = cosets_for<F>(ctx, log_n - K, rate_bits, F::pow(shift, (u64)1 << K), false, &set.t.sub))) return s;
+        if ((s = ensure_big_work(ctx, log_n, rate_bits, sizeof(T)))) return s;
         DeviceBuf& wb = ctx->big_work[big_work_level(log_n)];
         set.t.work = &wb.p; set.t.work_bytes = &wb.bytes;
     }
-    u64 *dlo, *dhi;
-    gb_status s;
-    if ((s = upload(ctx, lo, &dlo, &set.owned))) return s;
-    if ((s = upload(ctx, hi, &dhi, &set.owned))) return s;
-    set.t.pow_lo = dlo; set.t.pow_hi = dhi;
-    {
-        u64 *a, *b;
-        if ((s = upload(ctx, times_r(lo), &a, &set.owned))) return s;
-        if ((s = upload(ctx, times_r(hi), &b, &set.owned))) return s;
-        set.t.pow_lo_m = a; set.t.pow_hi_m = b;
+    if constexpr (!is_goldilocks<F>)
+        if (log_n == 22 && !inverse)   // BabyBear: the finer cosets of 2^20 rows (k_bb_lde_pa16x2w)
+            if ((s = cosets_for<F>(ctx, 20, rate_bits + 2, shift, false, &set.t.fine))) return s;
+    if ((s = upload(ctx, lo, &set.t.pow_lo, set.owned))) return s;
+    if ((s = upload(ctx, hi, &set.t.pow_hi, set.owned))) return s;
+    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins of kernels_ntt16.hip
+        if ((s = upload(ctx, times_r(lo), &set.t.pow_lo_m, set.owned))) return s;
+        if ((s = upload(ctx, times_r(hi), &set.t.pow_hi_m, set.owned))) return s;
     }
-    auto res = ctx->gl_cosets.emplace(key, std::move(set));
-    *out = &res.first->second.t;
-    return GB_OK;
-}
-
-// ---- BabyBear tables (Montgomery form) ----
-gb_status upload32(gb_ctx* ctx, const std::vector<u32>& host, u32** dev, std::vector<void*>* owned) {
-    void* p = nullptr;
-    HIP_TRY(ctx, hipMalloc(&p, host.size() * sizeof(u32)));
-    HIP_TRY(ctx, hipMemcpy(p, host.data(), host.size() * sizeof(u32), hipMemcpyHostToDevice));
-    *dev = static_cast<u32*>(p);
-    if (owned) owned->push_back(p);
-    return GB_OK;
-}
-std::vector<u32> bb_powers(u32 base_mont, size_t count) {
-    std::vector<u32> v(count);
-    u32 x = bb::R1;
-    for (size_t i = 0; i < count; i++) {
-        v[i] = x;
-        x = bb::mul(x, base_mont);
-    }
-    return v;
-}
-gb_status bb_tables_for(gb_ctx* ctx, u32 log_n, const gbk::BbNttTables** out) {
-    auto it = ctx->bb_tables.find(log_n);
-    if (it != ctx->bb_tables.end()) { *out = &it->second.t; return GB_OK; }
-    gb_status s;
-    if (!ctx->bb_tw4096_fwd) {
-        u32 w = bb::two_adic_generator(12);
-        if ((s = upload32(ctx, bb_powers(w, 4096), &ctx->bb_tw4096_fwd, nullptr))) return s;
-        if ((s = upload32(ctx, bb_powers(bb::inv(w), 4096), &ctx->bb_tw4096_inv, nullptr))) return s;
-    }
-    BbTableSet set;
-    set.t.log_n = log_n;
-    set.t.sub = set.t.wide = nullptr;
-    set.t.tw16k_inv = nullptr;
-    set.t.outer_bits = gbk::ntt_outer_bits(log_n);
-    if (set.t.outer_bits) {
-        const gbk::BbNttTables* sub;
-        if (gb_status s2 = bb_tables_for(ctx, log_n - set.t.outer_bits, &sub)) return s2;
-        set.t.sub = sub;
-    } else if (log_n > 20) {
-        if (log_n == 22) {   // the strided LDE pass of 2^22 rows works with the 2^20-row twiddles (k_bb_lde_pa16x2w)
-            const gbk::BbNttTables* w20;
-            if (gb_status s2 = bb_tables_for(ctx, 20, &w20)) return s2;
-            set.t.wide = w20;
-        }
-        u32* t16;
-        if (gb_status s2 = upload32(ctx, bb_powers(bb::inv(bb::two_adic_generator(14)), (size_t)1 << 14), &t16, &set.owned)) return s2;
-        set.t.tw16k_inv = t16;
-    }
-    set.t.tw4096_fwd = ctx->bb_tw4096_fwd;
-    set.t.tw4096_inv = ctx->bb_tw4096_inv;
-    u32 w = bb::two_adic_generator(log_n), wi = bb::inv(w);
-    size_t n = (size_t)1 << log_n, nhi = n > 1024 ? n / 1024 : 1;
-    u32 *lo_f, *hi_f, *lo_i, *hi_i;
-    if ((s = upload32(ctx, bb_powers(w, 1024), &lo_f, &set.owned))) return s;
-    if ((s = upload32(ctx, bb_powers(bb::pow(w, 1024), nhi), &hi_f, &set.owned))) return s;
-    if ((s = upload32(ctx, bb_powers(wi, 1024), &lo_i, &set.owned))) return s;
-    if ((s = upload32(ctx, bb_powers(bb::pow(wi, 1024), nhi), &hi_i, &set.owned))) return s;
-    set.t.tw_lo_fwd = lo_f; set.t.tw_hi_fwd = hi_f; set.t.tw_lo_inv = lo_i; set.t.tw_hi_inv = hi_i;
-    set.t.n_inv = bb::inv(bb::to_mont((u32)(n % bb::P)));
-    set.t.tw_top_fwd = nullptr;
-    if (set.t.outer_bits) {
-        const u32 log_m = log_n - set.t.outer_bits;
-        std::vector<u32> top(256);
-        for (u32 j = 0; j < 256; j++) top[j] = bb::pow(w, (u64)bitrev32(j, 8) << (log_m - 8));
-        u32* t;
-        if ((s = upload32(ctx, top, &t, &set.owned))) return s;
-        set.t.tw_top_fwd = t;
-    }
-    auto res = ctx->bb_tables.emplace(log_n, std::move(set));
-    *out = &res.first->second.t;
-    return GB_OK;
-}
-gb_status bb_cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, u32 shift_mont, bool inverse, const gbk::BbCosetTables** out) {
-    auto key = std::make_tuple(log_n, rate_bits, shift_mont, inverse ? 1 : 0);
-    auto it = ctx->bb_cosets.find(key);
-    if (it != ctx->bb_cosets.end()) {
-        if (!inverse)
-            if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(u32))) return sw;
-        *out = &it->second.t;
-        return GB_OK;
-    }
-    size_t n = (size_t)1 << log_n;
-    size_t nlo = n < 4096 ? n : 4096, nhi = n > 4096 ? n / 4096 : 1;
-    u32 nc = 1u << rate_bits;
-    u32 wN = bb::two_adic_generator(log_n + rate_bits);
-    std::vector<u32> lo(nc * nlo), hi(nc * nhi);
-    for (u32 c = 0; c < nc; c++) {
-        u32 s = bb::mul(shift_mont, bb::pow(wN, bitrev32(c, rate_bits)));
-        if (inverse) s = bb::inv(s);
-        std::vector<u32> pl = bb_powers(s, nlo), ph = bb_powers(bb::pow(s, 4096), nhi);
-        std::memcpy(&lo[c * nlo], pl.data(), nlo * sizeof(u32));
-        std::memcpy(&hi[c * nhi], ph.data(), nhi * sizeof(u32));
-    }
-    BbCosetSet set;
-    set.t.rate_bits = rate_bits;
-    set.t.sub = set.t.fine = nullptr; set.t.work = nullptr; set.t.work_bytes = nullptr;
-    if (const u32 K = gbk::ntt_outer_bits(log_n); K && !inverse) {
-        const gbk::BbCosetTables* sub;
-        if (gb_status s2 = bb_cosets_for(ctx, log_n - K, rate_bits, bb::pow(shift_mont, (u64)1 << K), false, &sub)) return s2;
-        set.t.sub = sub;
-        if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(u32))) return sw;
-        DeviceBuf& wb = ctx->big_work[big_work_level(log_n)];
-        set.t.work = &wb.p; set.t.work_bytes = &wb.bytes;
-    } else if (log_n == 22 && !inverse) {   // the finer cosets of 2^20 rows (k_bb_lde_pa16x2w)
-        const gbk::BbCosetTables* fine;
-        if (gb_status s2 = bb_cosets_for(ctx, 20, rate_bits + 2, shift_mont, false, &fine)) return s2;
-        set.t.fine = fine;
-    }
-    u32 *dlo, *dhi;
-    gb_status s;
-    if ((s = upload32(ctx, lo, &dlo, &set.owned))) return s;
-    if ((s = upload32(ctx, hi, &dhi, &set.owned))) return s;
-    set.t.pow_lo = dlo; set.t.pow_hi = dhi;
-    auto res = ctx->bb_cosets.emplace(key, std::move(set));
+    auto res = tc.cosets.emplace(key, std::move(set));
     *out = &res.first->second.t;
     return GB_OK;
 }
@@ -826,21 +717,103 @@ struct SegKeep {
     size_t bytes = 0;
     u32 start = 0;           // first column of the last segment
 };
-// Upload chunks of a host batch, in columns: 4, 4, 8, then `full`.  The GPU's per-column work (transform + leaf hashing) is slower
-// than PCIe delivers columns, so after a short ramp the upload is hidden - what is not hidden is the wait for the FIRST columns:
-// with 4 + 4 the first 8-column hashing segment starts after ~1.5 ms of a 2^20-row Goldilocks witness (4 + 12: ~3.5 ms).
-static inline size_t first_chunks(size_t c0, size_t full) { return c0 < 8 ? 4 : c0 < 16 ? 8 : full; }
+// per-field host glue: transcript hash, NTT / Merkle launchers, and what commit() does differently per field
+template <class F>
+struct Host;
+template <>
+struct Host<GlF> {
+    typedef poseidon_gl_host::Challenger Challenger;
+    typedef gbk::GlNttTables Tables;
+    typedef gbk::GlCosetTables Cosets;
+    static void hash_no_pad(const u64* in, size_t n, u64* out) { poseidon_gl_host::hash_no_pad(in, n, out); }
+    static void intt(const u64* src, u64* dst, u64* scratch, size_t ncols, const Tables& t, hipStream_t st) {
+        gbk::gl_intt_columns(src, dst, scratch, ncols, t, st);
+    }
+    static void lde(const u64* coeffs, u64* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
+        gbk::gl_lde_columns(coeffs, out, ncols, t, c, st);
+    }
+    static void merkle_leaves(const u64* lde, u64 N, u32 width, u64* levels, hipStream_t st) {
+        gbk::gl_merkle_leaves(lde, N, width, N, levels, st);
+    }
+    static void merkle_leaves_segment(const u64* lde, u64 N, u32 c_begin, u32 c_end, u64* state, bool last, u32 next_cols, u64* levels,
+                                      hipStream_t st) {
+        gbk::gl_merkle_leaves_segment(lde, N, c_begin, c_end, N, state, last, next_cols, levels, st);
+    }
+    static void merkle_level(const u64* in, u64* out, u64 num_out, hipStream_t st) { gbk::gl_merkle_level(in, out, num_out, st); }
+    static void to_device_form(const u64* src, u64* dst, size_t count, hipStream_t st) {   // canonical words ARE the device form
+        if (src != dst) (void)hipMemcpyAsync(dst, src, count * sizeof(u64), hipMemcpyDeviceToDevice, st);
+    }
+    static void p3_to_device_form(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }   // GB_INPUT_P3_REPR words
+    static u64 p3_to_canonical(u64 x) { return x >= gl::P ? x - gl::P : x; }
+    static void p3_to_canonical_dev(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }
+    static bool intt_canonical(u64*, u64*, u64*, size_t, const Tables&, hipStream_t, size_t = 0) { return false; }   // device form IS canonical
+    static void from_device_form(u64*, size_t, hipStream_t) {}
+    // canonical columns of 2^bits points -> dst in device form, dst[j] = src[bitrev_bits(j)] (salt columns -> leaf order)
+    static void bitrev_copy_to_device_form(const u64* src, u64* dst, u32 bits, size_t ncols, hipStream_t st) {
+        gbk::u64_bitrev_copy(src, dst, bits, ncols, st);
+    }
+    static constexpr bool device_form_is_canonical = true;
+    // commit(): columns of the first upload chunk of a host batch (4, 4, 8, then 16 columns), fewest columns staged at all, and
+    // whether its scratch is reserved up front ([host input or salts | transform scratch]) or grown to what each step needs
+    static constexpr size_t first_chunk = 4, min_staged_cols = 1;
+    static constexpr bool scratch_up_front = false;
+};
+template <>
+struct Host<BbF> {
+    typedef poseidon2_bb_host::Challenger Challenger;
+    typedef gbk::BbNttTables Tables;
+    typedef gbk::BbCosetTables Cosets;
+    static void hash_no_pad(const u32* in, size_t n, u32* out) { poseidon2_bb_host::hash_no_pad(in, n, out); }
+    static void intt(const u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st) {
+        gbk::bb_intt_columns(src, dst, scratch, ncols, t, st);
+    }
+    static void lde(const u32* coeffs, u32* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
+        gbk::bb_lde_columns(coeffs, out, ncols, t, c, st);
+    }
+    static void merkle_leaves(const u32* lde, u64 N, u32 width, u32* levels, hipStream_t st) {
+        gbk::bb_merkle_leaves(lde, N, width, N, levels, st);
+    }
+    static void merkle_leaves_segment(const u32* lde, u64 N, u32 c_begin, u32 c_end, u32* state, bool last, u32 next_cols, u32* levels,
+                                      hipStream_t st) {
+        gbk::bb_merkle_leaves_segment(lde, N, c_begin, c_end, N, state, last, next_cols, levels, st);
+    }
+    static void merkle_level(const u32* in, u32* out, u64 num_out, hipStream_t st) { gbk::bb_merkle_level(in, out, num_out, st); }
+    static void to_device_form(const u32* src, u32* dst, size_t count, hipStream_t st) { gbk::bb_to_mont(src, dst, count, st); }
+    static void p3_to_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); }   // p3's MontyField31 words ARE the device form (reduced below p: they are a caller's memory)
+    static u32 p3_to_canonical(u32 x) { return bb::from_mont(x); }
+    static void p3_to_canonical_dev(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); gbk::bb_from_mont(p, p, count, st); }
+    // values -> coefficients of columns held in CANONICAL form (what commit() leaves of a host witness beyond the routed wires);
+    // the first mont_cols of them are left in device form in `src`.  false: the shape is not covered, nothing was launched
+    static bool intt_canonical(u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st, size_t mont_cols = 0) {
+        return gbk::bb_intt_columns_canonical(src, dst, scratch, ncols, mont_cols, t, st);
+    }
+    static void from_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_from_mont(p, p, count, st); }
+    static void bitrev_copy_to_device_form(const u32* src, u32* dst, u32 bits, size_t ncols, hipStream_t st) {
+        gbk::bb_bitrev_copy_to_mont(src, dst, bits, ncols, st);
+    }
+    static constexpr bool device_form_is_canonical = false;
+    // 4-byte words: the same bytes per upload chunk as Goldilocks' 4, 4, 8 (8, 8, 16, then 16 columns)
+    static constexpr size_t first_chunk = 8, min_staged_cols = 4;
+    static constexpr bool scratch_up_front = true;
+};
 
-gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_t log_n, uint32_t rate_bits,
-                 uint32_t cap_height, const void* salts, uint32_t flags, bool is_coeffs, gb_batch** out, void* values_dev = nullptr,
-                 SegKeep* keep = nullptr, size_t* values_mont_cols = nullptr) {
+// Upload chunks of a host batch, in columns: c, c, 2c, then 16 (c = Host<F>::first_chunk).  The GPU's per-column work (transform +
+// leaf hashing) is slower than PCIe delivers columns, so after a short ramp the upload is hidden - what is not hidden is the wait for
+// the FIRST columns: with 4 + 4 the first 8-column hashing segment starts after ~1.5 ms of a 2^20-row Goldilocks witness (4 + 12: ~3.5 ms).
+static inline size_t upload_chunk(size_t c0, size_t c) { return c0 < 2 * c ? c : c0 < 4 * c ? 2 * c : 16; }
+
+template <class F>
+gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, const void* salts,
+                 uint32_t flags, bool is_coeffs, gb_batch** out, void* values_dev = nullptr, SegKeep* keep = nullptr,
+                 size_t* values_mont_cols = nullptr) {
     // values_mont_cols (BabyBear, with values_dev): in - how many leading columns of values_dev the caller reads as device-form
     // VALUES afterwards; out - how many leading columns of values_dev ARE in device (Montgomery) form, the rest being canonical as
     // uploaded (the inverse transform takes canonical input where its radix-16 kernels cover the shape; otherwise all of them)
+    typedef typename F::T T;
+    typedef Host<F> HF;
     if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null ctx");
     if (!out) return fail(ctx, GB_ERR_INVALID, "null out");
     *out = nullptr;
-    if (field != GB_GOLDILOCKS && field != GB_BABYBEAR) return fail(ctx, GB_ERR_INVALID, "unknown field tag");
     if (ncols == 0) return fail(ctx, GB_ERR_INVALID, "from_values/from_coeffs needs at least one polynomial (oracle.rs:101)");
     if (!cols) return fail(ctx, GB_ERR_INVALID, "null cols");
     if (cols.ptrs)
@@ -850,7 +823,7 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
     // p3-baby-bear / p3-monty-31: x 2^32 mod p) - a host-memory convention
     const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
     if (p3 && (flags & GB_INPUT_DEVICE)) return fail(ctx, GB_ERR_INVALID, "GB_INPUT_P3_REPR describes host memory; device inputs are canonical");
-    if (log_n + rate_bits > (field == GB_GOLDILOCKS ? 32u : 27u))
+    if (log_n + rate_bits > F::TWO_ADICITY)
         return fail(ctx, GB_ERR_INVALID, "LDE size exceeds the field's two-adicity (32 Goldilocks / 27 BabyBear)");
     if (cap_height > log_n + rate_bits)
         return fail(ctx, GB_ERR_INVALID, "cap_height should be at most log2(leaves.len()) (merkle_tree.rs:154-157)");
@@ -864,7 +837,7 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
 
     gb_batch* b = new (std::nothrow) gb_batch();
     if (!b) return fail(ctx, GB_ERR_OOM, "host allocation failed");
-    b->ctx = ctx; b->field = field; b->log_n = log_n; b->rate_bits = rate_bits; b->cap_height = cap_height;
+    b->ctx = ctx; b->field = F::TAG; b->log_n = log_n; b->rate_bits = rate_bits; b->cap_height = cap_height;
     b->nsalt = nsalt; b->ncols = ncols;
     auto cleanup = [&](gb_status s) {
         gb_batch_free(b);
@@ -872,9 +845,9 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
     };
 
     void* p = nullptr;
-    const size_t es = esize(field);
-    b->coeffs_bytes = ncols * n * es;
-    b->lde_bytes = width * N * es;
+    const size_t in_bytes = ncols * n * sizeof(T), salt_bytes = nsalt * N * sizeof(T);
+    b->coeffs_bytes = in_bytes;
+    b->lde_bytes = width * N * sizeof(T);
     b->levels_bytes = 2 * N * 4 * sizeof(u64);  // 32-byte digests for both hashers
     if (pool_alloc(ctx, b->coeffs_bytes, &p) != hipSuccess) return cleanup(fail(ctx, GB_ERR_OOM, "hipMalloc coeffs"));
     b->coeffs = (u64*)p;
@@ -882,6 +855,9 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
     b->lde = (u64*)p;
     if (pool_alloc(ctx, b->levels_bytes, &p) != hipSuccess) return cleanup(fail(ctx, GB_ERR_OOM, "hipMalloc digests"));
     b->levels = (u64*)p;
+    T* const coeffs = (T*)b->coeffs;
+    T* const lde = (T*)b->lde;
+    T* const lv = (T*)b->levels;
 
     gb_status s;
     hipStream_t st = ctx->stream;
@@ -891,12 +867,12 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
         ~GatherGuard() { if (p) pool_free(ctx, p, bytes); }   // stream-ordered reuse: every reader is enqueued before the next taker
     } gather{ctx};
     if (dev_in && cols.ptrs) {
-        gather.bytes = ncols * n * es;
+        gather.bytes = in_bytes;
         if (pool_alloc(ctx, gather.bytes, &gather.p) != hipSuccess) { gather.p = nullptr; return cleanup(fail(ctx, GB_ERR_OOM, "hipMalloc column gather")); }
-        if (!copy_columns(cols, ncols, n * es, gather.p, hipMemcpyDeviceToDevice, st)) return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
+        if (!copy_columns(cols, ncols, n * sizeof(T), gather.p, hipMemcpyDeviceToDevice, st)) return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
         cols = ColSrc(gather.p);
     }
-    const bool pinned = !dev_in && all_pinned(cols, ncols, n * es);
+    const bool pinned = !dev_in && all_pinned(cols, ncols, n * sizeof(T));
     // Host input of a big batch: the leaf sponges run in segments of SEG columns as the columns arrive (chunked upload below), so
     // that the hashing - most of a commitment's time - overlaps the PCIe transfer instead of waiting for its end; the sponge state
     // waits in `seg_state` between segments (kernels_merkle.hip / kernels_bb.hip: k_*_merkle_leaves).
@@ -923,8 +899,8 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
     u32 last_seg_start = 0;
     for (u32 sz = seg_size(0); last_seg_start + sz < ncols; sz = seg_size(last_seg_start)) last_seg_start += sz;
     const u32 kf_final = std::min<u32>(8u, (u32)(width - last_seg_start));
-    const size_t seg_rows = (field == GB_GOLDILOCKS ? 4 : 8) + (8 - kf_final);
-    const size_t seg_state_bytes = seg_rows * N * (field == GB_GOLDILOCKS ? sizeof(u64) : sizeof(u32));
+    const size_t seg_rows = F::H + (8 - kf_final);
+    const size_t seg_state_bytes = seg_rows * N * sizeof(T);
     struct SegGuard {
         gb_ctx* ctx; void** p; size_t bytes;
         ~SegGuard() { if (*p) pool_free(ctx, *p, bytes); }
@@ -934,183 +910,113 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
             if (!seg_state && pool_alloc(ctx, seg_state_bytes, &seg_state) != hipSuccess) { seg_state = nullptr; return false; }
             Scope sm(ctx, "build Merkle tree");
             Scope sl(ctx, "hash leaves");
-            const u32 next_cols = (u32)(width - (seg_done + sz));
-            if (field == GB_GOLDILOCKS)
-                gbk::gl_merkle_leaves_segment(b->lde, N, seg_done, seg_done + sz, N, (u64*)seg_state, false, next_cols, b->levels, st);
-            else
-                gbk::bb_merkle_leaves_segment((const u32*)b->lde, N, seg_done, seg_done + sz, N, (u32*)seg_state, false, next_cols,
-                                              (u32*)b->levels, st);
+            HF::merkle_leaves_segment(lde, N, seg_done, seg_done + sz, (T*)seg_state, false, (u32)(width - (seg_done + sz)), lv, st);
             seg_done += sz;
         }
         return true;
     };
-    if (field == GB_BABYBEAR) {
-        // same flow over u32 Montgomery words; inputs are converted on the way in
-        const gbk::BbNttTables* bt;
-        const gbk::BbCosetTables* bc;
-        if ((s = bb_tables_for(ctx, log_n, &bt))) return cleanup(s);
-        if ((s = bb_cosets_for(ctx, log_n, rate_bits, bb::to_mont(bb::GENERATOR), false, &bc))) return cleanup(s);
-        u32* coeffs = (u32*)b->coeffs;
-        u32* lde = (u32*)b->lde;
-        const size_t in_bytes = ncols * n * 4, scr_bytes = std::max(in_bytes, (size_t)nsalt * N * 4);
-        if ((s = ensure(ctx, ctx->scratch, 2 * scr_bytes))) return cleanup(s);
-        u32* scr = (u32*)ctx->scratch.p;
-        const u32* in_dev = static_cast<const u32*>(cols.base);
-        const bool staged = !dev_in && !is_coeffs && log_n >= 12 && ncols >= 4;
-        if (staged) {
-            // column chunks: H2D straight into values_dev / the coefficient block (copy stream) -> Montgomery form in place ->
-            // inverse NTT -> LDE -> the leaf-sponge segments that have all their columns
-            const size_t per = 16;
-            u32* vals = values_dev ? static_cast<u32*>(values_dev) : coeffs;  // without a taker the values are transformed in place
-            u32* ntt_scr = scr + scr_bytes / 4;
-            EventList evs;
-            bool ok = true;
-            hipEvent_t e0 = evs.make(ok);                           // values_dev / coeffs may be a pool block still in use on `st`
-            ok = ok && hipEventRecord(e0, st) == hipSuccess && hipStreamWaitEvent(ctx->copy_stream, e0, 0) == hipSuccess;
-            for (size_t c0 = 0, cc = 0; c0 < ncols && ok; c0 += cc) {
-                cc = std::min(c0 < 32 ? 2 * first_chunks(c0 / 2, per / 2) : per, ncols - c0);   // 4-byte words: the same bytes per chunk as Goldilocks' 4, 4, 8
-                hipEvent_t copied = evs.make(ok);
-                ok = ok && upload_columns(ctx, cols, pinned, c0, cc, n * 4, vals + c0 * n) &&
-                     hipEventRecord(copied, ctx->copy_stream) == hipSuccess && hipStreamWaitEvent(st, copied, 0) == hipSuccess;
-                if (!ok) break;
-                const size_t want_mont = !values_dev ? 0 : values_mont_cols ? *values_mont_cols : ncols;
-                bool direct;
-                if (p3) {   // Montgomery words as they are in the host's memory: nothing to convert, but nothing to trust either
-                    gbk::bb_reduce_words(vals + c0 * n, cc * n, st);
-                    Scope sc(ctx, "IFFT");
-                    gbk::bb_intt_columns(vals + c0 * n, coeffs + c0 * n, ntt_scr, cc, *bt, st);
-                    if (values_mont_cols) *values_mont_cols = ncols;
-                    direct = true;
-                } else {
-                    Scope sc(ctx, "IFFT");
-                    direct = gbk::bb_intt_columns_canonical(vals + c0 * n, coeffs + c0 * n, ntt_scr, cc, want_mont > c0 ? want_mont - c0 : 0, *bt, st);
-                }
-                if (!direct) {
-                    gbk::bb_to_mont(vals + c0 * n, vals + c0 * n, cc * n, st);
-                    { Scope sc(ctx, "IFFT"); gbk::bb_intt_columns(vals + c0 * n, coeffs + c0 * n, ntt_scr, cc, *bt, st); }
-                    if (values_mont_cols) *values_mont_cols = ncols;
-                }
-                { Scope sc(ctx, "FFT + blinding"); gbk::bb_lde_columns(coeffs + c0 * n, lde + c0 * N, cc, *bt, *bc, st); }
-                if (!hash_ready_segments(c0 + cc)) return cleanup(fail(ctx, GB_ERR_OOM, "sponge state"));
-            }
-            if (!ok) return cleanup(fail(ctx, GB_ERR_HIP, "chunked upload of the input columns failed"));
-        } else if (!dev_in) {
-            if (!copy_columns(cols, ncols, n * 4, scr, hipMemcpyHostToDevice, st))
-                return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
-            mark_upload(ctx);
-            in_dev = scr;
-        }
-        bool direct_intt = false;
-        if (staged) {
-        } else if ((flags & GB_INPUT_DEVICE_FORM) || p3) {  // already Montgomery words on the device (prover-internal; a host's p3 words)
-            if (hipMemcpyAsync(coeffs, in_dev, in_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
-            if (p3) gbk::bb_reduce_words(coeffs, ncols * n, st);   // a host's words (the library's own device form is in range)
-        } else if (!is_coeffs && log_n >= 16 && log_n <= gbk::NTT_NATIVE_LOG) {
-            // canonical values on the device (a resident witness, a small host batch): the inverse transform takes them as they are
-            Scope sc(ctx, "IFFT");
-            (void)gbk::bb_intt_columns_canonical(const_cast<u32*>(in_dev), coeffs, scr + scr_bytes / 4, ncols, 0, *bt, st);
-            direct_intt = true;
-        } else {
-            gbk::bb_to_mont(in_dev, coeffs, ncols * n, st);
-        }
-        if (!is_coeffs && !staged && !direct_intt) {
-            Scope sc(ctx, "IFFT");
-            gbk::bb_intt_columns(coeffs, coeffs, scr + scr_bytes / 4, ncols, *bt, st);
-        }
-        {
-            Scope sc(ctx, "FFT + blinding");
-            if (!staged) gbk::bb_lde_columns(coeffs, lde, ncols, *bt, *bc, st);
-            if (nsalt) {
-                const u32* sdev = static_cast<const u32*>(salts);
-                if (!dev_in) {
-                    if (hipMemcpyAsync(scr, salts, (size_t)nsalt * N * 4, hipMemcpyHostToDevice, st) != hipSuccess)
-                        return cleanup(fail(ctx, GB_ERR_HIP, "copy of salts failed"));
-                    mark_upload(ctx);
-                    if (p3) { gbk::bb_reduce_words(scr, (size_t)nsalt * N, st); gbk::bb_from_mont(scr, scr, (size_t)nsalt * N, st); }   // the salt columns are F::rand_vec words too
-                    sdev = scr;
-                }
-                gbk::bb_bitrev_copy_to_mont(sdev, lde + ncols * N, log_N, nsalt, st);
-            }
-        }
-        {
-            Scope sc(ctx, "build Merkle tree");
-            u32* lv = (u32*)b->levels;
-            {
-                Scope sl(ctx, "hash leaves");
-                if (!seg_done && keep_split) {   // device input whose last column segment may have to be redone: hash in two segments
-                    if (pool_alloc(ctx, seg_state_bytes, &seg_state) != hipSuccess) { seg_state = nullptr; return cleanup(fail(ctx, GB_ERR_OOM, "sponge state")); }
-                    gbk::bb_merkle_leaves_segment(lde, N, 0, last_seg_start, N, (u32*)seg_state, false, (u32)(width - last_seg_start), lv, st);
-                    seg_done = last_seg_start;
-                }
-                if (seg_done) gbk::bb_merkle_leaves_segment(lde, N, seg_done, (u32)width, N, (u32*)seg_state, true, 0, lv, st);
-                else gbk::bb_merkle_leaves(lde, N, (u32)width, N, lv, st);
-            }
-            for (u32 k = 0; k < log_N - cap_height; k++)
-                gbk::bb_merkle_level(lv + 8 * level_offset(N, k), lv + 8 * level_offset(N, k + 1), N >> (k + 1), st);
-        }
-        if (hipGetLastError() != hipSuccess) return cleanup(fail(ctx, GB_ERR_HIP, "kernel launch failed"));
-        if (keep && seg_done && seg_state) { *keep = SegKeep{seg_state, seg_state_bytes, seg_done}; seg_state = nullptr; }
-        *out = b;
+    const typename HF::Tables* tabs;
+    const typename HF::Cosets* cos;
+    if ((s = tables_for<F>(ctx, log_n, &tabs))) return cleanup(s);
+    if ((s = cosets_for<F>(ctx, log_n, rate_bits, F::generator(), false, &cos))) return cleanup(s);
+    // scratch (ctx->scratch): [host input or salts | transform scratch], scr_bytes each where the field reserves it up front; else one
+    // block, grown to what each step needs
+    const size_t scr_bytes = HF::scratch_up_front ? std::max(in_bytes, salt_bytes) : 0;
+    if ((s = ensure(ctx, ctx->scratch, 2 * scr_bytes))) return cleanup(s);
+    auto scratch = [&](size_t off, size_t bytes, T** at) -> gb_status {
+        if (!HF::scratch_up_front)
+            if (gb_status e = ensure(ctx, ctx->scratch, bytes)) return e;
+        *at = (T*)((char*)ctx->scratch.p + off);
         return GB_OK;
-    }
-    const gbk::GlNttTables* tabs;
-    const gbk::GlCosetTables* cos;
-    if ((s = gl_tables_for(ctx, log_n, &tabs))) return cleanup(s);
-    if ((s = gl_cosets_for(ctx, log_n, rate_bits, gl::GENERATOR, false, &cos))) return cleanup(s);
+    };
+    T* ntt_scr = nullptr;
 
-    const u64* src = static_cast<const u64*>(cols.base);
-    const bool staged = !dev_in && !is_coeffs && log_n >= 12;
+    const bool staged = !dev_in && !is_coeffs && log_n >= 12 && ncols >= HF::min_staged_cols;
     if (staged) {
-        // column chunks: H2D into values_dev on the copy stream, then (main stream, behind an event) inverse NTT and LDE of the chunk
-        const size_t CH = 16;
-        u64* vals = values_dev ? static_cast<u64*>(values_dev) : b->coeffs;  // without a taker the values are transformed in place
-        if ((s = ensure(ctx, ctx->scratch, CH * n * sizeof(u64)))) return cleanup(s);
+        // column chunks: H2D into values_dev / the coefficient block on the copy stream, then (main stream, behind an event) device
+        // form -> inverse NTT -> LDE of the chunk -> the leaf-sponge segments that have all their columns
+        T* vals = values_dev ? static_cast<T*>(values_dev) : coeffs;  // without a taker the values are transformed in place
+        if ((s = scratch(scr_bytes, 16 * n * sizeof(T), &ntt_scr))) return cleanup(s);
         EventList evs;
         bool ok = true;
-        hipEvent_t e0 = evs.make(ok);                               // values_dev may be a pool block still in use on `st`
+        hipEvent_t e0 = evs.make(ok);                               // values_dev / coeffs may be a pool block still in use on `st`
         ok = ok && hipEventRecord(e0, st) == hipSuccess && hipStreamWaitEvent(ctx->copy_stream, e0, 0) == hipSuccess;
         for (size_t c0 = 0, cc = 0; c0 < ncols && ok; c0 += cc) {
-            cc = std::min(first_chunks(c0, CH), ncols - c0);
+            cc = std::min(upload_chunk(c0, HF::first_chunk), ncols - c0);
             hipEvent_t copied = evs.make(ok);
-            ok = ok && upload_columns(ctx, cols, pinned, c0, cc, n * sizeof(u64), vals + c0 * n) &&
+            ok = ok && upload_columns(ctx, cols, pinned, c0, cc, n * sizeof(T), vals + c0 * n) &&
                  hipEventRecord(copied, ctx->copy_stream) == hipSuccess && hipStreamWaitEvent(st, copied, 0) == hipSuccess;
             if (!ok) break;
-            if (p3) gbk::gl_canonicalize(vals + c0 * n, cc * n, st);   // p3-goldilocks keeps any u64 representative in memory
-            { Scope sc(ctx, "IFFT"); gbk::gl_intt_columns(vals + c0 * n, b->coeffs + c0 * n, (u64*)ctx->scratch.p, cc, *tabs, st); }
-            { Scope sc(ctx, "FFT + blinding"); gbk::gl_lde_columns(b->coeffs + c0 * n, b->lde + c0 * N, cc, *tabs, *cos, st); }
+            T* const v = vals + c0 * n;
+            bool direct = false;   // coefficients already: the inverse transform took the canonical values as they are
+            if (p3) {   // the host's words of the field types: nothing to convert, but nothing to trust either
+                HF::p3_to_device_form(v, cc * n, st);
+            } else if (!HF::device_form_is_canonical) {
+                const size_t want_mont = !values_dev ? 0 : values_mont_cols ? *values_mont_cols : ncols;
+                { Scope sc(ctx, "IFFT"); direct = HF::intt_canonical(v, coeffs + c0 * n, ntt_scr, cc, *tabs, st, want_mont > c0 ? want_mont - c0 : 0); }
+                if (!direct) HF::to_device_form(v, v, cc * n, st);
+            }
+            if (!direct) {
+                { Scope sc(ctx, "IFFT"); HF::intt(v, coeffs + c0 * n, ntt_scr, cc, *tabs, st); }
+                if (values_mont_cols) *values_mont_cols = ncols;
+            }
+            { Scope sc(ctx, "FFT + blinding"); HF::lde(coeffs + c0 * n, lde + c0 * N, cc, *tabs, *cos, st); }
             if (!hash_ready_segments(c0 + cc)) return cleanup(fail(ctx, GB_ERR_OOM, "sponge state"));
         }
         if (!ok) return cleanup(fail(ctx, GB_ERR_HIP, "chunked upload of the input columns failed"));
-    } else if (!dev_in || is_coeffs) {
-        // host input, or coefficients the batch must own a copy of
-        if (!copy_columns(cols, ncols, n * sizeof(u64), b->coeffs, dev_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
-            return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
-        if (!dev_in) mark_upload(ctx);
-        if (p3) gbk::gl_canonicalize(b->coeffs, ncols * n, st);
-        src = b->coeffs;
-    }
-    if (!is_coeffs && !staged) {
-        if ((s = ensure(ctx, ctx->scratch, ncols * n * sizeof(u64)))) return cleanup(s);
-        Scope sc(ctx, "IFFT");
-        gbk::gl_intt_columns(src, b->coeffs, (u64*)ctx->scratch.p, ncols, *tabs, st);
+    } else {
+        const T* src = static_cast<const T*>(cols.base);
+        if (!dev_in) {   // host input in one copy: into the coefficient block where it is in device form already, else into scratch
+            T* land = coeffs;
+            if (!HF::device_form_is_canonical && (s = scratch(0, in_bytes, &land))) return cleanup(s);
+            if (!copy_columns(cols, ncols, n * sizeof(T), land, hipMemcpyHostToDevice, st))
+                return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
+            mark_upload(ctx);
+            src = land;
+        }
+        bool direct = false;
+        if (HF::device_form_is_canonical || (flags & GB_INPUT_DEVICE_FORM) || p3) {
+            // in device form already (prover-internal; a host's p3 words once reduced).  The coefficient block gets its own copy, except
+            // for device values where the device form is canonical: their inverse transform reads them in place
+            if (src != coeffs && (is_coeffs || !HF::device_form_is_canonical)) {
+                if (hipMemcpyAsync(coeffs, src, in_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
+                src = coeffs;
+            }
+            if (p3) HF::p3_to_device_form(coeffs, ncols * n, st);   // a host's words (the library's own device form is in range)
+        } else if (!is_coeffs && log_n >= 16 && log_n <= gbk::NTT_NATIVE_LOG) {
+            // canonical values on the device (a resident witness, a small host batch): the inverse transform takes them as they are
+            if ((s = scratch(scr_bytes, in_bytes, &ntt_scr))) return cleanup(s);
+            Scope sc(ctx, "IFFT");
+            (void)HF::intt_canonical(const_cast<T*>(src), coeffs, ntt_scr, ncols, *tabs, st);
+            direct = true;
+        } else {
+            HF::to_device_form(src, coeffs, ncols * n, st);
+            src = coeffs;
+        }
+        if (!is_coeffs && !direct) {
+            if ((s = scratch(scr_bytes, in_bytes, &ntt_scr))) return cleanup(s);
+            Scope sc(ctx, "IFFT");
+            HF::intt(src, coeffs, ntt_scr, ncols, *tabs, st);
+        }
     }
     {
         Scope sc(ctx, "FFT + blinding");
-        if (!staged) gbk::gl_lde_columns(b->coeffs, b->lde, ncols, *tabs, *cos, st);
+        if (!staged) HF::lde(coeffs, lde, ncols, *tabs, *cos, st);
         if (nsalt) {
             // salt columns arrive in LDE-point order (like lde_values' extra columns, oracle.rs:144-148)
             // and are stored, like everything else, in leaf order: leaf j <- point bitrev(j)
-            const u64* sdev = static_cast<const u64*>(salts);
+            const T* sdev = static_cast<const T*>(salts);
             if (!dev_in) {
-                if ((s = ensure(ctx, ctx->scratch, nsalt * N * sizeof(u64)))) return cleanup(s);
-                if (hipMemcpyAsync(ctx->scratch.p, salts, nsalt * N * sizeof(u64), hipMemcpyHostToDevice, st) != hipSuccess)
+                T* sh;
+                if ((s = scratch(0, salt_bytes, &sh))) return cleanup(s);
+                if (hipMemcpyAsync(sh, salts, salt_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
                     return cleanup(fail(ctx, GB_ERR_HIP, "copy of salts failed"));
                 mark_upload(ctx);
-                if (p3) gbk::gl_canonicalize((u64*)ctx->scratch.p, (size_t)nsalt * N, st);
-                sdev = (const u64*)ctx->scratch.p;
+                if (p3) HF::p3_to_canonical_dev(sh, (size_t)nsalt * N, st);   // the salt columns are F::rand_vec words too
+                sdev = sh;
             }
-            gbk::u64_bitrev_copy(sdev, b->lde + ncols * N, log_N, nsalt, st);
+            HF::bitrev_copy_to_device_form(sdev, lde + ncols * N, log_N, nsalt, st);
         }
     }
     {
@@ -1119,14 +1025,14 @@ gb_status commit(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t ncols, uint32_
             Scope sl(ctx, "hash leaves");
             if (!seg_done && keep_split) {   // device input whose last column segment may have to be redone: hash in two segments
                 if (pool_alloc(ctx, seg_state_bytes, &seg_state) != hipSuccess) { seg_state = nullptr; return cleanup(fail(ctx, GB_ERR_OOM, "sponge state")); }
-                gbk::gl_merkle_leaves_segment(b->lde, N, 0, last_seg_start, N, (u64*)seg_state, false, (u32)(width - last_seg_start), b->levels, st);
+                HF::merkle_leaves_segment(lde, N, 0, last_seg_start, (T*)seg_state, false, (u32)(width - last_seg_start), lv, st);
                 seg_done = last_seg_start;
             }
-            if (seg_done) gbk::gl_merkle_leaves_segment(b->lde, N, seg_done, (u32)width, N, (u64*)seg_state, true, 0, b->levels, st);
-            else gbk::gl_merkle_leaves(b->lde, N, (u32)width, N, b->levels, st);
+            if (seg_done) HF::merkle_leaves_segment(lde, N, seg_done, (u32)width, (T*)seg_state, true, 0, lv, st);
+            else HF::merkle_leaves(lde, N, (u32)width, lv, st);
         }
         for (u32 k = 0; k < log_N - cap_height; k++)
-            gbk::gl_merkle_level(b->levels + 4 * level_offset(N, k), b->levels + 4 * level_offset(N, k + 1), N >> (k + 1), st);
+            HF::merkle_level(lv + F::H * level_offset(N, k), lv + F::H * level_offset(N, k + 1), N >> (k + 1), st);
     }
     if (hipGetLastError() != hipSuccess) return cleanup(fail(ctx, GB_ERR_HIP, "kernel launch failed"));
     if (keep && seg_done && seg_state) { *keep = SegKeep{seg_state, seg_state_bytes, seg_done}; seg_state = nullptr; }
@@ -1162,16 +1068,8 @@ gb_status gb_ctx_destroy(gb_ctx* ctx) try {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     gb_ctx_scope_reset(ctx);
-    for (auto& kv : ctx->gl_tables) for (void* p : kv.second.owned) hipFree(p);
-    for (auto& kv : ctx->gl_cosets) for (void* p : kv.second.owned) hipFree(p);
-    for (auto& kv : ctx->bb_tables) for (void* p : kv.second.owned) hipFree(p);
-    for (auto& kv : ctx->bb_cosets) for (void* p : kv.second.owned) hipFree(p);
-    if (ctx->bb_tw4096_fwd) hipFree(ctx->bb_tw4096_fwd);
-    if (ctx->bb_tw4096_inv) hipFree(ctx->bb_tw4096_inv);
-    if (ctx->tw4096_fwd) hipFree(ctx->tw4096_fwd);
-    if (ctx->tw4096_inv) hipFree(ctx->tw4096_inv);
-    if (ctx->tw4096_fwd_m) hipFree(ctx->tw4096_fwd_m);
-    if (ctx->tw4096_inv_m) hipFree(ctx->tw4096_inv_m);
+    cache<GlF>(ctx).release();
+    cache<BbF>(ctx).release();
     if (ctx->scratch.p) hipFree(ctx->scratch.p);
     if (ctx->small.p) hipFree(ctx->small.p);
     for (DeviceBuf& wb : ctx->big_work) if (wb.p) hipFree(wb.p);
@@ -1267,7 +1165,11 @@ static gb_status commit_entry(gb_ctx* ctx, uint32_t field, ColSrc cols, size_t n
         if (out) *out = nullptr;
         return fail(ctx, GB_ERR_INVALID, "unknown bits in flags");
     }
-    gb_status s = commit(ctx, field, cols, ncols, log_n, rate_bits, cap_height, salts, flags, is_coeffs, out);
+    gb_status s;
+    if (field == GB_GOLDILOCKS) s = commit<GlF>(ctx, cols, ncols, log_n, rate_bits, cap_height, salts, flags, is_coeffs, out);
+    else if (field == GB_BABYBEAR) s = commit<BbF>(ctx, cols, ncols, log_n, rate_bits, cap_height, salts, flags, is_coeffs, out);
+    else if (!ctx || !out) s = fail(ctx, GB_ERR_INVALID, ctx ? "null out" : "null ctx");
+    else { *out = nullptr; s = fail(ctx, GB_ERR_INVALID, "unknown field tag"); }
     if (!(flags & GB_INPUT_DEVICE)) s = finish_host_commit(ctx, s, out);   // `cols` / `salts` are the caller's again on return
     return s;
 }

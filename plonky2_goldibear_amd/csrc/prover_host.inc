@@ -7,8 +7,6 @@
 // of the same width.
 
 #include "gates.hpp"
-#include "poseidon2_bb_host.hpp"
-#include "poseidon_gl_host.hpp"
 
 struct gb_circuit {
     uint32_t field = 0;
@@ -69,72 +67,6 @@ static gb_status unwound_circuit(gb_circuit* c, const char* fn) noexcept {
 #define GB_CATCH_CIRCUIT(C) catch (...) { return unwound_circuit((C), __func__); }
 
 namespace {
-
-using gbk::BbF;
-using gbk::GlF;
-
-// per-field host glue: transcript hash, NTT / Merkle launchers, tables
-template <class F>
-struct Host;
-template <>
-struct Host<GlF> {
-    typedef poseidon_gl_host::Challenger Challenger;
-    typedef gbk::GlNttTables Tables;
-    typedef gbk::GlCosetTables Cosets;
-    static void hash_no_pad(const u64* in, size_t n, u64* out) { poseidon_gl_host::hash_no_pad(in, n, out); }
-    static gb_status tables_for(gb_ctx* ctx, u32 lg, const Tables** out) { return gl_tables_for(ctx, lg, out); }
-    static gb_status cosets_for(gb_ctx* ctx, u32 lg, u32 r, u64 shift, bool inverse, const Cosets** out) {
-        return gl_cosets_for(ctx, lg, r, shift, inverse, out);
-    }
-    static void intt(const u64* src, u64* dst, u64* scratch, size_t ncols, const Tables& t, hipStream_t st) {
-        gbk::gl_intt_columns(src, dst, scratch, ncols, t, st);
-    }
-    static void lde(const u64* coeffs, u64* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
-        gbk::gl_lde_columns(coeffs, out, ncols, t, c, st);
-    }
-    static void merkle_level(const u64* in, u64* out, u64 num_out, hipStream_t st) { gbk::gl_merkle_level(in, out, num_out, st); }
-    static void merkle_last_segment(const u64* lde, u64 N, u32 c_begin, u32 width, void* state, u64* levels, hipStream_t st) {
-        gbk::gl_merkle_leaves_segment(lde, N, c_begin, width, N, (u64*)state, true, 0, levels, st);
-    }
-    static void to_device_form(u64*, size_t, hipStream_t) {}
-    static void p3_to_device_form(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }   // GB_INPUT_P3_REPR words
-    static u64 p3_to_canonical(u64 x) { return x >= gl::P ? x - gl::P : x; }
-    static void p3_to_canonical_dev(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }
-    static bool intt_canonical(u64*, u64*, u64*, size_t, const Tables&, hipStream_t) { return false; }   // device form IS canonical
-    static void from_device_form(u64*, size_t, hipStream_t) {}
-    static constexpr bool device_form_is_canonical = true;
-};
-template <>
-struct Host<BbF> {
-    typedef poseidon2_bb_host::Challenger Challenger;
-    typedef gbk::BbNttTables Tables;
-    typedef gbk::BbCosetTables Cosets;
-    static void hash_no_pad(const u32* in, size_t n, u32* out) { poseidon2_bb_host::hash_no_pad(in, n, out); }
-    static gb_status tables_for(gb_ctx* ctx, u32 lg, const Tables** out) { return bb_tables_for(ctx, lg, out); }
-    static gb_status cosets_for(gb_ctx* ctx, u32 lg, u32 r, u32 shift, bool inverse, const Cosets** out) {
-        return bb_cosets_for(ctx, lg, r, shift, inverse, out);
-    }
-    static void intt(const u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st) {
-        gbk::bb_intt_columns(src, dst, scratch, ncols, t, st);
-    }
-    static void lde(const u32* coeffs, u32* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
-        gbk::bb_lde_columns(coeffs, out, ncols, t, c, st);
-    }
-    static void merkle_level(const u32* in, u32* out, u64 num_out, hipStream_t st) { gbk::bb_merkle_level(in, out, num_out, st); }
-    static void merkle_last_segment(const u32* lde, u64 N, u32 c_begin, u32 width, void* state, u32* levels, hipStream_t st) {
-        gbk::bb_merkle_leaves_segment(lde, N, c_begin, width, N, (u32*)state, true, 0, levels, st);
-    }
-    static void to_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_to_mont(p, p, count, st); }
-    static void p3_to_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); }   // p3's MontyField31 words ARE the device form (reduced below p: they are a caller's memory)
-    static u32 p3_to_canonical(u32 x) { return bb::from_mont(x); }
-    static void p3_to_canonical_dev(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); gbk::bb_from_mont(p, p, count, st); }
-    // values -> coefficients of columns held in CANONICAL form (what commit() leaves of a host witness beyond the routed wires)
-    static bool intt_canonical(u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st) {
-        return gbk::bb_intt_columns_canonical(src, dst, scratch, ncols, 0, t, st);
-    }
-    static void from_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_from_mont(p, p, count, st); }
-    static constexpr bool device_form_is_canonical = false;
-};
 
 // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (fri/reduction_strategies.rs:39-50).  false = the
 // configuration on which the reference panics there: `assert!(degree_bits >= arity_bits)` inside the loop (an arity that does not
@@ -322,7 +254,7 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
     const size_t ncs = cfg->num_selectors + cfg->num_constants + cfg->num_routed_wires;
     gb_status s;
     // constants_sigmas_commitment (circuit_builder.rs:1230-1239), blinding = false
-    if ((s = commit(ctx, F::TAG, constants_sigmas, ncs, lg, r, cfg->cap_height, nullptr, flags, false, &c->cs)))
+    if ((s = commit<F>(ctx, constants_sigmas, ncs, lg, r, cfg->cap_height, nullptr, flags, false, &c->cs)))
         return cleanup((flags & GB_INPUT_DEVICE) ? s : finish_host_commit(ctx, s, nullptr));   // no copy from the caller's buffer left in flight
     // sigma values stay resident for the Z computation (ProverOnlyCircuitData.sigmas)
     void* p = nullptr;
@@ -336,7 +268,7 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
                       (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream))
         return cleanup(fail(ctx, GB_ERR_HIP, "copy of sigma values failed"));
     if (flags & GB_INPUT_P3_REPR) HF::p3_to_device_form(c->sigma_vals, sig_count, ctx->stream);   // the field types' in-memory words
-    else HF::to_device_form(c->sigma_vals, sig_count, ctx->stream);
+    else HF::to_device_form(c->sigma_vals, c->sigma_vals, sig_count, ctx->stream);
     std::vector<T> k_canon(cfg->num_routed_wires);
     if (flags & GB_INPUT_DEVICE) {
         if (hipMemcpy(k_canon.data(), k_is, k_canon.size() * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
@@ -535,8 +467,8 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     // coset_ifft of size n 2^qb (prover.rs:921-925) = per-coset size-n inverse NTTs + radix-2^qb combine
     const typename HF::Tables* tabs;
     const typename HF::Cosets* inv_cos;
-    if ((s = HF::tables_for(ctx, lg, &tabs))) return s;
-    if ((s = HF::cosets_for(ctx, lg, qb, F::generator(), true, &inv_cos))) return s;
+    if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
+    if ((s = cosets_for<F>(ctx, lg, qb, F::generator(), true, &inv_cos))) return s;
     if ((s = ensure(ctx, ctx->scratch, nq * n * sizeof(T)))) return s;
     { Scope sq(ctx, "quotient IFFT"); HF::intt(qv, qc, (T*)ctx->scratch.p, nq, *tabs, st); }   // (a scope of its own: not a commitment's transform)
     gbk::CosetPow<F> ip{inv_cos->pow_lo, inv_cos->pow_hi, (u32)(n < 4096 ? n : 4096), (u32)(n > 4096 ? n / 4096 : 1)};
@@ -614,8 +546,8 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
         T* cur_coeffs = fcols;
         for (u32 li = 0; li < nlayers; li++) {
             const size_t cur_n = (size_t)1 << cur_lg, cur_N = cur_n << r;
-            if ((s = HF::tables_for(ctx, cur_lg, &tabs))) return s;
-            if ((s = HF::cosets_for(ctx, cur_lg, r, shift, false, &cos))) return s;
+            if ((s = tables_for<F>(ctx, cur_lg, &tabs))) return s;
+            if ((s = cosets_for<F>(ctx, cur_lg, r, shift, false, &cos))) return s;
             T* vals = tmp.get<T>(D * cur_N);
             if (!vals) return fail(ctx, GB_ERR_OOM, "FRI values");
             { Scope sl(ctx, "FRI LDE"); HF::lde(cur_coeffs, vals, D, *tabs, *cos, st); }
@@ -830,7 +762,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             T* colbuf = tmp.get<T>(n);
             if (!colbuf) return fail(ctx, GB_ERR_OOM, "witness column");
             HIP_TRY(ctx, hipMemcpyAsync(colbuf, witness.col(hint->wire, col_bytes), col_bytes, hipMemcpyDeviceToDevice, st));
-            HF::to_device_form(colbuf, n, st);
+            HF::to_device_form(colbuf, colbuf, n, st);
             col_src = colbuf;
         } else {                                                  // host matrix: the kept device copy, one element re-written
             if (ctx->retry_verify) {   // option "retry_verify": is the caller's matrix the kept one but for that element?  (a debugging
@@ -865,8 +797,8 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         }
         const typename HF::Tables* tabs;
         const typename HF::Cosets* cos;
-        if ((s = HF::tables_for(ctx, lg, &tabs))) return s;
-        if ((s = HF::cosets_for(ctx, lg, r, F::generator(), false, &cos))) return s;
+        if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
+        if ((s = cosets_for<F>(ctx, lg, r, F::generator(), false, &cos))) return s;
         if ((s = ensure(ctx, ctx->scratch, 2 * n * sizeof(T)))) return s;
         T* coeffs_col = (T*)wires->coeffs + (size_t)hint->wire * n;
         T* lde_col = (T*)wires->lde + (size_t)hint->wire * N;
@@ -883,7 +815,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         {
             Scope sm(ctx, "build Merkle tree");
             T* lv = (T*)wires->levels;
-            { Scope sl(ctx, "hash leaves"); HF::merkle_last_segment((const T*)wires->lde, N, seg.start, nw, seg.state, lv, st); }
+            { Scope sl(ctx, "hash leaves"); HF::merkle_leaves_segment((const T*)wires->lde, N, seg.start, nw, (T*)seg.state, true, 0, lv, st); }
             for (u32 k = 0; k < lg + r - capH; k++)
                 HF::merkle_level(lv + H * level_offset(N, k), lv + H * level_offset(N, k + 1), N >> (k + 1), st);
         }
@@ -895,7 +827,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             wit_vals = (T*)p;
         }
         Scope sc(ctx, "compute wires commitment");
-        if ((s = commit(ctx, F::TAG, witness, nw, lg, r, capH, salt_w, flags, false, &wires, wit_vals, salts ? nullptr : &seg, &wit_mont_cols)))
+        if ((s = commit<F>(ctx, witness, nw, lg, r, capH, salt_w, flags, false, &wires, wit_vals, salts ? nullptr : &seg, &wit_mont_cols)))
             return (flags & GB_INPUT_DEVICE) ? s : finish_host_commit(ctx, s, nullptr);   // the witness is the caller's again
     }
     // the Z computation needs the routed wire VALUES on the device (device form) as well
@@ -910,7 +842,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         if (!copy_columns(witness, nr, col_bytes, wit_copy, (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
             return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
         if (p3) HF::p3_to_device_form(wit_copy, (size_t)nr * n, st);
-        else HF::to_device_form(wit_copy, (size_t)nr * n, st);
+        else HF::to_device_form(wit_copy, wit_copy, (size_t)nr * n, st);
         wit_dev = wit_copy;
     }
     std::vector<T> cap;
@@ -948,7 +880,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             s = fail(ctx, GB_ERR_PERM_ARG_ZERO, "InvZeroPermArg (armed by gb_test_arm_perm_arg_failure)");
         }
         if (s) return failed(s);
-        if ((s = commit(ctx, F::TAG, zs_vals, nzs, lg, r, capH, salt_z, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, false, &zs))) {
+        if ((s = commit<F>(ctx, zs_vals, nzs, lg, r, capH, salt_z, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, false, &zs))) {
             if (defer) (void)hipMemsetAsync(c->perm_err, 0, 4, st);   // nobody will ask the deferred question: leave the word zero
             return s;
         }
@@ -968,7 +900,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         Scope sc(ctx, "compute quotient polys");
         T* chunks = nullptr;
         if ((s = stage_quotient_polys<F>(c, tmp, wires, zs, pi_hash, betas_d, gammas_d, alphas, &chunks))) return s;
-        if ((s = commit(ctx, F::TAG, chunks, nq, lg, r, capH, salt_q, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, true, &quot))) return s;
+        if ((s = commit<F>(ctx, chunks, nq, lg, r, capH, salt_q, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, true, &quot))) return s;
     }
     if ((s = read_cap<F>(quot, cap))) return s;
     ch.observe(cap.data(), cap.size());
@@ -1101,7 +1033,7 @@ static gb_status abi_zs_partial_products(Circuit<F>* c, ColSrc witness, uint32_t
         if (!copy_columns(witness, nr, n * sizeof(T), copy, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
             return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
         if (p3) HF::p3_to_device_form(copy, (size_t)nr * n, st);
-        else HF::to_device_form(copy, (size_t)nr * n, st);
+        else HF::to_device_form(copy, copy, (size_t)nr * n, st);
         wit_dev = copy;
     }
     std::vector<T> bd(nch), gd(nch);
