@@ -51,8 +51,8 @@ struct ScopeAcc {
 template <class F>
 struct TableCache {
     typedef typename F::T T;
-    typedef std::conditional_t<std::is_same<F, GlF>::value, gbk::GlNttTables, gbk::BbNttTables> Tables;
-    typedef std::conditional_t<std::is_same<F, GlF>::value, gbk::GlCosetTables, gbk::BbCosetTables> Cosets;
+    typedef gbk::NttTables<F> Tables;
+    typedef gbk::CosetTables<F> Cosets;
     template <class X>
     struct Owner {   // a table set and the device blocks it owns
         X t{};
@@ -692,7 +692,6 @@ bool copy_columns(const ColSrc& src, size_t ncols, size_t col_bytes, void* dst, 
 }
 
 inline size_t hout(u32 field) { return field == GB_GOLDILOCKS ? 4 : 8; }
-inline size_t esize(u32 field) { return field == GB_GOLDILOCKS ? 8 : 4; }
 inline size_t level_offset(u64 N, u32 k) { return (size_t)(2 * N - ((2 * N) >> k)); }
 
 struct EventList {  // events of one enqueue sequence, destroyed together (destruction is deferred until they have completed)
@@ -717,7 +716,8 @@ struct SegKeep {
     size_t bytes = 0;
     u32 start = 0;           // first column of the last segment
 };
-// per-field host glue: transcript hash, NTT / Merkle launchers, and what commit() does differently per field
+// per-field host glue: transcript hash, Merkle launchers, and what commit() does differently per field (the transforms and the
+// element-wise kernels are field-generic: kernels.hpp)
 template <class F>
 struct Host;
 template <>
@@ -726,12 +726,6 @@ struct Host<GlF> {
     typedef gbk::GlNttTables Tables;
     typedef gbk::GlCosetTables Cosets;
     static void hash_no_pad(const u64* in, size_t n, u64* out) { poseidon_gl_host::hash_no_pad(in, n, out); }
-    static void intt(const u64* src, u64* dst, u64* scratch, size_t ncols, const Tables& t, hipStream_t st) {
-        gbk::gl_intt_columns(src, dst, scratch, ncols, t, st);
-    }
-    static void lde(const u64* coeffs, u64* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
-        gbk::gl_lde_columns(coeffs, out, ncols, t, c, st);
-    }
     static void merkle_leaves(const u64* lde, u64 N, u32 width, u64* levels, hipStream_t st) {
         gbk::gl_merkle_leaves(lde, N, width, N, levels, st);
     }
@@ -743,15 +737,9 @@ struct Host<GlF> {
     static void to_device_form(const u64* src, u64* dst, size_t count, hipStream_t st) {   // canonical words ARE the device form
         if (src != dst) (void)hipMemcpyAsync(dst, src, count * sizeof(u64), hipMemcpyDeviceToDevice, st);
     }
-    static void p3_to_device_form(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }   // GB_INPUT_P3_REPR words
     static u64 p3_to_canonical(u64 x) { return x >= gl::P ? x - gl::P : x; }
-    static void p3_to_canonical_dev(u64* p, size_t count, hipStream_t st) { gbk::gl_canonicalize(p, count, st); }
     static bool intt_canonical(u64*, u64*, u64*, size_t, const Tables&, hipStream_t, size_t = 0) { return false; }   // device form IS canonical
-    static void from_device_form(u64*, size_t, hipStream_t) {}
-    // canonical columns of 2^bits points -> dst in device form, dst[j] = src[bitrev_bits(j)] (salt columns -> leaf order)
-    static void bitrev_copy_to_device_form(const u64* src, u64* dst, u32 bits, size_t ncols, hipStream_t st) {
-        gbk::u64_bitrev_copy(src, dst, bits, ncols, st);
-    }
+    static void from_device_form(const u64* src, u64* dst, size_t count, hipStream_t st) { to_device_form(src, dst, count, st); }
     static constexpr bool device_form_is_canonical = true;
     // commit(): columns of the first upload chunk of a host batch (4, 4, 8, then 16 columns), fewest columns staged at all, and
     // whether its scratch is reserved up front ([host input or salts | transform scratch]) or grown to what each step needs
@@ -764,12 +752,6 @@ struct Host<BbF> {
     typedef gbk::BbNttTables Tables;
     typedef gbk::BbCosetTables Cosets;
     static void hash_no_pad(const u32* in, size_t n, u32* out) { poseidon2_bb_host::hash_no_pad(in, n, out); }
-    static void intt(const u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st) {
-        gbk::bb_intt_columns(src, dst, scratch, ncols, t, st);
-    }
-    static void lde(const u32* coeffs, u32* out, size_t ncols, const Tables& t, const Cosets& c, hipStream_t st) {
-        gbk::bb_lde_columns(coeffs, out, ncols, t, c, st);
-    }
     static void merkle_leaves(const u32* lde, u64 N, u32 width, u32* levels, hipStream_t st) {
         gbk::bb_merkle_leaves(lde, N, width, N, levels, st);
     }
@@ -779,23 +761,26 @@ struct Host<BbF> {
     }
     static void merkle_level(const u32* in, u32* out, u64 num_out, hipStream_t st) { gbk::bb_merkle_level(in, out, num_out, st); }
     static void to_device_form(const u32* src, u32* dst, size_t count, hipStream_t st) { gbk::bb_to_mont(src, dst, count, st); }
-    static void p3_to_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); }   // p3's MontyField31 words ARE the device form (reduced below p: they are a caller's memory)
     static u32 p3_to_canonical(u32 x) { return bb::from_mont(x); }
-    static void p3_to_canonical_dev(u32* p, size_t count, hipStream_t st) { gbk::bb_reduce_words(p, count, st); gbk::bb_from_mont(p, p, count, st); }
     // values -> coefficients of columns held in CANONICAL form (what commit() leaves of a host witness beyond the routed wires);
     // the first mont_cols of them are left in device form in `src`.  false: the shape is not covered, nothing was launched
     static bool intt_canonical(u32* src, u32* dst, u32* scratch, size_t ncols, const Tables& t, hipStream_t st, size_t mont_cols = 0) {
         return gbk::bb_intt_columns_canonical(src, dst, scratch, ncols, mont_cols, t, st);
     }
-    static void from_device_form(u32* p, size_t count, hipStream_t st) { gbk::bb_from_mont(p, p, count, st); }
-    static void bitrev_copy_to_device_form(const u32* src, u32* dst, u32 bits, size_t ncols, hipStream_t st) {
-        gbk::bb_bitrev_copy_to_mont(src, dst, bits, ncols, st);
-    }
+    static void from_device_form(const u32* src, u32* dst, size_t count, hipStream_t st) { gbk::bb_from_mont(src, dst, count, st); }
     static constexpr bool device_form_is_canonical = false;
     // 4-byte words: the same bytes per upload chunk as Goldilocks' 4, 4, 8 (8, 8, 16, then 16 columns)
     static constexpr size_t first_chunk = 8, min_staged_cols = 4;
     static constexpr bool scratch_up_front = true;
 };
+
+// GB_INPUT_P3_REPR words (the field types' in-memory words: p3-goldilocks any u64 representative, p3-monty-31 Montgomery words; the
+// reduction below p is the device form) -> canonical values, in place
+template <class F>
+void p3_to_canonical_dev(typename F::T* p, size_t count, hipStream_t st) {
+    gbk::reduce_words<F>(p, count, st);
+    Host<F>::from_device_form(p, p, count, st);
+}
 
 // Upload chunks of a host batch, in columns: c, c, 2c, then 16 (c = Host<F>::first_chunk).  The GPU's per-column work (transform +
 // leaf hashing) is slower than PCIe delivers columns, so after a short ramp the upload is hidden - what is not hidden is the wait for
@@ -950,17 +935,17 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
             T* const v = vals + c0 * n;
             bool direct = false;   // coefficients already: the inverse transform took the canonical values as they are
             if (p3) {   // the host's words of the field types: nothing to convert, but nothing to trust either
-                HF::p3_to_device_form(v, cc * n, st);
+                gbk::reduce_words<F>(v, cc * n, st);
             } else if (!HF::device_form_is_canonical) {
                 const size_t want_mont = !values_dev ? 0 : values_mont_cols ? *values_mont_cols : ncols;
                 { Scope sc(ctx, "IFFT"); direct = HF::intt_canonical(v, coeffs + c0 * n, ntt_scr, cc, *tabs, st, want_mont > c0 ? want_mont - c0 : 0); }
                 if (!direct) HF::to_device_form(v, v, cc * n, st);
             }
             if (!direct) {
-                { Scope sc(ctx, "IFFT"); HF::intt(v, coeffs + c0 * n, ntt_scr, cc, *tabs, st); }
+                { Scope sc(ctx, "IFFT"); gbk::intt_columns<F>(v, coeffs + c0 * n, ntt_scr, cc, *tabs, st); }
                 if (values_mont_cols) *values_mont_cols = ncols;
             }
-            { Scope sc(ctx, "FFT + blinding"); HF::lde(coeffs + c0 * n, lde + c0 * N, cc, *tabs, *cos, st); }
+            { Scope sc(ctx, "FFT + blinding"); gbk::lde_columns<F>(coeffs + c0 * n, lde + c0 * N, cc, *tabs, *cos, st); }
             if (!hash_ready_segments(c0 + cc)) return cleanup(fail(ctx, GB_ERR_OOM, "sponge state"));
         }
         if (!ok) return cleanup(fail(ctx, GB_ERR_HIP, "chunked upload of the input columns failed"));
@@ -983,7 +968,7 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
                     return cleanup(fail(ctx, GB_ERR_HIP, "copy of input columns failed"));
                 src = coeffs;
             }
-            if (p3) HF::p3_to_device_form(coeffs, ncols * n, st);   // a host's words (the library's own device form is in range)
+            if (p3) gbk::reduce_words<F>(coeffs, ncols * n, st);   // a host's words (the library's own device form is in range)
         } else if (!is_coeffs && log_n >= 16 && log_n <= gbk::NTT_NATIVE_LOG) {
             // canonical values on the device (a resident witness, a small host batch): the inverse transform takes them as they are
             if ((s = scratch(scr_bytes, in_bytes, &ntt_scr))) return cleanup(s);
@@ -997,12 +982,12 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
         if (!is_coeffs && !direct) {
             if ((s = scratch(scr_bytes, in_bytes, &ntt_scr))) return cleanup(s);
             Scope sc(ctx, "IFFT");
-            HF::intt(src, coeffs, ntt_scr, ncols, *tabs, st);
+            gbk::intt_columns<F>(src, coeffs, ntt_scr, ncols, *tabs, st);
         }
     }
     {
         Scope sc(ctx, "FFT + blinding");
-        if (!staged) HF::lde(coeffs, lde, ncols, *tabs, *cos, st);
+        if (!staged) gbk::lde_columns<F>(coeffs, lde, ncols, *tabs, *cos, st);
         if (nsalt) {
             // salt columns arrive in LDE-point order (like lde_values' extra columns, oracle.rs:144-148)
             // and are stored, like everything else, in leaf order: leaf j <- point bitrev(j)
@@ -1013,10 +998,10 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
                 if (hipMemcpyAsync(sh, salts, salt_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
                     return cleanup(fail(ctx, GB_ERR_HIP, "copy of salts failed"));
                 mark_upload(ctx);
-                if (p3) HF::p3_to_canonical_dev(sh, (size_t)nsalt * N, st);   // the salt columns are F::rand_vec words too
+                if (p3) p3_to_canonical_dev<F>(sh, (size_t)nsalt * N, st);   // the salt columns are F::rand_vec words too
                 sdev = sh;
             }
-            HF::bitrev_copy_to_device_form(sdev, lde + ncols * N, log_N, nsalt, st);
+            gbk::bitrev_copy<F>(sdev, lde + ncols * N, log_N, nsalt, st);
         }
     }
     {
@@ -1037,6 +1022,56 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
     if (hipGetLastError() != hipSuccess) return cleanup(fail(ctx, GB_ERR_HIP, "kernel launch failed"));
     if (keep && seg_done && seg_state) { *keep = SegKeep{seg_state, seg_state_bytes, seg_done}; seg_state = nullptr; }
     *out = b;
+    return GB_OK;
+}
+
+// ---- read-backs of a batch, canonical values; each one field-generic body behind the batch's field tag
+template <class F>
+gb_status read_coeffs(gb_batch* b, size_t col, void* out) {
+    typedef typename F::T T;
+    gb_ctx* ctx = b->ctx;
+    const size_t n = (size_t)1 << b->log_n;
+    const T* src = (const T*)b->coeffs + col * n;
+    if (!Host<F>::device_form_is_canonical) {
+        gb_status s = ensure(ctx, ctx->scratch, n * sizeof(T));
+        if (s) return s;
+        Host<F>::from_device_form(src, (T*)ctx->scratch.p, n, ctx->stream);
+        src = (const T*)ctx->scratch.p;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(out, src, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GB_OK;
+}
+
+template <class F>
+gb_status read_row(gb_batch* b, u64 leaf, u32 width, void* out) {
+    typedef typename F::T T;
+    gb_ctx* ctx = b->ctx;
+    const u64 N = (u64)1 << (b->log_n + b->rate_bits);
+    gb_status s = ensure(ctx, ctx->small, 64 * 1024);
+    if (s) return s;
+    if (width * sizeof(u64) > ctx->small.bytes) return fail(ctx, GB_ERR_UNSUPPORTED, "row too wide");
+    gbk::gather_row<F>((const T*)b->lde, N, width, leaf, (T*)ctx->small.p, ctx->stream);
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->small.p, width * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return GB_OK;
+}
+gb_status read_row(gb_batch* b, u64 leaf, u32 width, void* out) {
+    return b->field == GB_BABYBEAR ? read_row<BbF>(b, leaf, width, out) : read_row<GlF>(b, leaf, width, out);
+}
+
+template <class F>
+gb_status read_leaves(gb_batch* b, void* out) {
+    typedef typename F::T T;
+    gb_ctx* ctx = b->ctx;
+    const u64 N = (u64)1 << (b->log_n + b->rate_bits);
+    const u32 width = (u32)(b->ncols + b->nsalt);
+    const size_t bytes = (size_t)N * width * sizeof(T);
+    gb_status s = ensure(ctx, ctx->scratch, bytes);
+    if (s) return s;
+    gbk::transpose_to_rows<F>((const T*)b->lde, N, width, N, (T*)ctx->scratch.p, ctx->stream);
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GB_OK;
 }
 
@@ -1292,36 +1327,9 @@ gb_status gb_batch_cap(gb_batch* b, void* out) try {
 
 gb_status gb_batch_coeffs(gb_batch* b, size_t col, void* out) try {
     if (!b || !out) return fail(b ? b->ctx : nullptr, GB_ERR_INVALID, "null argument");
-    gb_ctx* ctx = b->ctx;
-    if (col >= b->ncols) return fail(ctx, GB_ERR_INVALID, "polynomial index out of range");
-    const size_t n = (size_t)1 << b->log_n;
-    if (b->field == GB_BABYBEAR) {
-        gb_status s = ensure(ctx, ctx->scratch, n * 4);
-        if (s) return s;
-        gbk::bb_from_mont((const u32*)b->coeffs + col * n, (u32*)ctx->scratch.p, n, ctx->stream);
-        HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return GB_OK;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(out, b->coeffs + col * n, n * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GB_OK;
+    if (col >= b->ncols) return fail(b->ctx, GB_ERR_INVALID, "polynomial index out of range");
+    return b->field == GB_BABYBEAR ? read_coeffs<BbF>(b, col, out) : read_coeffs<GlF>(b, col, out);
 } GB_CATCH(b ? b->ctx : nullptr)
-
-static gb_status read_row(gb_batch* b, u64 leaf, u32 width, void* out) {
-    gb_ctx* ctx = b->ctx;
-    const u64 N = (u64)1 << (b->log_n + b->rate_bits);
-    gb_status s = ensure(ctx, ctx->small, 64 * 1024);
-    if (s) return s;
-    if (width * sizeof(u64) > ctx->small.bytes) return fail(ctx, GB_ERR_UNSUPPORTED, "row too wide");
-    if (b->field == GB_BABYBEAR)
-        gbk::bb_gather_row((const u32*)b->lde, N, width, leaf, (u32*)ctx->small.p, ctx->stream);
-    else
-        gbk::gl_gather_row(b->lde, N, width, leaf, (u64*)ctx->small.p, ctx->stream);
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->small.p, width * esize(b->field), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GB_OK;
-}
 
 gb_status gb_batch_lde_values(gb_batch* b, uint64_t index, uint64_t step, void* out) try {
     if (!b || !out) return fail(b ? b->ctx : nullptr, GB_ERR_INVALID, "null argument");
@@ -1373,19 +1381,7 @@ gb_status gb_batch_digests(gb_batch* b, void* out) try {
 
 gb_status gb_batch_leaves(gb_batch* b, void* out) try {
     if (!b || !out) return fail(b ? b->ctx : nullptr, GB_ERR_INVALID, "null argument");
-    gb_ctx* ctx = b->ctx;
-    const u64 N = (u64)1 << (b->log_n + b->rate_bits);
-    const u32 width = (u32)(b->ncols + b->nsalt);
-    const size_t bytes = (size_t)N * width * esize(b->field);
-    gb_status s = ensure(ctx, ctx->scratch, bytes);
-    if (s) return s;
-    if (b->field == GB_BABYBEAR)
-        gbk::bb_transpose_to_rows((const u32*)b->lde, N, width, N, (u32*)ctx->scratch.p, ctx->stream);
-    else
-        gbk::u64_transpose_to_rows(b->lde, N, width, N, (u64*)ctx->scratch.p, ctx->stream);
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return GB_OK;
+    return b->field == GB_BABYBEAR ? read_leaves<BbF>(b, out) : read_leaves<GlF>(b, out);
 } GB_CATCH(b ? b->ctx : nullptr)
 
 gb_status gb_batch_device_ptrs(gb_batch* b, void** coeffs, void** lde, void** digest_levels) try {

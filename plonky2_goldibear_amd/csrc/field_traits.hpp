@@ -32,6 +32,8 @@ struct GlF {
     static GB_HD T one() { return 1; }
     static GB_HD T enc(u64 canonical) { return canonical; }
     static GB_HD u64 dec(T x) { return x; }
+    // any word -> its residue below p (GB_INPUT_P3_REPR: p3-goldilocks keeps any u64 representative; x < 2^64 < 2p)
+    static GB_HD T reduce_word(T x) { return x >= gl::P ? x - gl::P : x; }
     static GB_HD T add(T a, T b) { return gl::add(a, b); }
     static GB_HD T sub(T a, T b) { return gl::sub(a, b); }
     static GB_HD T mul(T a, T b) { return gl::mul(a, b); }
@@ -103,6 +105,12 @@ struct BbF {
     static GB_HD T one() { return bb::R1; }
     static GB_HD T enc(u64 canonical) { return bb::to_mont((u32)canonical); }
     static GB_HD u64 dec(T x) { return bb::from_mont(x); }
+    // any word -> its residue below p (GB_INPUT_P3_REPR: p3-monty-31 keeps its Montgomery words below p, but the words are the
+    // caller's memory: one out of range would otherwise go into the transforms as it is - ADVICE r5)
+    static GB_HD T reduce_word(T x) {
+        x = x >= 2 * bb::P ? x - 2 * bb::P : x;
+        return x >= bb::P ? x - bb::P : x;
+    }
     static GB_HD T add(T a, T b) { return bb::add(a, b); }
     static GB_HD T sub(T a, T b) { return bb::sub(a, b); }
     static GB_HD T mul(T a, T b) { return bb::mul(a, b); }

@@ -5,13 +5,15 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "field_traits.hpp"
 #include "gate_set.hpp"
 #include "challenge_slices.hpp"
 
 namespace gbk {
 
-// ---------------------------------------------------------------- Goldilocks NTT / LDE (kernels_ntt.hip)
+// ---------------------------------------------------------------- NTT / LDE tables
 
 // Device-resident twiddle tables for one transform size n = 2^log_n (built once per ctx and size).
 struct GlNttTables {
@@ -47,7 +49,7 @@ struct GlCosetTables {
     u32 rate_bits;
     const u64* pow_lo;  // [2^r][min(n,4096)]
     const u64* pow_hi;  // [2^r][max(1, n/4096)]
-    const u64 *pow_lo_m, *pow_hi_m;  // the same times R (Montgomery form), for kernels_ntt16.hip
+    const u64 *pow_lo_m, *pow_hi_m;  // the same times R (Montgomery form), for kernels_ntt16.hip's LDE passes
     // log_n > 22 (ntt_outer.hpp): the coset tables of the sub-transforms (shift^R) and the context's work buffer of this level - the
     // ADDRESS of the context's pointer / size, read at the call: the block moves when it grows
     const GlCosetTables* sub;
@@ -55,49 +57,7 @@ struct GlCosetTables {
     const size_t* work_bytes;
 };
 
-// Columns per group of the inverse transform's passes from 2^18 rows up (BabyBear: twice as many): the scratch block of one group is
-// reused by the next and never leaves the Infinity Cache - measured -8 % on the three memory-bound passes (HISTORY.md, round 3); the
-// LDE passes are bound by VALU issue and run all columns per launch.
-static constexpr size_t INTT_GROUP = 16;
-
-// values on H_n (natural order) -> coefficients (natural order), in `coeffs` [ncols][n].
-// `scratch` must hold ncols*n elements. src may equal coeffs.
-void gl_intt_columns(const u64* src, u64* coeffs, u64* scratch, size_t ncols, const GlNttTables& t, hipStream_t stream);
-
-// any u64 representative -> the canonical one, in place (GB_INPUT_P3_REPR: p3-goldilocks' in-memory words)
-void gl_canonicalize(u64* p, size_t count, hipStream_t stream);
-
-// coefficients [ncols][n] -> LDE [ncols][N] in LEAF order: lde[c][j] = P_c(7 * w_N^bitrev_logN(j))
-// (fri/oracle.rs:108-109 order, no transpose / bit-reverse pass needed afterwards).
-void gl_lde_columns(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables& t, const GlCosetTables& ct,
-                    hipStream_t stream);
-
-// ---------------------------------------------------------------- Poseidon-12 Merkle (kernels_merkle.hip)
-
-// leaf digests: out[j] = hash_or_noop(row j), row j = { cols[c*col_stride + j] : c < width }
-void gl_merkle_leaves(const u64* cols, size_t col_stride, u32 width, u64 num_leaves, u64* out, hipStream_t stream);
-// a column segment [c_begin, c_end) of every leaf's sponge, the state parked in `state` ([4 + 8 - keep_from][num_leaves], rows as used) between segments
-void gl_merkle_leaves_segment(const u64* cols, size_t col_stride, u32 c_begin, u32 c_end, u64 num_leaves, u64* state, bool last,
-                              u32 next_cols, u64* out, hipStream_t stream);
-// one level: out[i] = two_to_one(in[2i], in[2i+1]), i < num_out
-void gl_merkle_level(const u64* in, u64* out, u64 num_out, hipStream_t stream);
-// one state per 16-lane row for small trees; false = not applicable (caller uses the lane-per-leaf kernel)
-bool gl_fri_leaves_coop(const u64* vals, size_t len, u32 arity_bits, u64 num_leaves, u64* out, hipStream_t stream);
-bool bb_fri_leaves_coop(const u32* vals, size_t len, u32 arity_bits, u64 num_leaves, u32* out, hipStream_t stream);
-// level-major digests -> the reference's interleaved layout (hash/merkle_tree.rs:50-58)
-void gl_digests_to_reference_layout(const u64* levels, u64* out, u32 log_leaves, u32 cap_height, hipStream_t stream);
-// gather one row (width elements at stride col_stride) into dst[0..width)
-void gl_gather_row(const u64* cols, size_t col_stride, u32 width, u64 index, u64* dst, hipStream_t stream);
-// siblings of MerkleTree::prove(leaf) from level-major digests: dst[i] = level_i[(leaf >> i) ^ 1], i < layers
-void gl_gather_siblings(const u64* levels, u32 log_leaves, u32 cap_height, u64 leaf, u64* dst, hipStream_t stream);
-// dst[j] = src[bitrev_bits(j)] for `ncols` columns of 2^bits elements (salt columns -> leaf order)
-void u64_bitrev_copy(const u64* src, u64* dst, u32 bits, size_t ncols, hipStream_t stream);
-// leaf-order column-major [width][N] -> row-major leaves [N][width] (debug / parity export)
-void u64_transpose_to_rows(const u64* cols, size_t col_stride, u32 width, u64 rows, u64* dst, hipStream_t stream);
-// raw permutation of `count` states (tests / microbenchmarks)
-void gl_poseidon_permute(const u64* in, u64* out, u64 count, hipStream_t stream);
-
-// ---------------------------------------------------------------- BabyBear (kernels_bb.hip); element data in Montgomery form
+// BabyBear: the same tables over Montgomery words (the plain tables are the kernels' form: no _m twins)
 struct BbNttTables {
     u32 log_n;
     const u32 *tw4096_fwd, *tw4096_inv, *tw_lo_fwd, *tw_hi_fwd, *tw_lo_inv, *tw_hi_inv;
@@ -116,20 +76,73 @@ struct BbCosetTables {
     void* const* work;
     const size_t* work_bytes;
 };
-void bb_intt_columns(const u32* src, u32* coeffs, u32* scratch, size_t ncols, const BbNttTables& t, hipStream_t stream);
+
+template <class F>
+using NttTables = std::conditional_t<std::is_same<F, GlF>::value, GlNttTables, BbNttTables>;
+template <class F>
+using CosetTables = std::conditional_t<std::is_same<F, GlF>::value, GlCosetTables, BbCosetTables>;
+
+// ---------------------------------------------------------------- NTT / LDE (ntt_passes.hpp; instantiated in kernels_ntt16.hip, kernels_bb16.hip)
+// Templated on the field traits; element pointers are in the field's device form.
+
+// Columns per group of the inverse transform's passes from 2^18 rows up, in 8-byte words (BabyBear: twice as many columns): the
+// scratch block of one group is reused by the next and never leaves the Infinity Cache - measured -8 % on the three memory-bound
+// passes (HISTORY.md, round 3); the LDE passes are bound by VALU issue and run all columns per launch.
+static constexpr size_t INTT_GROUP = 16;
+
+// values on H_n (natural order) -> coefficients (natural order), in `coeffs` [ncols][n].
+// `scratch` must hold ncols*n elements. src may equal coeffs.
+template <class F>
+void intt_columns(const typename F::T* src, typename F::T* coeffs, typename F::T* scratch, size_t ncols, const NttTables<F>& t,
+                  hipStream_t stream);
+// BabyBear: values -> coefficients from CANONICAL values (k_intt16_p1<BbF, true>): no conversion pass; the first mont_cols columns
+// of `vals` are left in Montgomery form, the rest canonical.  false: shape not covered (2^16..2^22 rows are), nothing done.
 bool bb_intt_columns_canonical(u32* vals, u32* coeffs, u32* scratch, size_t ncols, size_t mont_cols, const BbNttTables& t, hipStream_t stream);
-void bb_lde_columns(const u32* coeffs, u32* lde, size_t ncols, const BbNttTables& t, const BbCosetTables& ct, hipStream_t stream);
+// coefficients [ncols][n] -> LDE [ncols][N] in LEAF order: lde[c][j] = P_c(7 * w_N^bitrev_logN(j))
+// (fri/oracle.rs:108-109 order, no transpose / bit-reverse pass needed afterwards).
+template <class F>
+void lde_columns(const typename F::T* coeffs, typename F::T* lde, size_t ncols, const NttTables<F>& t, const CosetTables<F>& ct,
+                 hipStream_t stream);
+// gather one row (width elements at stride col_stride) into dst[0..width), canonical
+template <class F>
+void gather_row(const typename F::T* cols, size_t col_stride, u32 width, u64 index, typename F::T* dst, hipStream_t stream);
+// leaf-order column-major [width][N] -> row-major canonical leaves [N][width] (debug / parity export)
+template <class F>
+void transpose_to_rows(const typename F::T* cols, size_t col_stride, u32 width, u64 rows, typename F::T* dst, hipStream_t stream);
+// canonical src -> dst in device form, dst[j] = src[bitrev_bits(j)] for `ncols` columns of 2^bits elements (salt columns -> leaf order)
+template <class F>
+void bitrev_copy(const typename F::T* src, typename F::T* dst, u32 bits, size_t ncols, hipStream_t stream);
+// any word -> the residue below p, in place (GB_INPUT_P3_REPR: the words of the reference's field types from a host)
+template <class F>
+void reduce_words(typename F::T* p, size_t count, hipStream_t stream);
+
+// ---------------------------------------------------------------- Poseidon-12 Merkle (kernels_merkle.hip)
+
+// leaf digests: out[j] = hash_or_noop(row j), row j = { cols[c*col_stride + j] : c < width }
+void gl_merkle_leaves(const u64* cols, size_t col_stride, u32 width, u64 num_leaves, u64* out, hipStream_t stream);
+// a column segment [c_begin, c_end) of every leaf's sponge, the state parked in `state` ([4 + 8 - keep_from][num_leaves], rows as used) between segments
+void gl_merkle_leaves_segment(const u64* cols, size_t col_stride, u32 c_begin, u32 c_end, u64 num_leaves, u64* state, bool last,
+                              u32 next_cols, u64* out, hipStream_t stream);
+// one level: out[i] = two_to_one(in[2i], in[2i+1]), i < num_out
+void gl_merkle_level(const u64* in, u64* out, u64 num_out, hipStream_t stream);
+// one state per 16-lane row for small trees; false = not applicable (caller uses the lane-per-leaf kernel)
+bool gl_fri_leaves_coop(const u64* vals, size_t len, u32 arity_bits, u64 num_leaves, u64* out, hipStream_t stream);
+bool bb_fri_leaves_coop(const u32* vals, size_t len, u32 arity_bits, u64 num_leaves, u32* out, hipStream_t stream);
+// level-major digests -> the reference's interleaved layout (hash/merkle_tree.rs:50-58)
+void gl_digests_to_reference_layout(const u64* levels, u64* out, u32 log_leaves, u32 cap_height, hipStream_t stream);
+// siblings of MerkleTree::prove(leaf) from level-major digests: dst[i] = level_i[(leaf >> i) ^ 1], i < layers
+void gl_gather_siblings(const u64* levels, u32 log_leaves, u32 cap_height, u64 leaf, u64* dst, hipStream_t stream);
+// raw permutation of `count` states (tests / microbenchmarks)
+void gl_poseidon_permute(const u64* in, u64* out, u64 count, hipStream_t stream);
+
+// ---------------------------------------------------------------- BabyBear Poseidon2-16 Merkle (kernels_bb.hip); element data in Montgomery form
 void bb_merkle_leaves(const u32* cols, size_t col_stride, u32 width, u64 num_leaves, u32* out, hipStream_t stream);
 void bb_merkle_leaves_segment(const u32* cols, size_t col_stride, u32 c_begin, u32 c_end, u64 num_leaves, u32* state, bool last,
                               u32 next_cols, u32* out, hipStream_t stream);  // state: [8 + 8 - keep_from][num_leaves]
 void bb_merkle_level(const u32* in, u32* out, u64 num_out, hipStream_t stream);
 void bb_poseidon2_permute(const u32* in, u32* out, u64 count, hipStream_t stream);  // canonical in/out
 void bb_to_mont(const u32* src, u32* dst, size_t n, hipStream_t stream);
-void bb_reduce_words(u32* p, size_t n, hipStream_t stream);   // any u32 -> the residue below p, in place (p3 words from a host)
 void bb_from_mont(const u32* src, u32* dst, size_t n, hipStream_t stream);
-void bb_gather_row(const u32* cols, size_t col_stride, u32 width, u64 index, u32* dst, hipStream_t stream);  // -> canonical
-void bb_bitrev_copy_to_mont(const u32* src, u32* dst, u32 bits, size_t ncols, hipStream_t stream);
-void bb_transpose_to_rows(const u32* cols, size_t col_stride, u32 width, u64 rows, u32* dst, hipStream_t stream);  // -> canonical
 
 // ---------------------------------------------------------------- prover (kernels_prover.hip)
 // Templated on the field traits of field_traits.hpp (GlF / BbF); element pointers are in the field's device form.

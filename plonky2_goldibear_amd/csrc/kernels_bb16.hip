@@ -1,21 +1,18 @@
 // BabyBear NTT passes, v2: radix-16 butterflies held in registers (gfx950).
 //
-// Same passes, tiles, index math and memory layouts as kernels_ntt16.hip (Goldilocks); what differs is the
-// arithmetic: BabyBear has no power-of-two roots of unity, so the 17 non-trivial twiddles inside a 16-point
-// DFT are Montgomery multiplications by compile-time constants w_16^k.  The multiplication count per element
-// and layer is therefore the same as radix-2 (1/2); what the register form buys is one LDS round trip per four
-// layers instead of one per layer (v1, kernels_bb.hip: 34.8 ms of LDE per 2^20 proof, ~5x the VALU bound).
-// kernels_bb.hip's v1 passes remain for the inverse transform of 2^13..2^15 rows and for single-tile sizes.
+// Pass structure and dispatch: ntt_passes.hpp, shared with Goldilocks; the LDE's radix-16 passes follow the same tiles, index math
+// and memory layouts as kernels_ntt16.hip's.  What differs is the arithmetic: BabyBear has no power-of-two roots of unity, so the
+// 17 non-trivial twiddles inside a 16-point DFT are Montgomery multiplications by compile-time constants w_16^k.  The
+// multiplication count per element and layer is therefore the same as radix-2 (1/2); what the register form buys is one LDS round
+// trip per four layers instead of one per layer (v1, LDS radix-2 passes: 34.8 ms of LDE per 2^20 proof, ~5x the VALU bound).
 #include <algorithm>
+#include <cassert>
 
 #include "bb_field.hpp"
 #include "kernels.hpp"
+#include "ntt_passes.hpp"
 
 namespace gbk {
-
-static constexpr int THREADS = 256;
-
-__device__ __forceinline__ constexpr u32 brev4(u32 x) { return ((x & 1) << 3) | ((x & 2) << 1) | ((x & 4) >> 1) | ((x & 8) >> 3); }
 
 namespace bbc {  // compile-time twiddles (canonical arithmetic, stored in Montgomery form)
 constexpr u32 cmul(u32 a, u32 b) { return (u32)((u64)a * b % bb::P); }
@@ -93,11 +90,6 @@ __device__ __forceinline__ void dft_small(u32 (&x)[16]) {
 #pragma unroll
     for (int o = 0; o < (1 << K); o += 2) bfly<INV, 1, 0>(x[o], x[o + 1]);
 }
-__device__ __forceinline__ constexpr u32 brevk(u32 x, int k) {
-    u32 r = 0;
-    for (int i = 0; i < k; i++) r |= ((x >> i) & 1) << (k - 1 - i);
-    return r;
-}
 
 namespace bbc {
 constexpr u32 W64 = cpow(bb::TWO_ADIC_GEN_27, 1u << 21), W64_INV = cpow(W64, 63);
@@ -130,19 +122,15 @@ __device__ __forceinline__ void dft32(u32 (&x)[32]) {
     dft16<INV>(*reinterpret_cast<u32(*)[16]>(&x[16]));
 }
 
-__device__ __forceinline__ u32 bb_tw_split16(const u32* __restrict__ hi, const u32* __restrict__ lo, u32 e) {
-    u32 eh = e >> 10, el = e & 1023;
-    u32 w = lo[el];
-    return eh ? bb::mul(w, hi[eh]) : w;
-}
-
-// The 15 inter-stage twiddles w_4096^(k m), k = brev4(slot), as ONE batch of independent loads issued before the
-// DFT that precedes their use.  (Loaded one by one behind `if (e)` each of them cost a full memory round trip:
-// rocprofv3 showed the waves of these kernels parked in s_waitcnt for 46-66 % of their lifetime.)
-__device__ __forceinline__ void load_tw16(u32 (&tw)[16], const u32* __restrict__ tw4096, u32 m) {
-#pragma unroll
-    for (u32 s = 1; s < 16; s++) tw[s] = tw4096[brev4(s) * m];
-}
+template <>
+struct Dft<BbF> {
+    template <bool INV>
+    static __device__ __forceinline__ void dft16(u32 (&x)[16]) { gbk::dft16<INV>(x); }
+    template <bool INV, int K>
+    static __device__ __forceinline__ void dft_small(u32 (&x)[16]) { gbk::dft_small<INV, K>(x); }
+    template <bool INV, int H, int O>
+    static __device__ __forceinline__ void layer64(u32* x) { gbk::layer64<INV, H, O>(x); }
+};
 
 // ------------------------------------------------------------------ LDE pass B: 4096 contiguous points, 3 radix-16 stages
 // grid = number of 4096-tiles of `lde` (in place).  natural -> bit-reversed.
@@ -151,8 +139,8 @@ __global__ __launch_bounds__(THREADS) void k_bb_lde_pb16(u32* __restrict__ lde, 
     const u32 tid = threadIdx.x;
     const u32 hi4 = tid >> 4, lo4 = tid & 15;
     u32 tw1[16], tw2[16];
-    load_tw16(tw1, tw4096, tid);       // w_4096^(k2 (16 d1 + d0))
-    load_tw16(tw2, tw4096, lo4 * 16);  // w_256^(k1 d0)
+    load_tw16<BbF>(tw1, tw4096, tid);       // w_4096^(k2 (16 d1 + d0))
+    load_tw16<BbF>(tw2, tw4096, lo4 * 16);  // w_256^(k1 d0)
     u32 x[16], nx[16];
     u32 tile = blockIdx.x;
     if (tile < ntiles) {
@@ -223,10 +211,10 @@ __global__ __launch_bounds__(16 * JW) void k_bb_lde_pa16x2(const u32* __restrict
     u32 orig[16];
 #pragma unroll
     for (u32 a1 = 0; a1 < 16; a1++) orig[a1] = cin[(size_t)(a1 * 16 + hi4) << 12];  // stage-1 thread = (a0 = hi4, j)
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, 16 * l);
-    const u32 f0 = bb_tw_split16(tw_hi, tw_lo, brev4(hi4) * l);  // w_n^(k_a1 l)
+    const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, 16 * l);
+    const u32 f0 = tw_split16<BbF>(tw_hi, tw_lo, brev4(hi4) * l);  // w_n^(k_a1 l)
     u32 tw[16];
-    load_tw16(tw, tw4096, hi4 * 16);  // w_256^(k_a1 a0): the same for every coset
+    load_tw16<BbF>(tw, tw4096, hi4 * 16);  // w_256^(k_a1 a0): the same for every coset
     for (u32 c = 0; c < (1u << rate_bits); c++) {
         const u32* ph = pow_hi + (size_t)c * 256 + hi4;
         u32 x[16];
@@ -292,10 +280,10 @@ __global__ __launch_bounds__(1024) void k_bb_lde_pa16x2w(const u32* __restrict__
     for (u32 h = 0; h < H; h++)
 #pragma unroll
         for (u32 a1 = 0; a1 < 16; a1++) orig[h][a1] = cin[(size_t)((b + 2 * h) * 256 + a1 * 16 + hi4) << 12];
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, 16 * l);          // tables of m = 2^20 rows
-    const u32 f0 = bb_tw_split16(tw_hi, tw_lo, brev4(hi4) * l);
+    const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, 16 * l);          // tables of m = 2^20 rows
+    const u32 f0 = tw_split16<BbF>(tw_hi, tw_lo, brev4(hi4) * l);
     u32 tw[16];
-    load_tw16(tw, tw4096, hi4 * 16);  // w_256^(k_a1 a0)
+    load_tw16<BbF>(tw, tw4096, hi4 * 16);  // w_256^(k_a1 a0)
     // lane mask of the digit bit, opaque to the optimiser: written as selects on a lane-varying bool the butterflies below made the
     // compiler spill registers (it unswitched around them); as bit blends (v_bfi) they cost the same and spill nothing
     u32 m5 = b ? ~0u : 0u;
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(256 << K, 4) void k_bb_lde_pa32(const u32* __restri
     constexpr u32 L = 20 + K, A0 = 8u << K, NT = 256u << K, SLOT = NT, ROWS = 256u << K, JW = 32;
     __shared__ u32 sh[32 * SLOT];      // [k_a1 slot][a0][j]
     __shared__ u32 twl[ROWS];          // w_ROWS^m: the inter-stage twiddles
-    __shared__ u32 phs[2][ROWS];       // s_c^(4096 a') of this coset and of the next (see k_gl_lde_pa32)
+    __shared__ u32 phs[2][ROWS];       // s_c^(4096 a') of this coset and of the next (see kernels_ntt16.hip's k_gl_lde_pa32)
     const size_t col = blockIdx.x >> 7;
     const u32 tg = blockIdx.x & 127;
     const u32 tid = threadIdx.x, hi = tid >> 5, j = tid & 31;
@@ -381,7 +369,7 @@ __global__ __launch_bounds__(256 << K, 4) void k_bb_lde_pa32(const u32* __restri
 #pragma unroll
     for (u32 a1 = 0; a1 < 32; a1++) orig[a1] = cin[(size_t)(a1 * A0 + hi) << 12];
     __syncthreads();
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, 32 * l);   // w_n^(32 l)
+    const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, 32 * l);   // w_n^(32 l)
     const u32 ncosets = 1u << rate_bits;
     u32 sl_next = pow_lo[l];
     for (u32 c = 0; c < ncosets; c++) {
@@ -404,7 +392,7 @@ __global__ __launch_bounds__(256 << K, 4) void k_bb_lde_pa32(const u32* __restri
 #pragma unroll
             for (u32 a0 = 0; a0 < 32; a0++) x[a0] = sh[hi * SLOT + a0 * JW + j];
             dft32<false>(x);
-            u32 f = bb::mul(sl, bb_tw_split16(tw_hi, tw_lo, brevk(hi, 5) * l));
+            u32 f = bb::mul(sl, tw_split16<BbF>(tw_hi, tw_lo, brevk(hi, 5) * l));
 #pragma unroll
             for (u32 k = 0; k < 32; k++) {
                 out[(size_t)(hi * 32 + brevk(k, 5)) << 12] = bb::mul(x[brevk(k, 5)], f);
@@ -418,7 +406,7 @@ __global__ __launch_bounds__(256 << K, 4) void k_bb_lde_pa32(const u32* __restri
 #pragma unroll
                 for (u32 a0 = 0; a0 < 16; a0++) y[a0] = sh[slot * SLOT + a0 * JW + j];
                 dft16<false>(y);
-                u32 f = bb::mul(sl, bb_tw_split16(tw_hi, tw_lo, brevk(slot, 5) * l));
+                u32 f = bb::mul(sl, tw_split16<BbF>(tw_hi, tw_lo, brevk(slot, 5) * l));
 #pragma unroll
                 for (u32 k = 0; k < 16; k++) {
                     out[(size_t)(slot * 16 + brev4(k)) << 12] = bb::mul(y[brev4(k)], f);
@@ -476,8 +464,8 @@ __global__ __launch_bounds__(THREADS) void k_bb_lde_pa16xs(const u32* __restrict
 #pragma unroll
             for (u32 b = 0; b < R; b++) y[b] = sh[s2 * 256 + b * M + jj];
             dft_small<false, K>(y);
-            u32 f = bb::mul(pow_lo[(size_t)c * 4096 + l], bb_tw_split16(tw_hi, tw_lo, ka1 * l));
-            const u32 ratio = bb_tw_split16(tw_hi, tw_lo, 16 * l);
+            u32 f = bb::mul(pow_lo[(size_t)c * 4096 + l], tw_split16<BbF>(tw_hi, tw_lo, ka1 * l));
+            const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, 16 * l);
             u32* out = lde + (col << (L + rate_bits)) + (size_t)c * n + l;
 #pragma unroll
             for (u32 k = 0; k < R; k++) {  // row position = brev_LA(k_a) = slot * 2^K + brevK(k')
@@ -503,7 +491,7 @@ __global__ __launch_bounds__(THREADS) void k_bb_lde_pa_small(const u32* __restri
 #pragma unroll
     for (u32 a = 0; a < R; a++) orig[a] = cin[(size_t)a << 12];
     const u32 ncosets = 1u << rate_bits;
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, l);  // w_n^l
+    const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, l);  // w_n^l
     for (u32 c = 0; c < ncosets; c++) {
         const u32* ph = pow_hi + ((size_t)c << K);
         u32 x[16];
@@ -533,7 +521,7 @@ __global__ __launch_bounds__(THREADS) void k_bb_lde_pa16x1(const u32* __restrict
 #pragma unroll
     for (u32 a = 0; a < 16; a++) orig[a] = cin[(size_t)a << 12];
     const u32 ncosets = 1u << rate_bits;
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, l);
+    const u32 ratio = tw_split16<BbF>(tw_hi, tw_lo, l);
     for (u32 c = 0; c < ncosets; c++) {
         const u32* ph = pow_hi + (size_t)c * 16;
         u32 x[16];
@@ -550,204 +538,27 @@ __global__ __launch_bounds__(THREADS) void k_bb_lde_pa16x1(const u32* __restrict
     }
 }
 
-// ------------------------------------------------------------------ inverse NTT passes (LA = 8, LB in {0, 4}, LC = 8)
-struct BbInv16Geom {
-    u32 L, LB;  // LA = LC = 8, LL = LB + 8
-};
+// ------------------------------------------------------------------ launchers (called from ntt_passes.hpp's lde_columns<BbF>)
 
-// P1: grid = ncols * 2^(LL-4); tile 256 rows (a) x 16 contiguous; rows written in natural k_a order.
-// WB (round 4): the input is CANONICAL - the transform is linear and every twiddle product multiplies by the twiddle's value
-// (x (w R) / R), so canonical words go through it unchanged in scale and P3's last factor n^-1 R^2 instead of n^-1 R brings the
-// coefficients out in Montgomery form: no conversion pass (k_bb_to_mont: a read and a write of the whole witness).  The columns
-// somebody reads as VALUES afterwards - the routed wires, for the permutation argument - are written back in Montgomery form
-// here, each element by the one thread that has just read it (col < mont_cols).
-template <bool WB>
-__global__ __launch_bounds__(THREADS) void k_bb_intt16_p1(const u32* src, u32* __restrict__ dst, BbInv16Geom g,
-                                                          const u32* __restrict__ tw4096, const u32* __restrict__ tw_hi,
-                                                          const u32* __restrict__ tw_lo, u32* src_mont, u32 mont_cols) {
-    __shared__ u32 sh[16 * 272];
-    const u32 LL = g.LB + 8;
-    const u32 tiles_per_col = 1u << (LL - 4);
-    const size_t col = blockIdx.x / tiles_per_col;
-    const u32 tg = blockIdx.x % tiles_per_col;
-    const size_t base = (col << g.L) + ((size_t)tg << 4);
-    const u32 tid = threadIdx.x, hi4 = tid >> 4, j = tid & 15;
-    u32 x[16];
-#pragma unroll
-    for (u32 a1 = 0; a1 < 16; a1++) x[a1] = src[base + ((size_t)(a1 * 16 + hi4) << LL) + j];
-    if (WB && col < mont_cols) {
-#pragma unroll
-        for (u32 a1 = 0; a1 < 16; a1++) src_mont[base + ((size_t)(a1 * 16 + hi4) << LL) + j] = bb::to_mont(x[a1]);
-    }
-    u32 tw[16];
-    load_tw16(tw, tw4096, hi4 * 16);
-    const u32 l = (tg << 4) + j;
-    const u32 ka1 = brev4(hi4);
-    // output twiddle w_n^-(k_a l), k_a = k_a1 + 16 k: a geometric progression in k with ratio w_n^-(16 l)
-    u32 f = bb_tw_split16(tw_hi, tw_lo, ka1 * l);
-    const u32 ratio = bb_tw_split16(tw_hi, tw_lo, 16 * l);
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) sh[s * 272 + tid] = s ? bb::mul(x[s], tw[s]) : x[s];
-    __syncthreads();
-#pragma unroll
-    for (u32 a0 = 0; a0 < 16; a0++) x[a0] = sh[hi4 * 272 + a0 * 16 + j];
-    dft16<true>(x);
-#pragma unroll
-    for (u32 k = 0; k < 16; k++) {
-        dst[base + ((size_t)(ka1 + 16 * k) << LL) + j] = bb::mul(x[brev4(k)], f);
-        if (k < 15) f = bb::mul(f, ratio);
-    }
-}
-
-// P2 (LB = 4): grid = ncols * 16 * 16; tile 16 k_a x 16 b x 16 c; src [k_a][b][c] -> dst [k_b][k_a][c]
-__global__ __launch_bounds__(THREADS) void k_bb_intt16_p2(const u32* __restrict__ src, u32* __restrict__ dst, u32 L,
-                                                          const u32* __restrict__ tw4096) {
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ia = threadIdx.x >> 4, jc = threadIdx.x & 15;
-    const u32 ka = 16 * ga + ia, c = 16 * gc + jc;
-    u32 x[16];
-#pragma unroll
-    for (u32 b = 0; b < 16; b++) x[b] = src[cbase + ((size_t)ka << 12) + ((size_t)b << 8) + c];
-    u32 tw[16];
-    load_tw16(tw, tw4096, c);  // w_4096^-(c k_b)
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++)
-        dst[cbase + ((size_t)brev4(s) << 16) + ((size_t)ka << 8) + c] = s ? bb::mul(x[s], tw[s]) : x[s];
-}
-
-// P2 for LB = K in 1..3 (L = 16 + K): the same pass with a radix-2^K DFT over b; src [k_a][b][c] -> dst [k_b][k_a][c]
-template <int K>
-__global__ __launch_bounds__(THREADS) void k_bb_intt16_p2s(const u32* __restrict__ src, u32* __restrict__ dst, const u32* __restrict__ tw4096) {
-    constexpr u32 L = 16 + K, R = 1u << K;
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ka = 16 * ga + (threadIdx.x >> 4), c = 16 * gc + (threadIdx.x & 15);
-    u32 x[16];
-#pragma unroll
-    for (u32 b = 0; b < R; b++) x[b] = src[cbase + ((size_t)ka << (8 + K)) + ((size_t)b << 8) + c];
-    u32 tw[R];
-#pragma unroll
-    for (u32 s = 1; s < R; s++) tw[s] = tw4096[(brevk(s, K) * c) << (4 - K)];  // w_{2^(8+K)}^-(c k_b)
-    dft_small<true, K>(x);
-#pragma unroll
-    for (u32 s = 0; s < R; s++)
-        dst[cbase + ((size_t)brevk(s, K) << 16) + ((size_t)ka << 8) + c] = s ? bb::mul(x[s], tw[s]) : x[s];
-}
-
-// P2 for LB = 5, 6 (2^21 and 2^22 rows, round 6): the middle pass as a radix-32 / radix-64 DFT over b in registers - one or two DIF
-// layers with compile-time twiddles w_64^-j, then 16-point blocks.  src [k_a][b][c] -> dst [k_b][k_a][c]; tw16k = w_{2^14}^-j, j < 2^14.
-template <int LB>
-__global__ __launch_bounds__(THREADS) void k_bb_intt16_p2w(const u32* __restrict__ src, u32* __restrict__ dst, const u32* __restrict__ tw16k) {
-    constexpr u32 L = 16 + LB, R = 1u << LB;
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ka = 16 * ga + (threadIdx.x >> 4), c = 16 * gc + (threadIdx.x & 15);
-    u32 x[R];
-#pragma unroll
-    for (u32 b = 0; b < R; b++) x[b] = src[cbase + ((size_t)ka << (8 + LB)) + ((size_t)b << 8) + c];
-    if constexpr (LB == 6) {
-        layer64<true, 32, 0>(x);
-        layer64<true, 16, 0>(x);
-        layer64<true, 16, 32>(x);
-    } else {
-        layer64<true, 16, 0>(x);
-    }
-#pragma unroll
-    for (u32 o = 0; o < R; o += 16) dft16<true>(*reinterpret_cast<u32(*)[16]>(&x[o]));
-#pragma unroll
-    for (u32 s = 0; s < R; s++) {
-        const u32 kb = brevk(s, LB);
-        dst[cbase + ((size_t)kb << 16) + ((size_t)ka << 8) + c] = s ? bb::mul(x[s], tw16k[(kb * c) << (6 - LB)]) : x[s];   // w_{2^(8+LB)}^-(c k_b)
-    }
-}
-
-// P3: grid = ncols * 2^LB * 16; tile 16 k_a x 256 c (c = 16 c1 + c0); src [k_b][k_a][c];
-// dst natural k = k_a + 256 k_b + 2^(8+LB) k_c, scaled by n^-1
-__global__ __launch_bounds__(THREADS) void k_bb_intt16_p3(const u32* __restrict__ src, u32* __restrict__ dst, BbInv16Geom g,
-                                                          const u32* __restrict__ tw4096, u32 n_inv) {
-    __shared__ u32 sh[16 * 272];
-    const u32 nb = 1u << g.LB;
-    const size_t col = blockIdx.x / (nb * 16);
-    const u32 rem = blockIdx.x % (nb * 16);
-    const u32 kb = rem >> 4, ga = rem & 15;
-    const size_t cbase = col << g.L;
-    const size_t sbase = cbase + ((size_t)kb << 16) + ((size_t)(16 * ga) << 8);
-    const u32 tid = threadIdx.x, hi4 = tid >> 4, lo4 = tid & 15;
-    u32 x[16];
-    // stage 1 thread = (ia = hi4, c0 = lo4): digit c1
-#pragma unroll
-    for (u32 c1 = 0; c1 < 16; c1++) x[c1] = src[sbase + hi4 * 256 + c1 * 16 + lo4];
-    u32 tw[16];
-    load_tw16(tw, tw4096, lo4 * 16);  // w_256^-(k_c1 c0)
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) sh[s * 272 + lo4 * 17 + hi4] = s ? bb::mul(x[s], tw[s]) : x[s];  // [k_c1 slot][c0][ia], rows padded to 17
-    __syncthreads();
-    // stage 2 thread = (k_c1 slot = hi4, ia = lo4): digit c0
-#pragma unroll
-    for (u32 c0 = 0; c0 < 16; c0++) x[c0] = sh[hi4 * 272 + c0 * 17 + lo4];
-    dft16<true>(x);
-    const u32 kc1 = brev4(hi4);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) {
-        const u32 kc = kc1 + 16 * brev4(s);
-        dst[cbase + ((size_t)kc << (8 + g.LB)) + ((size_t)kb << 8) + 16 * ga + lo4] = bb::mul(x[s], n_inv);
-    }
-}
-
-// ------------------------------------------------------------------ launchers (called from kernels_ntt.hip's dispatchers)
-
-// canonical_src != nullptr: the input is canonical (= canonical_src, writable), its first mont_cols columns are overwritten with their
-// Montgomery form, the coefficients come out in Montgomery form like those of a Montgomery-form input
-bool bb_intt_columns_r16(const u32* src, u32* coeffs, u32* scratch, size_t ncols, const BbNttTables& t, hipStream_t stream,
-                         u32* canonical_src, size_t mont_cols) {
-    const u32 L = t.log_n;
-    if (L < 16 || L > 22) return false;
-    BbInv16Geom g{L, L - 16};
-    const u32 LL = g.LB + 8;
-    u32* p1_dst = g.LB ? coeffs : scratch;
-    const u32 n_inv = canonical_src ? bb::to_mont(t.n_inv) : t.n_inv;   // n^-1 R^2 : n^-1 R
-    if (canonical_src)
-        hipLaunchKernelGGL(k_bb_intt16_p1<true>, dim3((u32)(ncols << (LL - 4))), dim3(THREADS), 0, stream, canonical_src, p1_dst, g, t.tw4096_inv,
-                           t.tw_hi_inv, t.tw_lo_inv, canonical_src, (u32)std::min<size_t>(mont_cols, ncols));
-    else
-        hipLaunchKernelGGL(k_bb_intt16_p1<false>, dim3((u32)(ncols << (LL - 4))), dim3(THREADS), 0, stream, src, p1_dst, g, t.tw4096_inv,
-                           t.tw_hi_inv, t.tw_lo_inv, (u32*)nullptr, 0u);
-    const dim3 g2((u32)(ncols << 8));
-    if (g.LB == 6) hipLaunchKernelGGL(k_bb_intt16_p2w<6>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw16k_inv);
-    else if (g.LB == 5) hipLaunchKernelGGL(k_bb_intt16_p2w<5>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw16k_inv);
-    else if (g.LB == 4) hipLaunchKernelGGL(k_bb_intt16_p2, g2, dim3(THREADS), 0, stream, coeffs, scratch, L, t.tw4096_inv);
-    else if (g.LB == 3) hipLaunchKernelGGL(k_bb_intt16_p2s<3>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv);
-    else if (g.LB == 2) hipLaunchKernelGGL(k_bb_intt16_p2s<2>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv);
-    else if (g.LB == 1) hipLaunchKernelGGL(k_bb_intt16_p2s<1>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv);
-    hipLaunchKernelGGL(k_bb_intt16_p3, dim3((u32)(ncols << (g.LB + 4))), dim3(THREADS), 0, stream, scratch, coeffs, g,
-                       t.tw4096_inv, n_inv);
-    return true;
-}
-
-bool bb_lde_pa_r16(const u32* coeffs, u32* lde, size_t ncols, const BbNttTables& t, const BbCosetTables& ct, hipStream_t stream) {
+// The 2^22-row pass reads the tables of the 2^20-row transform (t.wide) and the cosets of the rate r + 2 (ct.fine): tables_for /
+// cosets_for build both at that size, and no other pass handles it
+void lde_pa_r16(const u32* coeffs, u32* lde, size_t ncols, const BbNttTables& t, const BbCosetTables& ct, hipStream_t stream) {
     const u32 L = t.log_n;
     if (L == 20) {
         hipLaunchKernelGGL(k_bb_lde_pa16x2<32>, dim3((u32)(ncols << 7)), dim3(512), 0, stream, coeffs, lde, L, ct.rate_bits,
                            t.tw4096_fwd, t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
-        return true;
+        return;
     }
     if (L == 21 || L == 22) {
         if (L == 21) {
             hipLaunchKernelGGL(k_bb_lde_pa32<1>, dim3((u32)(ncols << 7)), dim3(512), 0, stream, coeffs, lde, ct.rate_bits, t.tw4096_fwd,
                                t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
         } else {   // twiddles of the 2^20-row transform (t.wide), cosets of the rate r + 2 (ct.fine), s_c^(4096 a') of this size
-            if (!t.wide || !ct.fine) return false;
+            assert(t.wide && ct.fine && "the 2^22-row LDE pass needs the 2^20-row twiddles and the rate r + 2 cosets");
             hipLaunchKernelGGL(k_bb_lde_pa16x2w<2>, dim3((u32)(ncols << 7)), dim3(1024), 0, stream, coeffs, lde, ct.rate_bits, t.tw4096_fwd,
                                t.wide->tw_hi_fwd, t.wide->tw_lo_fwd, ct.fine->pow_lo, ct.pow_hi);
         }
-        return true;
+        return;
     }
 #define GB_PAS(KK)                                                                                                        \
     hipLaunchKernelGGL(k_bb_lde_pa16xs<KK>, dim3((u32)(ncols << (4 + KK))), dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, \
@@ -757,23 +568,31 @@ bool bb_lde_pa_r16(const u32* coeffs, u32* lde, size_t ncols, const BbNttTables&
         if (L == 13) hipLaunchKernelGGL(k_bb_lde_pa_small<1>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
         if (L == 14) hipLaunchKernelGGL(k_bb_lde_pa_small<2>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
         if (L == 15) hipLaunchKernelGGL(k_bb_lde_pa_small<3>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
-        return true;
+        return;
     }
-    if (L == 17) { GB_PAS(1); return true; }
-    if (L == 18) { GB_PAS(2); return true; }
-    if (L == 19) { GB_PAS(3); return true; }
+    if (L == 17) { GB_PAS(1); return; }
+    if (L == 18) { GB_PAS(2); return; }
+    if (L == 19) { GB_PAS(3); return; }
 #undef GB_PAS
-    if (L == 16) {
+    if (L == 16)
         hipLaunchKernelGGL(k_bb_lde_pa16x1, dim3((u32)(ncols << 4)), dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits,
                            t.tw_hi_fwd, t.tw_lo_fwd, ct.pow_lo, ct.pow_hi);
-        return true;
-    }
-    return false;
 }
 
-void bb_lde_pb_r16(u32* lde, size_t ntiles, const BbNttTables& t, hipStream_t stream) {
+void lde_pb_r16(u32* lde, size_t ntiles, const BbNttTables& t, hipStream_t stream) {
     const u32 grid = (u32)std::min<size_t>(ntiles, 256 * 7);  // persistent: 7 workgroups per CU (65 VGPRs, 17 KB LDS each)
     hipLaunchKernelGGL(k_bb_lde_pb16, dim3(grid), dim3(THREADS), 0, stream, lde, t.tw4096_fwd, (u32)ntiles);
 }
+
+bool bb_intt_columns_canonical(u32* vals, u32* coeffs, u32* scratch, size_t ncols, size_t mont_cols, const BbNttTables& t, hipStream_t stream) {
+    if (t.log_n < 16 || t.log_n > NTT_NATIVE_LOG) return false;
+    const size_t n = (size_t)1 << t.log_n;
+    for_intt_groups<BbF>(t.log_n, ncols, [&](size_t c0, size_t nc) {
+        intt_columns_r16<BbF, true>(vals + c0 * n, coeffs + c0 * n, scratch, nc, t, stream, vals + c0 * n, mont_cols > c0 ? mont_cols - c0 : 0);
+    });
+    return true;
+}
+
+GB_INSTANTIATE_NTT(BbF)
 
 }  // namespace gbk

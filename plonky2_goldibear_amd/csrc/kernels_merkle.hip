@@ -217,35 +217,12 @@ __global__ void k_gl_digests_to_reference(const u64* __restrict__ levels, u64* _
     for (int e = 0; e < 4; e++) out[4 * dst + e] = levels[4 * g + e];
 }
 
-__global__ void k_gl_gather_row(const u64* __restrict__ cols, size_t col_stride, u32 width, u64 index, u64* dst) {
-    u32 c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < width) dst[c] = cols[(size_t)c * col_stride + index];
-}
-
 __global__ void k_gl_gather_siblings(const u64* __restrict__ levels, u32 log_leaves, u32 cap_height, u64 leaf, u64* dst) {
     u32 i = threadIdx.x >> 2, e = threadIdx.x & 3;
     if (i >= log_leaves - cap_height) return;
     u64 N = (u64)1 << log_leaves;
     u64 off = 2 * N - ((2 * N) >> i);
     dst[4 * i + e] = levels[4 * (off + ((leaf >> i) ^ 1)) + e];
-}
-
-__global__ void k_u64_bitrev_copy(const u64* __restrict__ src, u64* __restrict__ dst, u32 bits, size_t total) {
-    size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    size_t col = g >> bits;
-    u64 j = g & (((u64)1 << bits) - 1);
-    u64 r = bits ? (__brevll(j) >> (64 - bits)) : 0;
-    dst[g] = src[(col << bits) + r];
-}
-
-__global__ void k_u64_transpose_to_rows(const u64* __restrict__ cols, size_t col_stride, u32 width, u64 rows,
-                                        u64* __restrict__ dst) {
-    u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= rows * width) return;
-    u64 r = g / width;
-    u32 c = (u32)(g % width);
-    dst[g] = cols[(size_t)c * col_stride + r];
 }
 
 // raw permutation, canonical in and out, through the same MFMA form the tree kernels use (gb_permute: the reference's KATs)
@@ -312,23 +289,9 @@ void gl_digests_to_reference_layout(const u64* levels, u64* out, u32 log_leaves,
     hipLaunchKernelGGL(k_gl_digests_to_reference, dim3(blocks_for(total, 256)), dim3(256), 0, stream, levels, out,
                        log_leaves, cap_height);
 }
-void gl_gather_row(const u64* cols, size_t col_stride, u32 width, u64 index, u64* dst, hipStream_t stream) {
-    hipLaunchKernelGGL(k_gl_gather_row, dim3(blocks_for(width, 64)), dim3(64), 0, stream, cols, col_stride, width, index,
-                       dst);
-}
 void gl_gather_siblings(const u64* levels, u32 log_leaves, u32 cap_height, u64 leaf, u64* dst, hipStream_t stream) {
     if (log_leaves == cap_height) return;
     hipLaunchKernelGGL(k_gl_gather_siblings, dim3(1), dim3(256), 0, stream, levels, log_leaves, cap_height, leaf, dst);
-}
-void u64_bitrev_copy(const u64* src, u64* dst, u32 bits, size_t ncols, hipStream_t stream) {
-    size_t total = ncols << bits;
-    if (!total) return;
-    hipLaunchKernelGGL(k_u64_bitrev_copy, dim3(blocks_for(total, 256)), dim3(256), 0, stream, src, dst, bits, total);
-}
-void u64_transpose_to_rows(const u64* cols, size_t col_stride, u32 width, u64 rows, u64* dst, hipStream_t stream) {
-    if (!rows || !width) return;
-    hipLaunchKernelGGL(k_u64_transpose_to_rows, dim3(blocks_for(rows * width, 256)), dim3(256), 0, stream, cols,
-                       col_stride, width, rows, dst);
 }
 void gl_poseidon_permute(const u64* in, u64* out, u64 count, hipStream_t stream) {
     hipLaunchKernelGGL(k_gl_poseidon_permute, dim3(blocks_for(count, 256)), dim3(256), 0, stream, in, out, count);

@@ -7,18 +7,13 @@
 // A thread keeps 16 points in registers for four layers; general twiddles (tables) appear only between
 // radix-16 stages, and LDS is touched once per stage instead of once per layer.
 //
-// Same passes, tiles and memory layouts as kernels_ntt.hip (whose LDS radix-2 passes remain for the inverse transform of
-// 2^13..2^15 rows and for single-tile sizes):
-//   inverse:  P1 (8 bits strided)  P2 (0..4 bits)  P3 (8 bits, transposed write)            2^16..2^20 rows
-//   LDE:      PA (4..8 bits strided, per-coset loop)  PB (12 bits contiguous, natural -> leaf order)
+// Pass structure and dispatch: ntt_passes.hpp, shared with BabyBear.  What is Goldilocks' own: the register DFTs below (Dft<GlF>) and
+// the LDE's radix-16 passes - PA (1..10 bits strided, per-coset loop), PB (12 bits contiguous, natural -> leaf order).
 #include "kernels.hpp"
 #include "gl_field.hpp"
+#include "ntt_passes.hpp"
 
 namespace gbk {
-
-static constexpr int THREADS = 256;
-
-__device__ __forceinline__ constexpr u32 brev4(u32 x) { return ((x & 1) << 3) | ((x & 2) << 1) | ((x & 4) >> 1) | ((x & 8) >> 3); }
 
 // x * 2^K mod p, canonical in, canonical out, 0 <= K < 96.  With f = 2^32 (f^2 = f - 1, f^3 = -1 mod p) and
 // y = x 2^(K mod 32) = y0 + y1 f + y2 f^2 (y2 < 2^(K mod 32)), multiplying on by f^(K / 32) only shuffles limbs:
@@ -116,11 +111,6 @@ __device__ __forceinline__ void dft_small(u64 (&x)[16]) {
 #pragma unroll
     for (int o = 0; o < (1 << K); o += 2) bfly<INV, 1, 0>(x[o], x[o + 1]);
 }
-__device__ __forceinline__ constexpr u32 brevk(u32 x, int k) {
-    u32 r = 0;
-    for (int i = 0; i < k; i++) r |= ((x >> i) & 1) << (k - 1 - i);
-    return r;
-}
 
 // (a - b) * w_64^(+-M): w_64 = 2^39 (w_64^4 = w_16 = 2^156), w_64^-1 = 2^153 - shifts like the roots of the 16-point DFT
 template <bool INV, int M>
@@ -149,19 +139,15 @@ __device__ __forceinline__ void dft32(u64 (&x)[32]) {
     dft16<INV>(*reinterpret_cast<u64(*)[16]>(&x[16]));
 }
 
-__device__ __forceinline__ u64 tw_split16(const u64* __restrict__ hi, const u64* __restrict__ lo, u32 e) {
-    u32 eh = e >> 10, el = e & 1023;
-    u64 w = lo[el];
-    return eh ? gl::mul_mont_lazy(w, hi[eh]) : w;   // Montgomery-form tables: (lo R)(hi R) / R = lo hi R, any residue
-}
-
-// The 15 inter-stage twiddles w_4096^(k m), k = brev4(slot), as ONE batch of independent loads issued before the
-// DFT that precedes their use.  (Loaded one by one behind `if (e)` each of them cost a full memory round trip:
-// rocprofv3 showed the waves of these kernels parked in s_waitcnt for 46-66 % of their lifetime.)
-__device__ __forceinline__ void load_tw16(u64 (&tw)[16], const u64* __restrict__ tw4096, u32 m) {
-#pragma unroll
-    for (u32 s = 1; s < 16; s++) tw[s] = tw4096[brev4(s) * m];
-}
+template <>
+struct Dft<GlF> {
+    template <bool INV>
+    static __device__ __forceinline__ void dft16(u64 (&x)[16]) { gbk::dft16<INV>(x); }
+    template <bool INV, int K>
+    static __device__ __forceinline__ void dft_small(u64 (&x)[16]) { gbk::dft_small<INV, K>(x); }
+    template <bool INV, int H, int O>
+    static __device__ __forceinline__ void layer64(u64* x) { gbk::layer64<INV, H, O>(x); }
+};
 
 // ------------------------------------------------------------------ LDE pass B: 4096 contiguous points, 3 radix-16 stages
 // grid = number of 4096-tiles of `lde` (in place).  natural -> bit-reversed.
@@ -236,8 +222,8 @@ __global__ __launch_bounds__(THREADS, 3) void k_gl_lde_pa16x2(const u64* __restr
 #pragma unroll
     for (u32 a1 = 0; a1 < 16; a1++) orig[a1] = cin[(size_t)(a1 * 16 + hi4) << 12];  // stage-1 thread = (a0 = hi4, j)
     __syncthreads();  // tw256 visible
-    const u64 ratio = tw_split16(tw_hi, tw_lo, 16 * l);
-    const u64 f0 = tw_split16(tw_hi, tw_lo, brev4(hi4) * l);  // w_n^(k_a1 l)
+    const u64 ratio = tw_split16<GlF>(tw_hi, tw_lo, 16 * l);
+    const u64 f0 = tw_split16<GlF>(tw_hi, tw_lo, brev4(hi4) * l);  // w_n^(k_a1 l)
     for (u32 c = 0; c < (1u << rate_bits); c++) {
         const u64* ph = pow_hi + (size_t)c * 256 + hi4;
         u64 x[16];
@@ -300,7 +286,7 @@ __global__ __launch_bounds__(128 << K, 2) void k_gl_lde_pa32(const u64* __restri
 #pragma unroll
     for (u32 a1 = 0; a1 < 32; a1++) orig[a1] = cin[(size_t)(a1 * A0 + hi) << 12];
     __syncthreads();  // twl, phs[0] visible
-    const u64 ratio = tw_split16(tw_hi, tw_lo, 32 * l);   // w_n^(32 l)
+    const u64 ratio = tw_split16<GlF>(tw_hi, tw_lo, 32 * l);   // w_n^(32 l)
     const u32 ncosets = 1u << rate_bits;
     u64 sl_next = pow_lo[l];
     for (u32 c = 0; c < ncosets; c++) {
@@ -326,7 +312,7 @@ __global__ __launch_bounds__(128 << K, 2) void k_gl_lde_pa32(const u64* __restri
 #pragma unroll
             for (u32 a0 = 0; a0 < 32; a0++) x[a0] = sh[hi * SLOT + a0 * 16 + j];
             dft32<false>(x);
-            u64 f = gl::mul_mont_lazy<true>(sl, tw_split16(tw_hi, tw_lo, brevk(hi, 5) * l));   // s^l w_n^(k_a1 l)
+            u64 f = gl::mul_mont_lazy<true>(sl, tw_split16<GlF>(tw_hi, tw_lo, brevk(hi, 5) * l));   // s^l w_n^(k_a1 l)
 #pragma unroll
             for (u32 k = 0; k < 32; k++) {  // k_a' = k_a1 + 32 k: row position brev10(k_a') = hi * 32 + brev5(k)
                 out[(size_t)(hi * 32 + brevk(k, 5)) << 12] = gl::mul_mont<true>(x[brevk(k, 5)], f);
@@ -340,7 +326,7 @@ __global__ __launch_bounds__(128 << K, 2) void k_gl_lde_pa32(const u64* __restri
 #pragma unroll
                 for (u32 a0 = 0; a0 < 16; a0++) y[a0] = sh[slot * SLOT + a0 * 16 + j];
                 dft16<false>(y);
-                u64 f = gl::mul_mont_lazy<true>(sl, tw_split16(tw_hi, tw_lo, brevk(slot, 5) * l));
+                u64 f = gl::mul_mont_lazy<true>(sl, tw_split16<GlF>(tw_hi, tw_lo, brevk(slot, 5) * l));
 #pragma unroll
                 for (u32 k = 0; k < 16; k++) {  // row position brev9(k_a1 + 32 k) = slot * 16 + brev4(k)
                     out[(size_t)(slot * 16 + brev4(k)) << 12] = gl::mul_mont<true>(y[brev4(k)], f);
@@ -401,8 +387,8 @@ __global__ __launch_bounds__(THREADS, 3) void k_gl_lde_pa16xs(const u64* __restr
             for (u32 b = 0; b < R; b++) y[b] = sh[s2 * 272 + b * M + jj];
             dft_small<false, K>(y);
             // output twiddle s^l w_n^(k_a l), k_a = k_a1 + 16 k': a geometric progression in k' with ratio w_n^(16 l)
-            u64 f = gl::mul_mont_lazy(pow_lo[(size_t)c * 4096 + l], tw_split16(tw_hi, tw_lo, ka1 * l));
-            const u64 ratio = tw_split16(tw_hi, tw_lo, 16 * l);
+            u64 f = gl::mul_mont_lazy(pow_lo[(size_t)c * 4096 + l], tw_split16<GlF>(tw_hi, tw_lo, ka1 * l));
+            const u64 ratio = tw_split16<GlF>(tw_hi, tw_lo, 16 * l);
             u64* out = lde + (col << (L + rate_bits)) + (size_t)c * n + l;
 #pragma unroll
             for (u32 k = 0; k < R; k++) {  // row position = brev_LA(k_a) = slot * 2^K + brevK(k')
@@ -428,7 +414,7 @@ __global__ __launch_bounds__(THREADS) void k_gl_lde_pa_small(const u64* __restri
 #pragma unroll
     for (u32 a = 0; a < R; a++) orig[a] = cin[(size_t)a << 12];
     const u32 ncosets = 1u << rate_bits;
-    const u64 ratio = tw_split16(tw_hi, tw_lo, l);  // w_n^l
+    const u64 ratio = tw_split16<GlF>(tw_hi, tw_lo, l);  // w_n^l
     for (u32 c = 0; c < ncosets; c++) {
         const u64* ph = pow_hi + ((size_t)c << K);
         u64 x[16];
@@ -458,7 +444,7 @@ __global__ __launch_bounds__(THREADS) void k_gl_lde_pa16x1(const u64* __restrict
 #pragma unroll
     for (u32 a = 0; a < 16; a++) orig[a] = cin[(size_t)a << 12];
     const u32 ncosets = 1u << rate_bits;
-    const u64 ratio = tw_split16(tw_hi, tw_lo, l);
+    const u64 ratio = tw_split16<GlF>(tw_hi, tw_lo, l);
     for (u32 c = 0; c < ncosets; c++) {
         const u64* ph = pow_hi + (size_t)c * 16;
         u64 x[16];
@@ -475,178 +461,16 @@ __global__ __launch_bounds__(THREADS) void k_gl_lde_pa16x1(const u64* __restrict
     }
 }
 
-// ------------------------------------------------------------------ inverse NTT passes (LA = 8, LB in {0, 4}, LC = 8)
-struct Inv16Geom {
-    u32 L, LB;  // LA = LC = 8, LL = LB + 8
-};
-
-// P1: grid = ncols * 2^(LL-4); tile 256 rows (a) x 16 contiguous; rows written in natural k_a order
-__global__ __launch_bounds__(THREADS) void k_gl_intt16_p1(const u64* __restrict__ src, u64* __restrict__ dst, Inv16Geom g,
-                                                          const u64* __restrict__ tw4096, const u64* __restrict__ tw_hi,
-                                                          const u64* __restrict__ tw_lo) {
-    __shared__ u64 sh[16 * 272];
-    const u32 LL = g.LB + 8;
-    const u32 tiles_per_col = 1u << (LL - 4);
-    const size_t col = blockIdx.x / tiles_per_col;
-    const u32 tg = blockIdx.x % tiles_per_col;
-    const size_t base = (col << g.L) + ((size_t)tg << 4);
-    const u32 tid = threadIdx.x, hi4 = tid >> 4, j = tid & 15;
-    u64 x[16];
-#pragma unroll
-    for (u32 a1 = 0; a1 < 16; a1++) x[a1] = src[base + ((size_t)(a1 * 16 + hi4) << LL) + j];
-    u64 tw[16];
-    load_tw16(tw, tw4096, hi4 * 16);
-    const u32 l = (tg << 4) + j;
-    const u32 ka1 = brev4(hi4);
-    // output twiddle w_n^-(k_a l), k_a = k_a1 + 16 k: a geometric progression in k with ratio w_n^-(16 l)
-    u64 f = tw_split16(tw_hi, tw_lo, ka1 * l);
-    const u64 ratio = tw_split16(tw_hi, tw_lo, 16 * l);
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) sh[s * 272 + tid] = s ? gl::mul_mont(x[s], tw[s]) : x[s];
-    __syncthreads();
-#pragma unroll
-    for (u32 a0 = 0; a0 < 16; a0++) x[a0] = sh[hi4 * 272 + a0 * 16 + j];
-    dft16<true>(x);
-#pragma unroll
-    for (u32 k = 0; k < 16; k++) {
-        dst[base + ((size_t)(ka1 + 16 * k) << LL) + j] = gl::mul_mont(x[brev4(k)], f);
-        if (k < 15) f = gl::mul_mont_lazy(f, ratio);
-    }
-}
-
-// P2 (LB = 4): grid = ncols * 16 * 16; tile 16 k_a x 16 b x 16 c; src [k_a][b][c] -> dst [k_b][k_a][c]
-__global__ __launch_bounds__(THREADS) void k_gl_intt16_p2(const u64* __restrict__ src, u64* __restrict__ dst, u32 L,
-                                                          const u64* __restrict__ tw4096) {
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ia = threadIdx.x >> 4, jc = threadIdx.x & 15;
-    const u32 ka = 16 * ga + ia, c = 16 * gc + jc;
-    u64 x[16];
-#pragma unroll
-    for (u32 b = 0; b < 16; b++) x[b] = src[cbase + ((size_t)ka << 12) + ((size_t)b << 8) + c];
-    u64 tw[16];
-    load_tw16(tw, tw4096, c);  // w_4096^-(c k_b)
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++)
-        dst[cbase + ((size_t)brev4(s) << 16) + ((size_t)ka << 8) + c] = s ? gl::mul_mont(x[s], tw[s]) : x[s];
-}
-
-// P2 for LB = K in 1..3 (L = 16 + K): the same pass with a radix-2^K DFT over b; src [k_a][b][c] -> dst [k_b][k_a][c]
-template <int K>
-__global__ __launch_bounds__(THREADS) void k_gl_intt16_p2s(const u64* __restrict__ src, u64* __restrict__ dst, const u64* __restrict__ tw4096) {
-    constexpr u32 L = 16 + K, R = 1u << K;
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ka = 16 * ga + (threadIdx.x >> 4), c = 16 * gc + (threadIdx.x & 15);
-    u64 x[16];
-#pragma unroll
-    for (u32 b = 0; b < R; b++) x[b] = src[cbase + ((size_t)ka << (8 + K)) + ((size_t)b << 8) + c];
-    u64 tw[R];
-#pragma unroll
-    for (u32 s = 1; s < R; s++) tw[s] = tw4096[(brevk(s, K) * c) << (4 - K)];  // w_{2^(8+K)}^-(c k_b)
-    dft_small<true, K>(x);
-#pragma unroll
-    for (u32 s = 0; s < R; s++)
-        dst[cbase + ((size_t)brevk(s, K) << 16) + ((size_t)ka << 8) + c] = s ? gl::mul_mont(x[s], tw[s]) : x[s];
-}
-
-// P2 for LB = 5, 6 (2^21 and 2^22 rows, round 6): the middle pass as a radix-32 / radix-64 DFT over b in registers - every root of
-// unity of order <= 64 is a power of two, so the whole DFT is shifts; one or two DIF layers bring it down to 16-point blocks.
-// src [k_a][b][c] -> dst [k_b][k_a][c]; tw = w_{2^14}^-j (Montgomery form), j < 2^14.  X[k_b] ends up in slot brev_LB(k_b).
-template <int LB>
-__global__ __launch_bounds__(THREADS) void k_gl_intt16_p2w(const u64* __restrict__ src, u64* __restrict__ dst, const u64* __restrict__ tw16k) {
-    constexpr u32 L = 16 + LB, R = 1u << LB;
-    const size_t col = blockIdx.x >> 8;
-    const u32 ga = (blockIdx.x >> 4) & 15, gc = blockIdx.x & 15;
-    const size_t cbase = col << L;
-    const u32 ka = 16 * ga + (threadIdx.x >> 4), c = 16 * gc + (threadIdx.x & 15);
-    u64 x[R];
-#pragma unroll
-    for (u32 b = 0; b < R; b++) x[b] = src[cbase + ((size_t)ka << (8 + LB)) + ((size_t)b << 8) + c];
-    if constexpr (LB == 6) {
-        layer64<true, 32, 0>(x);
-        layer64<true, 16, 0>(x);
-        layer64<true, 16, 32>(x);
-    } else {
-        layer64<true, 16, 0>(x);
-    }
-#pragma unroll
-    for (u32 o = 0; o < R; o += 16) dft16<true>(*reinterpret_cast<u64(*)[16]>(&x[o]));
-#pragma unroll
-    for (u32 s = 0; s < R; s++) {
-        const u32 kb = brevk(s, LB);
-        dst[cbase + ((size_t)kb << 16) + ((size_t)ka << 8) + c] = s ? gl::mul_mont(x[s], tw16k[(kb * c) << (6 - LB)]) : x[s];   // w_{2^(8+LB)}^-(c k_b)
-    }
-}
-
-// P3: grid = ncols * 2^LB * 16; tile 16 k_a x 256 c (c = 16 c1 + c0); src [k_b][k_a][c];
-// dst natural k = k_a + 256 k_b + 2^(8+LB) k_c, scaled by n^-1
-__global__ __launch_bounds__(THREADS) void k_gl_intt16_p3(const u64* __restrict__ src, u64* __restrict__ dst, Inv16Geom g,
-                                                          const u64* __restrict__ tw4096, u64 n_inv) {
-    __shared__ u64 sh[16 * 272];
-    const u32 nb = 1u << g.LB;
-    const size_t col = blockIdx.x / (nb * 16);
-    const u32 rem = blockIdx.x % (nb * 16);
-    const u32 kb = rem >> 4, ga = rem & 15;
-    const size_t cbase = col << g.L;
-    const size_t sbase = cbase + ((size_t)kb << 16) + ((size_t)(16 * ga) << 8);
-    const u32 tid = threadIdx.x, hi4 = tid >> 4, lo4 = tid & 15;
-    u64 x[16];
-    // stage 1 thread = (ia = hi4, c0 = lo4): digit c1
-#pragma unroll
-    for (u32 c1 = 0; c1 < 16; c1++) x[c1] = src[sbase + hi4 * 256 + c1 * 16 + lo4];
-    u64 tw[16];
-    load_tw16(tw, tw4096, lo4 * 16);  // w_256^-(k_c1 c0)
-    dft16<true>(x);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) sh[s * 272 + lo4 * 17 + hi4] = s ? gl::mul_mont(x[s], tw[s]) : x[s];  // [k_c1 slot][c0][ia], rows padded to 17
-    __syncthreads();
-    // stage 2 thread = (k_c1 slot = hi4, ia = lo4): digit c0
-#pragma unroll
-    for (u32 c0 = 0; c0 < 16; c0++) x[c0] = sh[hi4 * 272 + c0 * 17 + lo4];
-    dft16<true>(x);
-    const u32 kc1 = brev4(hi4);
-#pragma unroll
-    for (u32 s = 0; s < 16; s++) {
-        const u32 kc = kc1 + 16 * brev4(s);
-        dst[cbase + ((size_t)kc << (8 + g.LB)) + ((size_t)kb << 8) + 16 * ga + lo4] = gl::mul_mont(x[s], n_inv);
-    }
-}
-
-// ------------------------------------------------------------------ launchers (called from kernels_ntt.hip's dispatchers)
+// ------------------------------------------------------------------ launchers (called from ntt_passes.hpp's lde_columns<GlF>)
 // Every kernel of this file takes the MONTGOMERY-form copies of the tables (GlNttTables::*_m, GlCosetTables::*_m): all of their
 // general multiplications have a table value as one factor (gl::mul_mont).
 
-bool gl_intt_columns_r16(const u64* src, u64* coeffs, u64* scratch, size_t ncols, const GlNttTables& t, hipStream_t stream) {
-    const u32 L = t.log_n;
-    if (L < 16 || L > 22) return false;
-    Inv16Geom g{L, L - 16};
-    const u32 LL = g.LB + 8;
-    u64* p1_dst = g.LB ? coeffs : scratch;
-    hipLaunchKernelGGL(k_gl_intt16_p1, dim3((u32)(ncols << (LL - 4))), dim3(THREADS), 0, stream, src, p1_dst, g, t.tw4096_inv_m,
-                       t.tw_hi_inv_m, t.tw_lo_inv_m);
-    const dim3 g2((u32)(ncols << 8));
-    if (g.LB == 6) hipLaunchKernelGGL(k_gl_intt16_p2w<6>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw16k_inv_m);
-    else if (g.LB == 5) hipLaunchKernelGGL(k_gl_intt16_p2w<5>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw16k_inv_m);
-    else if (g.LB == 4) hipLaunchKernelGGL(k_gl_intt16_p2, g2, dim3(THREADS), 0, stream, coeffs, scratch, L, t.tw4096_inv_m);
-    else if (g.LB == 3) hipLaunchKernelGGL(k_gl_intt16_p2s<3>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv_m);
-    else if (g.LB == 2) hipLaunchKernelGGL(k_gl_intt16_p2s<2>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv_m);
-    else if (g.LB == 1) hipLaunchKernelGGL(k_gl_intt16_p2s<1>, g2, dim3(THREADS), 0, stream, coeffs, scratch, t.tw4096_inv_m);
-    hipLaunchKernelGGL(k_gl_intt16_p3, dim3((u32)(ncols << (g.LB + 4))), dim3(THREADS), 0, stream, scratch, coeffs, g,
-                       t.tw4096_inv_m, t.n_inv_m);
-    return true;
-}
-
-bool gl_lde_pa_r16(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables& t, const GlCosetTables& ct, hipStream_t stream) {
+void lde_pa_r16(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables& t, const GlCosetTables& ct, hipStream_t stream) {
     const u32 L = t.log_n;
     if (L == 20) {
         hipLaunchKernelGGL(k_gl_lde_pa16x2, dim3((u32)(ncols << 8)), dim3(THREADS), 0, stream, coeffs, lde, L, ct.rate_bits,
                            t.tw4096_fwd_m, t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
-        return true;
+        return;
     }
     if (L == 21 || L == 22) {
         if (L == 21)
@@ -655,7 +479,7 @@ bool gl_lde_pa_r16(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables&
         else
             hipLaunchKernelGGL(k_gl_lde_pa32<2>, dim3((u32)(ncols << 8)), dim3(512), 0, stream, coeffs, lde, ct.rate_bits, t.tw4096_fwd_m,
                                t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
-        return true;
+        return;
     }
 #define GB_PAS(KK)                                                                                                        \
     hipLaunchKernelGGL(k_gl_lde_pa16xs<KK>, dim3((u32)(ncols << (4 + KK))), dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, \
@@ -665,22 +489,21 @@ bool gl_lde_pa_r16(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables&
         if (L == 13) hipLaunchKernelGGL(k_gl_lde_pa_small<1>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
         if (L == 14) hipLaunchKernelGGL(k_gl_lde_pa_small<2>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
         if (L == 15) hipLaunchKernelGGL(k_gl_lde_pa_small<3>, grid, dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits, t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
-        return true;
+        return;
     }
-    if (L == 17) { GB_PAS(1); return true; }
-    if (L == 18) { GB_PAS(2); return true; }
-    if (L == 19) { GB_PAS(3); return true; }
+    if (L == 17) { GB_PAS(1); return; }
+    if (L == 18) { GB_PAS(2); return; }
+    if (L == 19) { GB_PAS(3); return; }
 #undef GB_PAS
-    if (L == 16) {
+    if (L == 16)
         hipLaunchKernelGGL(k_gl_lde_pa16x1, dim3((u32)(ncols << 4)), dim3(THREADS), 0, stream, coeffs, lde, ct.rate_bits,
                            t.tw_hi_fwd_m, t.tw_lo_fwd_m, ct.pow_lo_m, ct.pow_hi_m);
-        return true;
-    }
-    return false;
 }
 
-void gl_lde_pb_r16(u64* lde, size_t ntiles, const GlNttTables& t, hipStream_t stream) {
+void lde_pb_r16(u64* lde, size_t ntiles, const GlNttTables& t, hipStream_t stream) {
     hipLaunchKernelGGL(k_gl_lde_pb16, dim3((u32)ntiles), dim3(THREADS), 0, stream, lde, t.tw4096_fwd_m);
 }
+
+GB_INSTANTIATE_NTT(GlF)
 
 }  // namespace gbk

@@ -12,7 +12,7 @@
 //   k_fri_*         fri_committed_trees fold + leaf hashing          fri/prover.rs:83-133
 //   k_pow_grind     fri_proof_of_work (minimum nonce)                fri/prover.rs:136-188
 //   k_query_gather  fri_prover_query_rounds: every opened row and path, one launch per twelve trees   fri/prover.rs:190-255
-// All data is column-major; LDE matrices are in leaf order (see kernels_ntt.hip).  Element data is in the
+// All data is column-major; LDE matrices are in leaf order (see ntt_passes.hpp).  Element data is in the
 // field's device form (F::T); digests and everything gathered for the proof bytes are canonical.
 #include "kernels.hpp"
 #include "poseidon2_bb.hpp"

@@ -1,6 +1,6 @@
 // Host orchestration of prove() on one context (included at the end of api.hip).
 // Follows internal_prove_with_partition_witness (plonk/prover.rs:228-447) step by step; every
-// heavy step is a kernel from kernels_prover.hip / kernels_ntt*.hip / kernels_bb.hip / kernels_merkle.hip, the
+// heavy step is a kernel from kernels_prover.hip / ntt_passes.hpp / kernels_*16.hip / kernels_bb.hip / kernels_merkle.hip, the
 // Fiat-Shamir transcript runs on the host (poseidon_gl_host.hpp / poseidon2_bb_host.hpp).
 // One template over the field traits (field_traits.hpp) serves Goldilocks and BabyBear: F::T is the device
 // form of an element (canonical u64 / Montgomery u32); the transcript and the proof bytes use canonical words
@@ -267,7 +267,7 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
     if (!copy_columns(sig_src, cfg->num_routed_wires, n * sizeof(T), c->sigma_vals,
                       (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream))
         return cleanup(fail(ctx, GB_ERR_HIP, "copy of sigma values failed"));
-    if (flags & GB_INPUT_P3_REPR) HF::p3_to_device_form(c->sigma_vals, sig_count, ctx->stream);   // the field types' in-memory words
+    if (flags & GB_INPUT_P3_REPR) gbk::reduce_words<F>(c->sigma_vals, sig_count, ctx->stream);   // the field types' in-memory words
     else HF::to_device_form(c->sigma_vals, c->sigma_vals, sig_count, ctx->stream);
     std::vector<T> k_canon(cfg->num_routed_wires);
     if (flags & GB_INPUT_DEVICE) {
@@ -470,7 +470,7 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
     if ((s = cosets_for<F>(ctx, lg, qb, F::generator(), true, &inv_cos))) return s;
     if ((s = ensure(ctx, ctx->scratch, nq * n * sizeof(T)))) return s;
-    { Scope sq(ctx, "quotient IFFT"); HF::intt(qv, qc, (T*)ctx->scratch.p, nq, *tabs, st); }   // (a scope of its own: not a commitment's transform)
+    { Scope sq(ctx, "quotient IFFT"); gbk::intt_columns<F>(qv, qc, (T*)ctx->scratch.p, nq, *tabs, st); }   // (a scope of its own: not a commitment's transform)
     gbk::CosetPow<F> ip{inv_cos->pow_lo, inv_cos->pow_hi, (u32)(n < 4096 ? n : 4096), (u32)(n > 4096 ? n / 4096 : 1)};
     gbk::quotient_combine<F>(lg, qb, nch, qc, c->combine_mat, ip, chunks, st);
     *chunks_out = chunks;
@@ -550,7 +550,7 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
             if ((s = cosets_for<F>(ctx, cur_lg, r, shift, false, &cos))) return s;
             T* vals = tmp.get<T>(D * cur_N);
             if (!vals) return fail(ctx, GB_ERR_OOM, "FRI values");
-            { Scope sl(ctx, "FRI LDE"); HF::lde(cur_coeffs, vals, D, *tabs, *cos, st); }
+            { Scope sl(ctx, "FRI LDE"); gbk::lde_columns<F>(cur_coeffs, vals, D, *tabs, *cos, st); }
             layer_vals[li] = vals;
             layer_lgN[li] = cur_lg + r;
             // fri_committed_trees (fri/prover.rs:83-133)
@@ -722,7 +722,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             T* stage = tmp.get<T>(2 * per);
             if (!stage) return fail(ctx, GB_ERR_OOM, "salt staging");
             HIP_TRY(ctx, hipMemcpyAsync(stage, salt_w + per, 2 * per * sizeof(T), hipMemcpyHostToDevice, st));
-            if (flags & GB_INPUT_P3_REPR) HF::p3_to_canonical_dev(stage, 2 * per, st);   // the Zs / quotient commits take device salts: canonical
+            if (flags & GB_INPUT_P3_REPR) p3_to_canonical_dev<F>(stage, 2 * per, st);   // the Zs / quotient commits take device salts: canonical
             salt_z = stage;
             salt_q = stage + per;
         }
@@ -808,10 +808,10 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
                 if (!HF::intt_canonical(const_cast<T*>(col_src), coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st))
                     return fail(ctx, GB_ERR_INVALID, "internal: canonical-input transform not available for this size");
             } else {
-                HF::intt(col_src, coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st);
+                gbk::intt_columns<F>(col_src, coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st);
             }
         }
-        { Scope sf(ctx, "FFT + blinding"); HF::lde(coeffs_col, lde_col, 1, *tabs, *cos, st); }
+        { Scope sf(ctx, "FFT + blinding"); gbk::lde_columns<F>(coeffs_col, lde_col, 1, *tabs, *cos, st); }
         {
             Scope sm(ctx, "build Merkle tree");
             T* lv = (T*)wires->levels;
@@ -841,7 +841,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         if (!wit_copy) return fail(ctx, GB_ERR_OOM, "witness copy");
         if (!copy_columns(witness, nr, col_bytes, wit_copy, (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
             return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
-        if (p3) HF::p3_to_device_form(wit_copy, (size_t)nr * n, st);
+        if (p3) gbk::reduce_words<F>(wit_copy, (size_t)nr * n, st);
         else HF::to_device_form(wit_copy, wit_copy, (size_t)nr * n, st);
         wit_dev = wit_copy;
     }
@@ -1032,7 +1032,7 @@ static gb_status abi_zs_partial_products(Circuit<F>* c, ColSrc witness, uint32_t
         if (!copy) return fail(ctx, GB_ERR_OOM, "witness copy");
         if (!copy_columns(witness, nr, n * sizeof(T), copy, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
             return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
-        if (p3) HF::p3_to_device_form(copy, (size_t)nr * n, st);
+        if (p3) gbk::reduce_words<F>(copy, (size_t)nr * n, st);
         else HF::to_device_form(copy, copy, (size_t)nr * n, st);
         wit_dev = copy;
     }
@@ -1045,7 +1045,7 @@ static gb_status abi_zs_partial_products(Circuit<F>* c, ColSrc witness, uint32_t
     }
     T* zs_vals = nullptr;
     if (gb_status s = stage_zs_partial_products<F>(c, tmp, wit_dev, bd, gd, &zs_vals)) return s;
-    HF::from_device_form(zs_vals, nzs * n, st);
+    HF::from_device_form(zs_vals, zs_vals, nzs * n, st);
     HIP_TRY(ctx, hipMemcpyAsync(values_out, zs_vals, nzs * n * sizeof(T), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
@@ -1092,7 +1092,7 @@ static gb_status abi_quotient_polys(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     }
     T* chunks = nullptr;
     if (gb_status s = stage_quotient_polys<F>(c, tmp, wires, zs, ph, bd, gd, al, &chunks)) return s;
-    HF::from_device_form(chunks, nq * n, st);
+    HF::from_device_form(chunks, chunks, nq * n, st);
     HIP_TRY(ctx, hipMemcpyAsync(chunks_out, chunks, nq * n * sizeof(T), (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
