@@ -47,8 +47,8 @@ struct GlF {
     // a + b for a result that is only multiplied (by a canonical partner): canonical here
     static GB_HD T add_lazy(T a, T b) { return gl::add(a, b); }
     // Multiplication by a per-proof CONSTANT (a challenge, a table value) that the host stores in "constant form": for Goldilocks
-    // c R (Montgomery), so that x c costs 5 mads + 8 carry ops and comes out canonical for canonical x (gl::mul_mont) instead of
-    // 5 + 11 + 4; for BabyBear the device form is Montgomery already.
+    // c R (Montgomery), so that x c costs 4 mads + 3 + the 7-instruction fold (gl::mont_fold_flags) and comes out canonical for canonical x (gl::mul_mont) instead of
+    // gl::mul's 4 + 3 + 11 + 4; for BabyBear the device form is Montgomery already.
     static GB_HD T cform(T c) { return gl::to_mont_slow(c); }
     // Product chains np <- np * f that are only multiplied again: Montgomery steps (8-op fold instead of 11); each step divides
     // by R, so a chain of `len` factors starts from R^len instead of 1 and ends on the plain product (some residue).

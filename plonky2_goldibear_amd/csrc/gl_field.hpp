@@ -64,6 +64,27 @@ __device__ __forceinline__ u64 mad_one(u32 x, u64 acc) {                        
     asm("v_mad_u64_u32 %0, %1, %2, 1, %0" : "+v"(acc), "=s"(unused) : "v"(x));
     return acc;
 }
+__device__ __forceinline__ u32 sub_flag(u32 a, u32 b, u64& borrow) {            // a - b = result - 2^32 [borrow]
+    u32 d;
+    asm("v_sub_co_u32 %0, %1, %2, %3" : "=v"(d), "=s"(borrow) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ u32 subb_flag(u32 a, u32 b, u64 in, u64& borrow) {   // a - b - [in] = result - 2^32 [borrow]
+    u32 d;
+    asm("v_subb_co_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(borrow) : "v"(a), "v"(b), "s"(in));
+    return d;
+}
+__device__ __forceinline__ u32 addc_flag(u32 x, u64 in, u64& carry) {           // x + [in] = result + 2^32 [carry]
+    u32 d;
+    asm("v_addc_co_u32 %0, %1, %2, 0, %3" : "=v"(d), "=s"(carry) : "v"(x), "s"(in));
+    return d;
+}
+__device__ __forceinline__ u32 subb_zero(u32 x, u64 in) {                       // x - [in]
+    u32 d;
+    u64 unused;
+    asm("v_subbrev_co_u32 %0, %1, 0, %2, %3" : "=v"(d), "=s"(unused) : "v"(x), "s"(in));
+    return d;
+}
 #endif
 __host__ inline u64 add(u64 a, u64 b) {
     u64 s, u;
@@ -84,6 +105,18 @@ __host__ inline u64 mad_carry(u32 a, u32 b, u64 acc, u64& carry) {
 }
 __host__ inline u32 addc_carry(u32 x, u64 carry) { return x + (u32)(carry & 1); }
 __host__ inline u64 mad_one(u32 x, u64 acc) { return acc + x; }
+__host__ inline u32 sub_flag(u32 a, u32 b, u64& borrow) { borrow = a < b; return a - b; }
+__host__ inline u32 subb_flag(u32 a, u32 b, u64 in, u64& borrow) {
+    const u64 d = (u64)a - b - (in & 1);
+    borrow = d >> 63;
+    return (u32)d;
+}
+__host__ inline u32 addc_flag(u32 x, u64 in, u64& carry) {
+    const u64 d = (u64)x + (in & 1);
+    carry = d >> 32;
+    return (u32)d;
+}
+__host__ inline u32 subb_zero(u32 x, u64 in) { return x - (u32)(in & 1); }
 __host__ __device__ __forceinline__ u64 neg(u64 a) { return a ? P - a : 0; }
 
 // (lo + 2^64 hi) mod p, any 128-bit input, canonical output.
@@ -172,16 +205,35 @@ __host__ __device__ __forceinline__ u64 mont_fold(u32 x0, u32 x1, u32 x2, u32 x3
     const u32 f1 = r1 - k;
     return (u64)f0 | ((u64)f1 << 32);
 }
+// mont_fold with its last step taken on the borrow FLAG itself (round 7): r - c EPS = r + c - 2^32 c is f0 = r0 + [c] as an
+// add-with-carry whose carry-IN is the flag (carry out co), and f1 = r1 - [c & ~co] as a subtract-with-borrow - the flag never
+// becomes a vector value (mont_fold's v_cndmask), and the one mask operation runs on the scalar unit: 7 vector instructions for
+// mont_fold's 8.  The SAME u64 word as mont_fold for every input (tests/test_mul_mont_forms.py).  The flags are lane masks in scalar
+// pairs, which only inline asm can name, so constants do not fold through it: from_mont-style callers (x2 = x3 = 0) keep mont_fold.
+__host__ __device__ __forceinline__ u64 mont_fold_flags(u32 x0, u32 x1, u32 x2, u32 x3) {
+    u32 e, bw, k0;
+    u64 c0, c, co;
+    const u32 a1 = __builtin_addc(x1, x0, 0u, &e);
+    const u32 b0 = __builtin_subc(x0, a1, e, &bw);
+    const u32 b1 = __builtin_subc(a1, 0u, bw, &k0);
+    const u32 r0 = sub_flag(x2, b0, c0);
+    const u32 r1 = subb_flag(x3, b1, c0, c);         // c: hi < b
+    const u32 f0 = addc_flag(r0, c, co);
+    const u32 f1 = subb_zero(r1, c & ~co);
+    return (u64)f0 | ((u64)f1 << 32);
+}
 // a * t for a table value stored in MONTGOMERY form (t R mod p, R = 2^64): a (t R) / R = a t (and Montgomery times Montgomery
 // stays Montgomery).  Any u64 operands give some residue (mul_mont_lazy).  CANONICAL operands give the CANONICAL product with no
 // further step (mul_mont): a, t R <= p - 1 makes the product's high word xh <= (p - 1)^2 / 2^64 < p, and mont_fold returns
 // xh - b without a borrow (<= xh < p) or xh - b + p with one (in [p - b, p - 1], b <= p - 1).  So a multiplication by a table
-// value costs 5 mads + 8 carry ops where gl::mul takes 5 + 11 + 4 (fold, then canonicalise).
+// value costs 4 mads + 3 + the fold (7 vector instructions as mont_fold_flags, 8 as mont_fold) where gl::mul takes
+// 4 + 3 + 11 + 4 (fold128, then canonicalise).
 template <bool FIVE = false>
 __host__ __device__ __forceinline__ u64 mul_mont_lazy(u64 a, u64 t_mont) {
     u32 r0, r1, hl, hh;
     mul_limbs<FIVE>(a, t_mont, r0, r1, hl, hh);
-    return mont_fold(r0, r1, hl, hh);
+    if constexpr (FIVE) return mont_fold(r0, r1, hl, hh);   // the strided LDE pass: the flag form's gain there (1 %) is inside its run-to-run spread
+    else return mont_fold_flags(r0, r1, hl, hh);
 }
 // mul_mont is mul_mont_lazy under the name that states its contract: CANONICAL operands in, canonical product out.  The NTT kernels
 // rely on it for what they store: their data operands are canonical (loaded from memory, or outputs of add / sub / mul_pow2 /

@@ -26,7 +26,7 @@ struct GlNttTables {
     const u64* tw_hi_inv;
     u64 n_inv;               // n^-1 mod p
     // the same tables times R = 2^64 mod p (Montgomery form) for the register-radix kernels of kernels_ntt16.hip, whose
-    // multiplications by table values then end in the 8-instruction Montgomery fold (gl::mul_mont) instead of fold128's 11;
+    // multiplications by table values then end in the 7-instruction Montgomery fold (gl::mul_mont: mont_fold_flags) instead of fold128's 11;
     // tw4096_fwd_m is [8192]: the powers, then the same powers in k_gl_lde_pb16's stage-1 order [slot][tid]
     const u64 *tw4096_fwd_m, *tw4096_inv_m, *tw_lo_fwd_m, *tw_hi_fwd_m, *tw_lo_inv_m, *tw_hi_inv_m;
     u64 n_inv_m;

@@ -51,7 +51,7 @@ constexpr u64 INIT[11 * 11] = {GL_POSEIDON_FAST_PARTIAL_ROUND_INITIAL_MATRIX_LIS
 }  // namespace raw
 
 // The state lives in MONTGOMERY form (x R, R = 2^64 mod p) inside the permutation: a state-by-state product (the s-box) is then
-// reduced by the Montgomery fold (8 carry ops, mont_fold) instead of the plain one (11, gl::fold128), while everything linear -
+// reduced by the Montgomery fold (7 vector instructions, gl::mont_fold_flags) instead of the plain one (11, gl::fold128), while everything linear -
 // small-integer MDS sums, products with the PLAIN constants w_hat / v / M_init (x R times c is (x c) R under the plain fold) -
 // is unchanged.  Only the constants that are ADDED to the state are stored times R.
 template <int N>
@@ -171,13 +171,10 @@ __device__ __forceinline__ u64 mul_lazy(u64 a, u64 b) {
     gl::mul_limbs(a, b, r0, r1, hl, hh);
     return gl::fold128(r0, r1, hl, hh);
 }
-using gl::mont_fold;   // the Montgomery reduction (gl_field.hpp): 8 carry ops against fold128's 11
-// a b / R for two Montgomery-form residues: any u64 in, any u64 out
-__device__ __forceinline__ u64 mul_mont(u64 a, u64 b) {
-    u32 r0, r1, hl, hh;
-    gl::mul_limbs(a, b, r0, r1, hl, hh);
-    return mont_fold(r0, r1, hl, hh);
-}
+using gl::mont_fold;   // the Montgomery reduction in its plain form (8 carry ops): for values that were not just multiplied (from_mont)
+// a b / R for two Montgomery-form residues: any u64 in, any u64 out (gl::mul_mont_lazy: four multiply-adds and the fold whose last
+// step works on the borrow flag, 14 vector instructions)
+__device__ __forceinline__ u64 mul_mont(u64 a, u64 b) { return gl::mul_mont_lazy(a, b); }
 // x -> x R = x (2^32 - 1) = (x0 << 32) - (x0 + x1) for x = x0 + 2^32 x1 (2^64 = 2^32 - 1 mod p), any u64 in, any u64 out
 __device__ __forceinline__ u64 to_mont(u64 x) {
     const u32 x0 = (u32)x, x1 = (u32)(x >> 32);

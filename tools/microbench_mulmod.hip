@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include "../plonky2_goldibear_amd/csrc/gl_field.hpp"   // the Montgomery forms M9-M12 use its limbs, its fold and its flag helpers
 typedef unsigned long long u64;
 typedef unsigned int u32;
 static constexpr u64 P = 0xFFFFFFFF00000001ULL, EPS = 0xFFFFFFFFULL;
@@ -163,8 +164,51 @@ __device__ __forceinline__ u64 mul8(u64 a, u64 b) {
     return (u64)(u32)f | ((u64)f1 << 32);
 }
 
+// ---- Montgomery products a b / 2^64 (round 4 on; the product's form since then is M9).  All four return the SAME u64 word.
+// M9: mul_limbs + mont_fold, the compiler's 15 vector instructions (two v_mov for the zero-extended addends, one v_cndmask).
+__device__ __forceinline__ u64 mul9(u64 a, u64 b) {
+    u32 r0, r1, hl, hh;
+    gl::mul_limbs<false>(a, b, r0, r1, hl, hh);
+    return gl::mont_fold(r0, r1, hl, hh);
+}
+// M10 (round 7, step 1, NOT adopted): the fold's subtrahend rides in the last multiply-add's addend - Y = (m2.hi, 0) - b written
+// straight into an aligned pair (borrow By), W = a1 b1 + Y with its carry C in a scalar pair, the top limb += K (carry K2); the
+// borrow of mont_fold's subtraction is By & ~(C | K2), two scalar instructions.  One v_mov fewer.
+template <bool FLAG_TAIL>
+__device__ __forceinline__ u64 mul10(u64 a, u64 t) {
+    const u32 a0 = (u32)a, a1 = (u32)(a >> 32), t0 = (u32)t, t1 = (u32)(t >> 32);
+    const u64 p00 = (u64)a0 * t0;
+    const u64 p01 = (u64)a0 * t1 + (p00 >> 32);
+    u64 K, y, By, C, K2, co;
+    const u64 m2 = gl::mad_carry(a1, t0, p01, K);
+    u32 e, bw, k0, y1;
+    const u32 s1 = __builtin_addc((u32)m2, (u32)p00, 0u, &e);
+    const u32 b0 = __builtin_subc((u32)p00, s1, e, &bw);
+    const u32 b1 = __builtin_subc(s1, 0u, bw, &k0);
+    const u32 y0 = gl::sub_flag((u32)(m2 >> 32), b0, y);
+    asm("v_subb_co_u32 %0, %1, 0, %2, %3" : "=v"(y1), "=s"(By) : "v"(b1), "s"(y));
+    const u64 w = gl::mad_carry(a1, t1, (u64)y0 | ((u64)y1 << 32), C);
+    const u32 r0 = (u32)w, r1 = gl::addc_flag((u32)(w >> 32), K, K2);
+    const u64 c = By & ~(C | K2);
+    if (FLAG_TAIL) {
+        const u32 f0 = gl::addc_flag(r0, c, co);
+        return (u64)f0 | ((u64)gl::subb_zero(r1, c & ~co) << 32);
+    }
+    u32 m, k;
+    asm("v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(c));
+    const u32 f0 = __builtin_subc(r0, m, 0u, &k);
+    return (u64)f0 | ((u64)(r1 - k) << 32);
+}
+// M11 (round 7, step 2, the product's form now): mul_limbs + mont_fold_flags - the last "- EPS when hi < b" as an add-with-carry
+// and a subtract-with-borrow on the flag itself, no v_cndmask.  M12: both steps.
+__device__ __forceinline__ u64 mul11(u64 a, u64 b) { return gl::mul_mont_lazy<false>(a, b); }
+
 template <int V>
 __device__ __forceinline__ u64 mulv(u64 a, u64 b) {
+    if (V == 9) return mul9(a, b);
+    if (V == 10) return mul10<false>(a, b);
+    if (V == 11) return mul11(a, b);
+    if (V == 12) return mul10<true>(a, b);
     if (V == 6) return mul6<true>(a, b);
     if (V == 7) return mul6<false>(a, b);
     if (V == 8) return mul8(a, b);
@@ -193,13 +237,43 @@ __global__ __launch_bounds__(256) void kbench(u64* out, u64 seed) {
     out[blockIdx.x * blockDim.x + threadIdx.x] = r;
 }
 
+// The regime the product runs in inside the hash kernels: FOUR waves per SIMD and a full register file, ~120 of 128 VGPRs held per lane (the lone-wave loop above
+// hides nothing behind other waves and has no register pressure).  A block of dummy registers is kept live across the loop and
+// the kernel is pinned to four waves per SIMD, so a flag in a scalar pair competes for issue with three other waves' work.
+#define HELD 48
+template <int V>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void kbench_held(u64* out, u64 seed) {
+    u64 x[8];
+    u32 d[HELD];
+    for (int i = 0; i < 8; i++) x[i] = canon(seed * (threadIdx.x + 1) * (2 * i + 3));
+    for (int i = 0; i < HELD; i++) d[i] = (u32)seed * (threadIdx.x + i);
+    u64 m = canon(seed ^ 0x123456789abcdefULL);
+    for (int it = 0; it < ITER; it++) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) x[i] = mulv<V>(x[i], m);
+#pragma unroll
+        for (int i = 0; i < 8; i++) x[i] = mulv<V>(x[i], x[(i + 1) & 7]);
+#pragma unroll
+        for (int i = 0; i < HELD; i++) asm volatile("" : "+v"(d[i]));   // every dummy stays in a register of its own
+    }
+    u64 r = 0;
+    for (int i = 0; i < 8; i++) r ^= x[i];
+    for (int i = 0; i < HELD; i++) r += d[i];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+
 template <int V>
 __global__ void kcheck(const u64* a, const u64* b, u64* o, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) o[i] = canon(canon(mulv<V>(a[i], b[i])));
+    if (i < n) o[i] = V >= 9 ? mulv<V>(a[i], b[i]) : canon(canon(mulv<V>(a[i], b[i])));
 }
 
 static u64 host_mul(u64 a, u64 b) { return (u64)(((unsigned __int128)a * b) % P); }
+static u64 host_mont_word(u64 a, u64 b) {   // the word mont_fold(mul_limbs(a, b)) returns (host overloads of gl_field.hpp)
+    u32 r0, r1, hl, hh;
+    gl::mul_limbs<false>(a, b, r0, r1, hl, hh);
+    return gl::mont_fold(r0, r1, hl, hh);
+}
 
 template <int V>
 void run(const char* name) {
@@ -219,7 +293,7 @@ void run(const char* name) {
     std::vector<u64> o(n);
     hipMemcpy(o.data(), dout, n * 8, hipMemcpyDeviceToHost);
     int bad = 0;
-    for (int i = 0; i < n; i++) if (o[i] != host_mul(a[i], b[i])) { if (bad < 3) printf("  MISMATCH %s a=%llx b=%llx got %llx want %llx\n", name, a[i], b[i], o[i], host_mul(a[i], b[i])); bad++; }
+    for (int i = 0; i < n; i++) if (V >= 9 ? (o[i] != host_mont_word(a[i], b[i]) || host_mul(o[i], EPS) != host_mul(a[i], b[i])) : o[i] != host_mul(a[i], b[i])) { if (bad < 3) printf("  MISMATCH %s a=%llx b=%llx got %llx want %llx\n", name, a[i], b[i], o[i], host_mul(a[i], b[i])); bad++; }
     // bench
     int blocks = 256 * 8;
     u64* d; hipMalloc(&d, blocks * 256 * 8);
@@ -232,7 +306,17 @@ void run(const char* name) {
     float ms; hipEventElapsedTime(&ms, e0, e1);
     double muls = (double)blocks * 256 * ITER * 16;
     double wave_muls_per_simd = muls / 64 / 1024;
-    printf("%-10s bad=%d  %8.3f ms  %7.2f Gmul/s  %6.1f cycles/wave-mul/SIMD @2.4GHz\n", name, bad, ms, muls / ms / 1e6, ms * 1e-3 * 2.4e9 / wave_muls_per_simd);
+    printf("%-10s bad=%d  %8.3f ms  %7.2f Gmul/s  %6.1f cycles/wave-mul/SIMD @2.4GHz", name, bad, ms, muls / ms / 1e6, ms * 1e-3 * 2.4e9 / wave_muls_per_simd);
+    if (V >= 9) {   // four waves per SIMD, ~120 of its 128 VGPRs held
+        hipLaunchKernelGGL(kbench_held<V>, dim3(blocks), dim3(256), 0, 0, d, 12345ull);
+        hipDeviceSynchronize();
+        hipEventRecord(e0);
+        hipLaunchKernelGGL(kbench_held<V>, dim3(blocks), dim3(256), 0, 0, d, 12345ull);
+        hipEventRecord(e1); hipEventSynchronize(e1);
+        hipEventElapsedTime(&ms, e0, e1);
+        printf("  | 4 waves/SIMD, ~120 VGPRs held: %8.3f ms  %6.1f cycles", ms, ms * 1e-3 * 2.4e9 / wave_muls_per_simd);
+    }
+    printf("\n");
     hipFree(d); hipFree(da); hipFree(db); hipFree(dout);
 }
 
@@ -246,5 +330,9 @@ int main() {
     run<6>("M6 madfold");
     run<7>("M7 nonops");
     run<8>("M8 madfold2");
+    run<9>("M9 mont15");
+    run<10>("M10 addend");
+    run<11>("M11 flags");
+    run<12>("M12 both");
     return 0;
 }
