@@ -403,6 +403,60 @@ gb_status gb_prove_openings(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial
 gb_status gb_pow_grind(gb_ctx* ctx, uint32_t field, const void* sponge_state, uint32_t witness_pos, uint32_t min_leading_zeros,
                        uint64_t* nonce);
 
+/* ---- polynomials and Merkle trees on their own ------------------------------------------------------------------------------
+ * What PolynomialBatch and prove() are made of, for a host that uses the reference's `field` crate or its Merkle tree outside
+ * prove(): PolynomialCoeffs::fft / coset_fft, PolynomialValues::ifft / coset_ifft / lde / lde_onto_coset
+ * (field/src/polynomial/mod.rs) and MerkleTree::new (hash/merkle_tree.rs) - the shapes of benches/ffts.rs and benches/merkle.rs.
+ *
+ * Transforms.  `in` and `out` are column-major blocks [ncols][len] of canonical words in NATURAL order.  ext = 0: an element is
+ * one base word; ext = 1: an element is D consecutive base words (D = 2 Goldilocks, 4 BabyBear) - the layout of
+ * PolynomialCoeffs<F::Extension>, which fri/oracle.rs:226-231 transforms; any other value is GB_ERR_INVALID.  `shift` is NULL (no
+ * coset: the same as a shift of 1) or a HOST pointer to one canonical base-field element (8 / 4 bytes); 0 or a value >= p is
+ * GB_ERR_INVALID.  The tables of 1 and of F::generator() stay with the context; those of any other shift are built for the call
+ * (which then waits for the stream once while it uploads them).  flags: GB_INPUT_DEVICE - `in` AND `out` are device pointers, the
+ * work is ordered on the context's stream as gb_commit_* with GB_INPUT_DEVICE, and both blocks must stay valid until
+ * gb_ctx_synchronize; GB_INPUT_P3_REPR - the host input words are the reference's field types as they lie in memory.  The output
+ * is canonical either way.  With host pointers the call returns when `out` is filled; pageable memory is fine.
+ * log_n >= 0; log_n + rate_bits above the field's two-adicity (32 / 27) is GB_ERR_INVALID (fft.rs:174-180); ncols == 0 is GB_OK
+ * and touches nothing; out == in is allowed when both have the same length (the reference consumes `self`); a device that is too
+ * small is GB_ERR_OOM.  Results are bit-identical to the reference's: its zero-tail shortcut (fft.rs:189-195) is an optimisation,
+ * not a different result. */
+
+/* PolynomialCoeffs::lde(rate_bits) then fft_with_options(Some(rate_bits)) (polynomial/mod.rs:201-203, 264-275), or with a shift
+ * coset_fft_with_options(shift, Some(rate_bits)) (:277-295).  coeffs [ncols][n], values [ncols][n << rate_bits]:
+ * values[i] = P(shift * w_N^i). */
+gb_status gb_fft(gb_ctx* ctx, uint32_t field, const void* coeffs, void* values, size_t ncols, uint32_t log_n, uint32_t rate_bits,
+                 uint32_t ext, const void* shift, uint32_t flags);
+/* PolynomialValues::ifft (:57-59) / coset_ifft(shift) (:62-72).  values, coeffs [ncols][n]. */
+gb_status gb_ifft(gb_ctx* ctx, uint32_t field, const void* values, void* coeffs, size_t ncols, uint32_t log_n, uint32_t ext,
+                  const void* shift, uint32_t flags);
+/* PolynomialValues::lde(rate_bits) (:78-81; shift NULL) / lde_onto_coset (:84-88; shift = F::generator(), any shift accepted):
+ * values on H_n -> values on shift * H_N, N = n << rate_bits.  The coefficients in between never leave the device. */
+gb_status gb_lde(gb_ctx* ctx, uint32_t field, const void* values, void* out, size_t ncols, uint32_t log_n, uint32_t rate_bits,
+                 uint32_t ext, const void* shift, uint32_t flags);
+
+/* MerkleTree::new(leaves, cap_height) (hash/merkle_tree.rs:152-181).  The tree is a batch without polynomials: it keeps its leaves
+ * and its level-major digests on the device as a commitment does, its blocks go back through the context's pool when it is
+ * freed, and a gb_merkle_tree handle is a gb_batch handle - the functions below also read the tree of a commitment, and
+ * gb_batch_cap / _leaf / _digests / _leaves / _free accept a stand-alone tree (gb_batch_coeffs, gb_batch_eval_ext and the stages
+ * of prove() answer GB_ERR_INVALID for one: it has no coefficients). */
+typedef struct gb_batch gb_merkle_tree;
+/* leaves [2^log_leaves][leaf_len] ROW-major canonical words (the flattened Vec<Vec<F>>; every leaf as long as the first); leaf
+ * digest = hash_or_noop.  flags: GB_INPUT_DEVICE / GB_INPUT_P3_REPR as above; host leaves belong to the caller again on return.
+ * cap_height > log_leaves is GB_ERR_INVALID with the reference's message, "cap_height={} should be at most
+ * log2(leaves.len())={}" (:154-157); leaf_len == 0 is GB_ERR_INVALID. */
+gb_status gb_merkle_tree_create(gb_ctx* ctx, uint32_t field, const void* leaves, uint32_t log_leaves, uint32_t leaf_len,
+                                uint32_t cap_height, uint32_t flags, gb_batch** out);
+gb_status gb_merkle_tree_free(gb_batch* tree); /* NULL: GB_OK */
+gb_status gb_merkle_tree_info(const gb_batch* tree, uint32_t* field, uint32_t* log_leaves, uint32_t* leaf_len, uint32_t* cap_height);
+/* .cap (:60-61): out[2^cap_height][H] */
+gb_status gb_merkle_tree_cap(gb_batch* tree, void* out);
+/* get(i) + prove(i) (:183-222): row[leaf_len], siblings[log_leaves - cap_height][H], *nsib = that count; any of the three
+ * pointers may be NULL; leaf_index >= 2^log_leaves is GB_ERR_INVALID */
+gb_status gb_merkle_tree_leaf(gb_batch* tree, uint64_t leaf_index, void* row, void* siblings, uint32_t* nsib);
+/* .digests in the reference's layout (:50-58): out[2 * (2^log_leaves - 2^cap_height)][H] */
+gb_status gb_merkle_tree_digests(gb_batch* tree, void* out);
+
 /* ---- bare kernels (parity tests and microbenchmarks) ---------------------------------------- */
 /* `count` Poseidon-12 (GL) / Poseidon2-16 (BB) permutations: in/out [count][width], host memory.
  * PoseidonGoldilocks::poseidon (hash/poseidon_goldilocks.rs:912-922). */

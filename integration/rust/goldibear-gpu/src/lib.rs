@@ -164,6 +164,20 @@ extern "C" {
     fn gb_proof_compress(c: *mut gb_circuit, proof: *const c_void, len: usize, out: *mut c_void, cap: usize, out_len: *mut usize) -> i32;
     fn gb_proof_decompress(c: *mut gb_circuit, compressed: *const c_void, len: usize, out: *mut c_void, cap: usize,
                            out_len: *mut usize) -> i32;
+    fn gb_fft(ctx: *mut gb_ctx, field: u32, coeffs: *const c_void, values: *mut c_void, ncols: usize, log_n: u32, rate_bits: u32,
+              ext: u32, shift: *const c_void, flags: u32) -> i32;
+    fn gb_ifft(ctx: *mut gb_ctx, field: u32, values: *const c_void, coeffs: *mut c_void, ncols: usize, log_n: u32, ext: u32,
+               shift: *const c_void, flags: u32) -> i32;
+    fn gb_lde(ctx: *mut gb_ctx, field: u32, values: *const c_void, out: *mut c_void, ncols: usize, log_n: u32, rate_bits: u32,
+              ext: u32, shift: *const c_void, flags: u32) -> i32;
+    // a gb_merkle_tree is a gb_batch without polynomials (`typedef struct gb_batch gb_merkle_tree;`)
+    fn gb_merkle_tree_create(ctx: *mut gb_ctx, field: u32, leaves: *const c_void, log_leaves: u32, leaf_len: u32, cap_height: u32,
+                             flags: u32, out: *mut *mut gb_batch) -> i32;
+    fn gb_merkle_tree_free(tree: *mut gb_batch) -> i32;
+    fn gb_merkle_tree_info(tree: *const gb_batch, field: *mut u32, log_leaves: *mut u32, leaf_len: *mut u32, cap_height: *mut u32) -> i32;
+    fn gb_merkle_tree_cap(tree: *mut gb_batch, out: *mut c_void) -> i32;
+    fn gb_merkle_tree_leaf(tree: *mut gb_batch, leaf_index: u64, row: *mut c_void, siblings: *mut c_void, nsib: *mut u32) -> i32;
+    fn gb_merkle_tree_digests(tree: *mut gb_batch, out: *mut c_void) -> i32;
 }
 
 /// Status code + the library's message.
@@ -277,6 +291,119 @@ fn column_table<W, C: AsRef<[W]>>(what: &str, columns: &[C], n: usize) -> Result
 impl Drop for GpuContext {
     fn drop(&mut self) {
         unsafe { gb_ctx_destroy(self.0) };
+    }
+}
+
+/// The reference's transforms on slices (field/src/polynomial/mod.rs): `PolynomialCoeffs::fft` / `coset_fft` (after `.lde(rate_bits)`),
+/// `PolynomialValues::ifft` / `coset_ifft` / `lde` / `lde_onto_coset`.  `data` holds `num_polys` polynomials laid end to end, natural
+/// order, canonical words (`W` = `u64` Goldilocks / `u32` BabyBear) or, with `Repr::P3InMemory`, the field type's own words; with
+/// `ext` every element is D consecutive words (`PolynomialCoeffs<F::Extension>`).  `shift`: `None`, or a canonical base-field element.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Transform {
+    Fft,
+    Ifft,
+    Lde,
+}
+impl GpuContext {
+    fn poly_shape<W>(len: usize, num_polys: usize, ext: bool) -> Result<u32, GpuError> {
+        let d = if !ext { 1 } else if std::mem::size_of::<W>() == 8 { 2 } else { 4 };
+        if num_polys == 0 || len % (num_polys * d) != 0 || !(len / (num_polys * d)).is_power_of_two() {
+            return Err(GpuError { status: GB_ERR_INVALID, message: "polynomial length must be a power of two".into() });
+        }
+        Ok((len / (num_polys * d)).trailing_zeros())
+    }
+    /// One transform into a fresh vector of `len << rate_bits` words (`rate_bits` is ignored by `Transform::Ifft`).
+    pub fn transform<W: Copy + Default>(&self, op: Transform, data: &[W], num_polys: usize, rate_bits: u32, ext: bool, shift: Option<W>,
+                                        repr: Repr) -> Result<Vec<W>, GpuError> {
+        let log_n = Self::poly_shape::<W>(data.len(), num_polys, ext)?;
+        let rate_bits = if op == Transform::Ifft { 0 } else { rate_bits };
+        let mut out = vec![W::default(); data.len() << rate_bits];
+        let sp = shift.as_ref().map_or(ptr::null(), |s| s as *const W as *const c_void);
+        let (src, dst, f) = (data.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void, field_tag::<W>());
+        check(self.0, unsafe {
+            match op {
+                Transform::Fft => gb_fft(self.0, f, src, dst, num_polys, log_n, rate_bits, ext as u32, sp, repr.flags()),
+                Transform::Ifft => gb_ifft(self.0, f, src, dst, num_polys, log_n, ext as u32, sp, repr.flags()),
+                Transform::Lde => gb_lde(self.0, f, src, dst, num_polys, log_n, rate_bits, ext as u32, sp, repr.flags()),
+            }
+        })?;
+        Ok(out)
+    }
+    /// `fft` / `coset_fft` / `ifft` / `coset_ifft` in place, as the reference consumes `self` (canonical words in, canonical out).
+    pub fn transform_in_place<W: Copy + Default>(&self, op: Transform, data: &mut [W], num_polys: usize, ext: bool, shift: Option<W>)
+                                                 -> Result<(), GpuError> {
+        let log_n = Self::poly_shape::<W>(data.len(), num_polys, ext)?;
+        let sp = shift.as_ref().map_or(ptr::null(), |s| s as *const W as *const c_void);
+        let (p, f) = (data.as_mut_ptr() as *mut c_void, field_tag::<W>());
+        check(self.0, unsafe {
+            match op {
+                Transform::Ifft => gb_ifft(self.0, f, p, p, num_polys, log_n, ext as u32, sp, GB_INPUT_HOST),
+                Transform::Fft => gb_fft(self.0, f, p, p, num_polys, log_n, 0, ext as u32, sp, GB_INPUT_HOST),
+                Transform::Lde => gb_lde(self.0, f, p, p, num_polys, log_n, 0, ext as u32, sp, GB_INPUT_HOST),
+            }
+        })
+    }
+}
+
+/// `MerkleTree::new(leaves, cap_height)` (hash/merkle_tree.rs:152-181) with the leaves and digests resident on the GPU.
+pub struct GpuMerkleTree<'c, W> {
+    ctx: &'c GpuContext,
+    handle: *mut gb_batch,
+    pub log_leaves: u32,
+    pub leaf_len: u32,
+    pub cap_height: u32,
+    _w: std::marker::PhantomData<W>,
+}
+impl<'c, W: Copy + Default> GpuMerkleTree<'c, W> {
+    /// `leaves`: the rows laid end to end ([num_leaves][leaf_len], every leaf `leaf_len` words)
+    pub fn new(ctx: &'c GpuContext, leaves: &[W], leaf_len: usize, cap_height: u32, repr: Repr) -> Result<Self, GpuError> {
+        if leaf_len == 0 || leaves.len() % leaf_len != 0 || !(leaves.len() / leaf_len).is_power_of_two() {
+            return Err(GpuError { status: GB_ERR_INVALID, message: "the number of leaves must be a power of two".into() });
+        }
+        let log_leaves = (leaves.len() / leaf_len).trailing_zeros();
+        let mut h = ptr::null_mut();
+        check(ctx.0, unsafe {
+            gb_merkle_tree_create(ctx.0, field_tag::<W>(), leaves.as_ptr() as *const c_void, log_leaves, leaf_len as u32, cap_height,
+                                  repr.flags(), &mut h)
+        })?;
+        let (mut f, mut ll, mut w, mut ch) = (0u32, 0u32, 0u32, 0u32);
+        let st = unsafe { gb_merkle_tree_info(h, &mut f, &mut ll, &mut w, &mut ch) };
+        let t = Self { ctx, handle: h, log_leaves: ll, leaf_len: w, cap_height: ch, _w: std::marker::PhantomData };
+        check(ctx.0, st)?;
+        Ok(t)
+    }
+    fn hash_len() -> usize {
+        if std::mem::size_of::<W>() == 8 { 4 } else { 8 }
+    }
+    /// `.cap`
+    pub fn cap(&self) -> Result<Vec<W>, GpuError> {
+        let mut out = vec![W::default(); Self::hash_len() << self.cap_height];
+        check(self.ctx.0, unsafe { gb_merkle_tree_cap(self.handle, out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+    /// `.digests` in the reference's layout (merkle_tree.rs:50-58)
+    pub fn digests(&self) -> Result<Vec<W>, GpuError> {
+        let count = 2 * ((1usize << self.log_leaves) - (1usize << self.cap_height));
+        let mut out = vec![W::default(); count * Self::hash_len()];
+        check(self.ctx.0, unsafe { gb_merkle_tree_digests(self.handle, out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+    /// `get(i)` and `prove(i)` (merkle_tree.rs:183-222): (leaf, siblings)
+    pub fn leaf_and_proof(&self, leaf_index: usize) -> Result<(Vec<W>, Vec<W>), GpuError> {
+        let layers = (self.log_leaves - self.cap_height) as usize;
+        let mut row = vec![W::default(); self.leaf_len as usize];
+        let mut sib = vec![W::default(); layers.max(1) * Self::hash_len()];
+        let mut nsib = 0u32;
+        check(self.ctx.0, unsafe {
+            gb_merkle_tree_leaf(self.handle, leaf_index as u64, row.as_mut_ptr() as *mut c_void, sib.as_mut_ptr() as *mut c_void, &mut nsib)
+        })?;
+        sib.truncate(nsib as usize * Self::hash_len());
+        Ok((row, sib))
+    }
+}
+impl<'c, W> Drop for GpuMerkleTree<'c, W> {
+    fn drop(&mut self) {
+        unsafe { gb_merkle_tree_free(self.handle) };
     }
 }
 

@@ -57,6 +57,7 @@ struct TableCache {
     struct Owner {   // a table set and the device blocks it owns
         X t{};
         std::vector<void*> owned;
+        std::vector<size_t> pooled_bytes;   // TempCosets only: `owned` are pool blocks of these sizes
     };
     const T *tw4096_fwd = nullptr, *tw4096_inv = nullptr;
     const T *tw4096_fwd_m = nullptr, *tw4096_inv_m = nullptr;   // Goldilocks: the same times R (Montgomery form)
@@ -320,8 +321,18 @@ template <class F>
 constexpr bool is_goldilocks = std::is_same<F, GlF>::value;
 
 template <class T>
-gb_status upload(gb_ctx* ctx, const std::vector<T>& host, const T** dev, std::vector<void*>& owned) {
+gb_status upload(gb_ctx* ctx, const std::vector<T>& host, const T** dev, std::vector<void*>& owned, std::vector<size_t>* pooled_bytes = nullptr) {
     void* p = nullptr;
+    if (pooled_bytes) {   // a table of one call (TempCosets): a pool block, written in stream order behind whoever read it last
+        const size_t bytes = host.size() * sizeof(T);
+        if (pool_alloc(ctx, bytes, &p) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, GB_ERR_OOM, "hipMalloc shift tables"); }
+        owned.push_back(p);
+        pooled_bytes->push_back(bytes);
+        HIP_TRY(ctx, hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `host` is the caller's local
+        *dev = static_cast<const T*>(p);
+        return GB_OK;
+    }
     HIP_TRY(ctx, hipMalloc(&p, host.size() * sizeof(T)));
     HIP_TRY(ctx, hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     *dev = static_cast<const T*>(p);
@@ -436,14 +447,29 @@ gb_status ensure_big_work(gb_ctx* ctx, u32 log_n, u32 rate_bits, size_t es) {
     }
     return GB_OK;
 }
+// The cache is keyed by the shift and never evicts, so it holds the sets of the shifts the library chooses itself.  The tables of a
+// caller-chosen shift (gb_fft / gb_ifft / gb_lde) are built into a TempCosets instead: pool blocks that go back when the call ends.
+template <class F>
+struct TempCosets {
+    typedef typename TableCache<F>::template Owner<typename TableCache<F>::Cosets> Set;
+    gb_ctx* ctx;
+    std::map<std::tuple<u32, u32, typename F::T, int>, Set> sets;
+    explicit TempCosets(gb_ctx* c) : ctx(c) {}
+    TempCosets(const TempCosets&) = delete;
+    ~TempCosets() {
+        for (auto& kv : sets)
+            for (size_t i = 0; i < kv.second.pooled_bytes.size(); i++) pool_free(ctx, kv.second.owned[i], kv.second.pooled_bytes[i]);
+    }
+};
 template <class F>
 gb_status cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, typename F::T shift, bool inverse,
-                     const typename TableCache<F>::Cosets** out) {
+                     const typename TableCache<F>::Cosets** out, TempCosets<F>* tmp = nullptr) {
     typedef typename F::T T;
     TableCache<F>& tc = cache<F>(ctx);
     auto key = std::make_tuple(log_n, rate_bits, shift, inverse ? 1 : 0);
-    auto it = tc.cosets.find(key);
-    if (it != tc.cosets.end()) {
+    auto& sets = tmp ? tmp->sets : tc.cosets;
+    auto it = sets.find(key);
+    if (it != sets.end()) {
         if (!inverse)   // (released by gb_ctx_trim)
             if (gb_status sw = ensure_big_work(ctx, log_n, rate_bits, sizeof(T))) return sw;
         *out = &it->second.t;
@@ -461,26 +487,30 @@ gb_status cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, typename F::T shift,
         std::memcpy(&lo[c * nlo], pl.data(), nlo * sizeof(T));
         std::memcpy(&hi[c * nhi], ph.data(), nhi * sizeof(T));
     }
-    typename TableCache<F>::template Owner<typename TableCache<F>::Cosets> set;
+    // (a TempCosets entry is filled in place: what an error leaves half built is released with the rest of it)
+    typename TableCache<F>::template Owner<typename TableCache<F>::Cosets> cached_set;
+    auto& set = tmp ? tmp->sets[key] : cached_set;
+    std::vector<size_t>* const pooled = tmp ? &set.pooled_bytes : nullptr;
     set.t.rate_bits = rate_bits;
     gb_status s;
     // inverse tables are read as power tables only (the quotient's coset_ifft); the LDE kernels never see them
     if (const u32 K = gbk::ntt_outer_bits(log_n); K && !inverse) {   // sub-transforms of n / R rows on the shift s_c^R, R = 2^K (ntt_outer.hpp)
-        if ((s = cosets_for<F>(ctx, log_n - K, rate_bits, F::pow(shift, (u64)1 << K), false, &set.t.sub))) return s;
+        if ((s = cosets_for<F>(ctx, log_n - K, rate_bits, F::pow(shift, (u64)1 << K), false, &set.t.sub, tmp))) return s;
         if ((s = ensure_big_work(ctx, log_n, rate_bits, sizeof(T)))) return s;
         DeviceBuf& wb = ctx->big_work[big_work_level(log_n)];
         set.t.work = &wb.p; set.t.work_bytes = &wb.bytes;
     }
     if constexpr (!is_goldilocks<F>)
         if (log_n == 22 && !inverse)   // BabyBear: the finer cosets of 2^20 rows (k_bb_lde_pa16x2w)
-            if ((s = cosets_for<F>(ctx, 20, rate_bits + 2, shift, false, &set.t.fine))) return s;
-    if ((s = upload(ctx, lo, &set.t.pow_lo, set.owned))) return s;
-    if ((s = upload(ctx, hi, &set.t.pow_hi, set.owned))) return s;
+            if ((s = cosets_for<F>(ctx, 20, rate_bits + 2, shift, false, &set.t.fine, tmp))) return s;
+    if ((s = upload(ctx, lo, &set.t.pow_lo, set.owned, pooled))) return s;
+    if ((s = upload(ctx, hi, &set.t.pow_hi, set.owned, pooled))) return s;
     if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins of kernels_ntt16.hip
-        if ((s = upload(ctx, times_r(lo), &set.t.pow_lo_m, set.owned))) return s;
-        if ((s = upload(ctx, times_r(hi), &set.t.pow_hi_m, set.owned))) return s;
+        if ((s = upload(ctx, times_r(lo), &set.t.pow_lo_m, set.owned, pooled))) return s;
+        if ((s = upload(ctx, times_r(hi), &set.t.pow_hi_m, set.owned, pooled))) return s;
     }
-    auto res = tc.cosets.emplace(key, std::move(set));
+    if (tmp) { *out = &set.t; return GB_OK; }
+    auto res = tc.cosets.emplace(key, std::move(cached_set));
     *out = &res.first->second.t;
     return GB_OK;
 }
@@ -1328,6 +1358,7 @@ gb_status gb_batch_cap(gb_batch* b, void* out) try {
 gb_status gb_batch_coeffs(gb_batch* b, size_t col, void* out) try {
     if (!b || !out) return fail(b ? b->ctx : nullptr, GB_ERR_INVALID, "null argument");
     if (col >= b->ncols) return fail(b->ctx, GB_ERR_INVALID, "polynomial index out of range");
+    if (!b->coeffs) return fail(b->ctx, GB_ERR_INVALID, "a stand-alone Merkle tree holds no polynomials");
     return b->field == GB_BABYBEAR ? read_coeffs<BbF>(b, col, out) : read_coeffs<GlF>(b, col, out);
 } GB_CATCH(b ? b->ctx : nullptr)
 
@@ -1423,6 +1454,7 @@ gb_status gb_permute(gb_ctx* ctx, uint32_t field, const void* in, void* out, uin
 
 }  // extern "C"
 
+#include "poly_host.inc"
 #include "prover_host.inc"
 #include "verifier_host.inc"
 #include "compress_host.inc"

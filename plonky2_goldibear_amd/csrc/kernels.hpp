@@ -116,6 +116,30 @@ void bitrev_copy(const typename F::T* src, typename F::T* dst, u32 bits, size_t 
 template <class F>
 void reduce_words(typename F::T* p, size_t count, hipStream_t stream);
 
+// ---------------------------------------------------------------- stand-alone transforms and trees (kernels_poly.hip)
+// The transform passes move canonical words and convert nothing (the transforms are linear and multiply by table values only:
+// canonical words in, canonical words out, for BabyBear's Montgomery tables too - kernels_poly.hip).  `ext`: an element is F::D
+// consecutive words, and the transforms see its coordinates as F::D columns (column c of the caller = columns c D .. c D + D - 1).
+
+// leaf order -> natural order: one workgroup per column up to 2^POLY_SMALL_LOG elements, 64 x 64 tiles above
+static constexpr u32 POLY_SMALL_LOG = 12;
+// extension elements [ncols][len][D] -> coordinate columns [ncols * D][len]
+template <class F>
+void ext_load(const typename F::T* src, typename F::T* dst, size_t ncols, u32 log_len, hipStream_t stream);
+// coordinate columns, natural order -> the caller's layout (interleaved if ext), element i times pow_lo[i % 4096] pow_hi[i / 4096]
+// where pow_lo is not null (split powers in plain device form, as CosetTables::pow_lo / pow_hi of one coset).  dst may equal src
+// unless ext; neither ext nor pow_lo: nothing to do.
+template <class F>
+void poly_store(const typename F::T* src, typename F::T* dst, size_t ncols, u32 log_len, bool ext, const typename F::T* pow_lo,
+                const typename F::T* pow_hi, hipStream_t stream);
+// coordinate columns in LEAF order (lde_columns' output) -> NATURAL order in the caller's layout: dst[i] = src[bitrev(i)]
+template <class F>
+void poly_bitrev_store(const typename F::T* src, typename F::T* dst, size_t ncols, u32 log_len, bool ext, hipStream_t stream);
+// row-major canonical leaves [num_rows][width] -> column-major device form [width][num_rows]; width <= ROWS_MAX_WIDTH
+static constexpr u32 ROWS_MAX_WIDTH = 64 * 65535;
+template <class F>
+void rows_to_columns(const typename F::T* rows, typename F::T* cols, u64 num_rows, u32 width, hipStream_t stream);
+
 // ---------------------------------------------------------------- Poseidon-12 Merkle (kernels_merkle.hip)
 
 // leaf digests: out[j] = hash_or_noop(row j), row j = { cols[c*col_stride + j] : c < width }

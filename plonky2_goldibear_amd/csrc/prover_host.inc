@@ -1056,6 +1056,7 @@ template <class F>
 static gb_status check_stage_batch(Circuit<F>* c, const gb_batch* b, size_t ncols, const char* what) {
     const gb_circuit_config& cfg = c->cfg;
     if (!b) return fail(c->ctx, GB_ERR_INVALID, std::string("null ") + what + " batch");
+    if (!b->coeffs) return fail(c->ctx, GB_ERR_INVALID, std::string(what) + " is a stand-alone Merkle tree, not a polynomial batch");
     if (b->ctx != c->ctx || b->field != c->field) return fail(c->ctx, GB_ERR_INVALID, std::string(what) + " batch belongs to another context or field");
     if (b->log_n != cfg.degree_bits || b->rate_bits != cfg.rate_bits || b->cap_height != cfg.cap_height || b->ncols != ncols ||
         b->nsalt != (cfg.zero_knowledge ? (size_t)GB_SALT_SIZE : 0))
@@ -1292,6 +1293,7 @@ gb_status gb_pow_grind(gb_ctx* ctx, uint32_t field, const void* sponge_state, ui
 gb_status gb_batch_eval_ext(gb_batch* b, const void* z, void* out) try {
     if (!b) return fail(nullptr, GB_ERR_INVALID, "null batch");
     if (!z || !out) return fail(b->ctx, GB_ERR_INVALID, "null argument");
+    if (!b->coeffs) return fail(b->ctx, GB_ERR_INVALID, "a stand-alone Merkle tree holds no polynomials");
     return b->field == GB_GOLDILOCKS ? batch_eval_ext<GlF>(b, z, out) : batch_eval_ext<BbF>(b, z, out);
 } GB_CATCH(b ? b->ctx : nullptr)
 

@@ -83,6 +83,15 @@ SIGNATURES = {
     "gb_prove_retry_cols": (_i32, [_vp, _cols, _u32, _u32, _u64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_salted_cols": (_i32, [_vp, _cols, _u32, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
     "gb_zs_partial_products_cols": (_i32, [_vp, _cols, _u32, _vp, _vp, _vp]),
+    "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
+    "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
+    "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
+    "gb_merkle_tree_create": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _u32, _pvp]),
+    "gb_merkle_tree_free": (_i32, [_vp]),
+    "gb_merkle_tree_info": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gb_merkle_tree_cap": (_i32, [_vp, _vp]),
+    "gb_merkle_tree_leaf": (_i32, [_vp, _u64, _vp, _vp, C.POINTER(_u32)]),
+    "gb_merkle_tree_digests": (_i32, [_vp, _vp]),
 }
 # include/goldibear_gpu_test_hooks.h: exports for the test suite, outside the product ABI
 TEST_HOOK_SIGNATURES = {

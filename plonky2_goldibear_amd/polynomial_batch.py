@@ -164,17 +164,74 @@ def _as_columns(cols, field=N.GB_GOLDILOCKS):
     return ptrs, (len(cols), n), (N.GB_INPUT_DEVICE if dev else N.GB_INPUT_HOST), keep
 
 
+class _TreeHandle:
+    """A stand-alone tree's device object (gb_merkle_tree): what MerkleTree reads of a PolynomialBatch, over gb_merkle_tree_*."""
+    _prefix = "gb_merkle_tree_"
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle, self._lib = ctx, handle, ctx._lib
+        f, ll, w, ch = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        N.check(self._lib.gb_merkle_tree_info(handle, C.byref(f), C.byref(ll), C.byref(w), C.byref(ch)))
+        self.field, self.degree_log, self.rate_bits, self.width, self.cap_height = f.value, ll.value, 0, w.value, ch.value
+        self._hout = 4 if self.field == N.GB_GOLDILOCKS else 8
+        self._dt = _dtype(self.field)
+        _live_batches.add(self)
+
+    def free(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self._lib.gb_merkle_tree_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        if not sys.is_finalizing():
+            self.free()
+
+    def _leaf(self, i):
+        row = np.empty(self.width, dtype=self._dt)
+        sib = np.empty((max(self.degree_log - self.cap_height, 1), self._hout), dtype=self._dt)
+        n = C.c_uint32()
+        N.check(self._lib.gb_merkle_tree_leaf(self.handle, i, row.ctypes.data, sib.ctypes.data, C.byref(n)), self.ctx.handle)
+        return row, sib[: n.value]
+
+
 class MerkleTree:
-    """View of a batch's tree: hash/merkle_tree.rs:46-62,183-222."""
+    """hash/merkle_tree.rs:46-62,183-222: the view of a batch's tree (MerkleTree(batch)), or a tree of its own over any leaves
+    (MerkleTree.new)."""
 
     def __init__(self, batch):
         self._b = weakref.proxy(batch)  # no cycle: the batch frees its device memory when dropped
+
+    @classmethod
+    def new(cls, ctx, leaves, cap_height, field=N.GB_GOLDILOCKS, p3_repr=False):
+        """MerkleTree::new(leaves, cap_height) (merkle_tree.rs:152-181).  leaves: [num_leaves][leaf_len] canonical words, row-major
+        (the reference's Vec<Vec<F>>) - a numpy array, or a torch CUDA tensor of the field's word size.  The tree lives on the GPU
+        until it is dropped (or .free()d)."""
+        ptr, shape, flags, keep = _as_input(leaves, field)
+        if len(shape) != 2:
+            raise N.ShapeError(N.GB_ERR_INVALID, "expected [num_leaves][leaf_len] leaves")
+        num, width = shape
+        log_leaves = int(num).bit_length() - 1
+        if num == 0 or (1 << log_leaves) != num:
+            raise N.ShapeError(N.GB_ERR_INVALID, "the number of leaves must be a power of two (merkle_tree.rs:153 log2_strict)")
+        if p3_repr:
+            flags |= N.GB_INPUT_P3_REPR
+        h = C.c_void_p()
+        N.check(ctx._lib.gb_merkle_tree_create(ctx.handle, field, ptr, log_leaves, width, cap_height, flags, C.byref(h)), ctx.handle)
+        del keep
+        t = cls.__new__(cls)
+        t._b = _TreeHandle(ctx, h)   # owned: freed with the tree
+        return t
+
+    def free(self):
+        """release a stand-alone tree's device memory now (a batch's tree goes with its batch)"""
+        if isinstance(self._b, _TreeHandle):
+            self._b.free()
 
     @property
     def cap(self):
         b = self._b
         out = np.empty((1 << b.cap_height, b._hout), dtype=b._dt)
-        N.check(b._lib.gb_batch_cap(b.handle, out.ctypes.data), b.ctx.handle)
+        N.check(getattr(b._lib, b._prefix + "cap")(b.handle, out.ctypes.data), b.ctx.handle)
         return out
 
     @property
@@ -183,14 +240,14 @@ class MerkleTree:
         b = self._b
         n = 2 * ((1 << (b.degree_log + b.rate_bits)) - (1 << b.cap_height))
         out = np.empty((n, b._hout), dtype=b._dt)
-        N.check(b._lib.gb_batch_digests(b.handle, out.ctypes.data), b.ctx.handle)
+        N.check(getattr(b._lib, b._prefix + "digests")(b.handle, out.ctypes.data), b.ctx.handle)
         return out
 
     @property
     def leaves(self):
         b = self._b
         out = np.empty((1 << (b.degree_log + b.rate_bits), b.width), dtype=b._dt)
-        N.check(b._lib.gb_batch_leaves(b.handle, out.ctypes.data), b.ctx.handle)
+        N.check(b._lib.gb_batch_leaves(b.handle, out.ctypes.data), b.ctx.handle)   # (a tree handle is a batch handle)
         return out
 
     def get(self, i):
@@ -203,6 +260,7 @@ class MerkleTree:
 
 class PolynomialBatch:
     """fri/oracle.rs:29-158 with the data resident on the GPU."""
+    _prefix = "gb_batch_"
 
     def __init__(self, ctx, handle, borrowed=False):
         self.ctx, self.handle, self._lib = ctx, handle, ctx._lib
