@@ -52,9 +52,10 @@ __host__ __device__ __forceinline__ u32 reduce_lazy(u64 t) {
     return (u32)((t + (u64)m * P) >> 32);
 }
 __host__ __device__ __forceinline__ u32 mul_lazy(u32 a, u32 b) { return reduce_lazy((u64)a * b); }  // a * b < P * 2^32
-// SIGNED Montgomery product: a, b signed words with |a|, |b| <= 1.03 P -> a word r congruent to a b 2^-32 with |r| < 0.97 P + 1.
+// SIGNED Montgomery product: a, b signed words with |a|, |b| <= 1.03 P -> a word r congruent to a b 2^-32 with |r| < 0.9973 P + 1
+// (|a b| / 2^32 + P / 2; 0.97 P for |a|, |b| <= P).
 // t = a b exactly; m = lo(t) / P mod 2^32 taken as SIGNED makes t - m P a multiple of 2^32 of magnitude < P^2 + 2^31 P, so its
-// high word needs no selection at all and the representation is closed under itself (0.97 P < 1.03 P): a product is two
+// high word needs no selection at all and the representation is closed under itself (0.9973 P < 1.03 P): a product is two
 // multiplies and one multiply-add (v_mad_i64_i32, v_mul_lo_u32, v_mad_i64_i32), with nothing after them - the unsigned forms
 // above end in [0, 2P), which a second product with a lazy partner would overflow.  `bias` (0 or P) is added for a consumer that
 // wants a non-negative word: r + P lies in (0, 2 P).

@@ -112,7 +112,7 @@ __device__ static const u32 ZERO16[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
 
 // x^7 for a word x with |x| <= 1.03 p as a signed number (canonical, or what bb::reduce_signed leaves); the result is LAZY
 // (in (0, 2p)).  The three inner products are SIGNED Montgomery products (bb::mul_signed: no final selection, the word just stays
-// within +-0.97 p), the last one adds p to come out non-negative: 12 multiplies + 5 plain operations, where two canonical and two
+// within +-0.9973 p), the last one adds p to come out non-negative: 12 multiplies + 5 plain operations, where two canonical and two
 // lazy unsigned products took 12 + 10.  Every consumer here takes a lazy word: the unreduced sums of the external layer and the
 // multiplication by kappa^-6 of the internal rounds.
 __device__ __forceinline__ u32 sbox7(u32 x) {

@@ -47,15 +47,20 @@ BB_SHAPES = _shapes((1, 8, 9, 16, 17, 167), 167)
 _bb_levels = {}   # (L, width) -> (leaves, [level 0 .. root]); shared by the cap heights of a shape, never modified
 
 
+def bb_levels_of(leaves):
+    """[level 0 .. root] of the BabyBear tree over `leaves`, from oracle_bb.hash_or_noop and two_to_one"""
+    levels = [np.stack([B.hash_or_noop(r) for r in leaves])]
+    while levels[-1].shape[0] > 1:
+        d = levels[-1]
+        levels.append(np.stack([B.two_to_one(d[2 * i], d[2 * i + 1]) for i in range(d.shape[0] // 2)]))
+    return levels
+
+
 def _bb_tree(L, width):
     if (L, width) not in _bb_levels:
         leaves = B.fill(7000 + 31 * L + width, L * width).reshape(L, width)
         leaves[0, 0], leaves[L - 1, width - 1] = 0, B.BB_P - 1
-        levels = [np.stack([B.hash_or_noop(r) for r in leaves])]
-        while levels[-1].shape[0] > 1:
-            d = levels[-1]
-            levels.append(np.stack([B.two_to_one(d[2 * i], d[2 * i + 1]) for i in range(d.shape[0] // 2)]))
-        _bb_levels[(L, width)] = (leaves, levels)
+        _bb_levels[(L, width)] = (leaves, bb_levels_of(leaves))
     return _bb_levels[(L, width)]
 
 
