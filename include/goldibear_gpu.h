@@ -395,6 +395,36 @@ typedef struct gb_challenger_state {
 gb_status gb_prove_openings(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial_products, gb_batch* quotient, const void* zeta,
                             gb_challenger_state* challenger, void* fri_proof_out, size_t fri_proof_cap, size_t* fri_proof_len);
 
+/* PolynomialBatch::prove_openings (fri/oracle.rs:187-246) on any FriInstanceInfo (fri/structure.rs), then fri_proof
+ * (fri/prover.rs:29-81).  oracles[num_oracles]: commitments made on ctx.  Batch b opens batch_sizes[b] polynomials at
+ * points[b] ([num_batches][D] canonical words); polynomials: [sum of batch_sizes][2] = (oracle_index, polynomial_index), batch
+ * after batch, in the order of FriBatchInfo::polynomials.  degree_bits, rate_bits, cap_height and the field are the oracles' own.
+ * challenger / fri_proof_out / sizes / behaviour on error: exactly as gb_prove_openings.
+ * The lists may be in any order, name a polynomial in several batches or twice in one, and leave an oracle out of every batch: it
+ * still contributes its row and path to every query round, as fri_proof is handed every oracle's tree.  Blinding needs no flag:
+ * an oracle committed with salts opens rows of ncols + GB_SALT_SIZE words; polynomial_index counts polynomials only.
+ * GB_ERR_INVALID (with a message): num_oracles, num_batches or a batch size of zero; a NULL oracle, one from another context or
+ * field, or a stand-alone Merkle tree; oracles that differ in degree_bits, rate_bits or cap_height; an index out of range; a
+ * reduction_arity_bits list gb_circuit_set_fri_reduction_arity_bits would refuse for this shape (the empty list is valid); a
+ * coordinate >= p; proof_of_work_bits > 31.  GB_ERR_UNSUPPORTED: a point equal to zero - divide_by_linear runs here on the powers
+ * of the point's INVERSE (any other point is fine, one inside the subgroup included: the reference does not check it here). */
+#define GB_MAX_FRI_QUERY_ROUNDS 4096 /* num_query_rounds of the two functions below: 0 or above this is GB_ERR_INVALID */
+gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t num_oracles, const void* points,
+                                const uint32_t* batch_sizes, uint32_t num_batches, const uint32_t* polynomials,
+                                const uint32_t* reduction_arity_bits, uint32_t num_layers, uint32_t proof_of_work_bits,
+                                uint32_t num_query_rounds, gb_challenger_state* challenger, void* fri_proof_out,
+                                size_t fri_proof_cap, size_t* fri_proof_len);
+/* verify_fri_proof (fri/verifier.rs:67-250) for the same description of an instance, on the host; ctx may be NULL.
+ * oracle_num_polys / oracle_blinding: FriOracleInfo; hiding: FriParams.hiding; openings: [sum of batch_sizes][D] (FriOpenings);
+ * initial_caps: [num_oracles][2^cap_height][H]; challenger: the transcript after the openings were observed (by value: the caller's
+ * copy is not advanced).  GB_OK / GB_ERR_VERIFY (the failed check in gb_last_error) / GB_ERR_INVALID (malformed bytes or arguments). */
+gb_status gb_fri_verify(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t hiding,
+                        const uint32_t* oracle_num_polys, const uint32_t* oracle_blinding, uint32_t num_oracles, const void* points,
+                        const uint32_t* batch_sizes, uint32_t num_batches, const uint32_t* polynomials, const void* openings,
+                        const void* initial_caps, const uint32_t* reduction_arity_bits, uint32_t num_layers,
+                        uint32_t proof_of_work_bits, uint32_t num_query_rounds, const gb_challenger_state* challenger,
+                        const void* fri_proof, size_t fri_proof_len);
+
 /* fri_proof_of_work (fri/prover.rs:136-188) on its own, for a host that keeps the Challenger: sponge_state is the
  * duplex state with the pending input buffer already written over lanes 0..witness_pos-1 (`duplex_intermediate_state`,
  * :165-167; [12] u64 / [16] u32 canonical), witness_pos = input_buffer.len().  Returns the MINIMUM candidate whose

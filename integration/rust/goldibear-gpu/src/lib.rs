@@ -151,6 +151,15 @@ extern "C" {
     fn gb_prove_openings(c: *mut gb_circuit, wires: *mut gb_batch, zs_partial_products: *mut gb_batch, quotient: *mut gb_batch,
                          zeta: *const c_void, challenger: *mut gb_challenger_state, fri_proof_out: *mut c_void,
                          fri_proof_cap: usize, fri_proof_len: *mut usize) -> i32;
+    fn gb_fri_prove_openings(ctx: *mut gb_ctx, oracles: *const *mut gb_batch, num_oracles: u32, points: *const c_void,
+                             batch_sizes: *const u32, num_batches: u32, polynomials: *const u32, reduction_arity_bits: *const u32,
+                             num_layers: u32, proof_of_work_bits: u32, num_query_rounds: u32, challenger: *mut gb_challenger_state,
+                             fri_proof_out: *mut c_void, fri_proof_cap: usize, fri_proof_len: *mut usize) -> i32;
+    fn gb_fri_verify(ctx: *mut gb_ctx, field: u32, degree_bits: u32, rate_bits: u32, cap_height: u32, hiding: u32,
+                     oracle_num_polys: *const u32, oracle_blinding: *const u32, num_oracles: u32, points: *const c_void,
+                     batch_sizes: *const u32, num_batches: u32, polynomials: *const u32, openings: *const c_void,
+                     initial_caps: *const c_void, reduction_arity_bits: *const u32, num_layers: u32, proof_of_work_bits: u32,
+                     num_query_rounds: u32, challenger: *const gb_challenger_state, fri_proof: *const c_void, fri_proof_len: usize) -> i32;
     fn gb_circuit_create_gates(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
                                constants_sigmas: *const c_void, k_is: *const c_void, flags: u32, out: *mut *mut gb_circuit) -> i32;
     fn gb_prove_retry(c: *mut gb_circuit, witness: *const c_void, flags: u32, wire: u32, row: u64, public_inputs: *const u64,
@@ -527,6 +536,91 @@ impl<'c, W> Drop for GpuPolynomialBatch<'c, W> {
     fn drop(&mut self) {
         unsafe { gb_batch_free(self.handle) };
     }
+}
+
+/// `FriInstanceInfo` (fri/structure.rs) as slices: `oracles[i]` = (`FriOracleInfo.num_polys`, `.blinding`); batch `b` opens
+/// `polynomials[b]` = its `FriPolynomialInfo`s as (oracle_index, polynomial_index), in order, at `points[b * D .. (b + 1) * D]`.
+pub struct FriInstance<'a, W> {
+    pub oracles: &'a [(usize, bool)],
+    pub points: &'a [W],
+    pub polynomials: &'a [&'a [(usize, usize)]],
+}
+/// What `fri_proof` and `verify_fri_proof` read of `FriParams` (fri/mod.rs:71-86)
+pub struct FriParams<'a> {
+    pub degree_bits: u32,
+    pub rate_bits: u32,
+    pub cap_height: u32,
+    pub hiding: bool,
+    pub proof_of_work_bits: u32,
+    pub num_query_rounds: u32,
+    pub reduction_arity_bits: &'a [usize],
+}
+impl<'a, W: Copy + Default> FriInstance<'a, W> {
+    /// (batch_sizes, [sum][2] = (oracle_index, polynomial_index)) as the C ABI takes them; the point count is checked here
+    fn lists(&self) -> Result<(Vec<u32>, Vec<u32>), GpuError> {
+        let d = if std::mem::size_of::<W>() == 8 { 2 } else { 4 };   // extension degree D
+        need("points", self.points.len(), self.polynomials.len() * d)?;
+        let mut sizes = Vec::with_capacity(self.polynomials.len());
+        let mut polys = Vec::new();
+        for batch in self.polynomials {
+            sizes.push(batch.len() as u32);
+            for &(o, k) in batch.iter() {
+                polys.push(o as u32);
+                polys.push(k as u32);
+            }
+        }
+        Ok((sizes, polys))
+    }
+}
+/// `PolynomialBatch::prove_openings` (fri/oracle.rs:187-246) on any `FriInstanceInfo`, then `fri_proof`: FriProof bytes.
+/// `oracles[i]` is the commitment of `instance.oracles[i]`; `challenger` (the transcript after the openings were observed) is
+/// advanced as the reference's is, and left alone on an error.
+pub fn fri_prove_openings<'c, W: Copy + Default>(ctx: &'c GpuContext, instance: &FriInstance<W>, oracles: &[&GpuPolynomialBatch<'c, W>],
+                                                 params: &FriParams, challenger: &mut gb_challenger_state) -> Result<Vec<u8>, GpuError> {
+    need("oracles", oracles.len(), instance.oracles.len())?;
+    for (b, &(num_polys, blinding)) in oracles.iter().zip(instance.oracles) {
+        need("FriOracleInfo.num_polys", num_polys, b.num_polys)?;
+        if blinding != b.blinding {
+            return Err(GpuError { status: GB_ERR_INVALID, message: "FriOracleInfo.blinding does not match the batch's salts".into() });
+        }
+    }
+    let (sizes, polys) = instance.lists()?;
+    let handles: Vec<*mut gb_batch> = oracles.iter().map(|b| b.handle).collect();
+    let arity: Vec<u32> = params.reduction_arity_bits.iter().map(|&b| b as u32).collect();
+    let mut buf = vec![0u8; 8 << 20];
+    let mut len = 0usize;
+    check(ctx.0, unsafe {
+        gb_fri_prove_openings(ctx.0, handles.as_ptr(), handles.len() as u32, instance.points.as_ptr() as *const c_void, sizes.as_ptr(),
+                              sizes.len() as u32, polys.as_ptr(), arity.as_ptr(), arity.len() as u32, params.proof_of_work_bits,
+                              params.num_query_rounds, challenger, buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
+    })?;
+    buf.truncate(len);
+    Ok(buf)
+}
+/// `verify_fri_proof` (fri/verifier.rs:67-250) on the host: Ok(true), Ok(false) when a check fails, Err for malformed bytes or
+/// arguments.  `openings`: every batch's values laid end to end ([sum of batch sizes][D]); `initial_caps`: every oracle's cap laid
+/// end to end; `challenger`: the transcript after the openings were observed (not advanced).
+pub fn fri_verify<W: Copy + Default>(instance: &FriInstance<W>, openings: &[W], initial_caps: &[W], params: &FriParams,
+                                     challenger: &gb_challenger_state, fri_proof: &[u8]) -> Result<bool, GpuError> {
+    let (d, h) = if std::mem::size_of::<W>() == 8 { (2, 4) } else { (4, 8) };
+    let (sizes, polys) = instance.lists()?;
+    need("openings", openings.len(), polys.len() / 2 * d)?;
+    need("initial_caps", initial_caps.len(), instance.oracles.len() * (h << params.cap_height))?;
+    let num_polys: Vec<u32> = instance.oracles.iter().map(|o| o.0 as u32).collect();
+    let blinding: Vec<u32> = instance.oracles.iter().map(|o| o.1 as u32).collect();
+    let arity: Vec<u32> = params.reduction_arity_bits.iter().map(|&b| b as u32).collect();
+    let st = unsafe {
+        gb_fri_verify(ptr::null_mut(), field_tag::<W>(), params.degree_bits, params.rate_bits, params.cap_height, params.hiding as u32,
+                      num_polys.as_ptr(), blinding.as_ptr(), num_polys.len() as u32, instance.points.as_ptr() as *const c_void,
+                      sizes.as_ptr(), sizes.len() as u32, polys.as_ptr(), openings.as_ptr() as *const c_void,
+                      initial_caps.as_ptr() as *const c_void, arity.as_ptr(), arity.len() as u32, params.proof_of_work_bits,
+                      params.num_query_rounds, challenger, fri_proof.as_ptr() as *const c_void, fri_proof.len())
+    };
+    if st == GB_ERR_VERIFY {
+        return Ok(false);
+    }
+    check(ptr::null(), st)?;
+    Ok(true)
 }
 
 /// What `CircuitBuilder::build()` leaves for the prover, resident on the GPU (circuit_builder.rs:1214-1312).

@@ -3,6 +3,7 @@
 csrc/      hand-written HIP kernels + the C ABI declared in include/goldibear_gpu.h
 native     ctypes binding of that ABI (no fallback: raises if the library is missing)
 polynomial_batch  host-side mirror of PolynomialBatch / MerkleTree (fri/oracle.rs, hash/merkle_tree.rs)
+fri         the polynomial commitment scheme on its own: prove_openings on any FriInstanceInfo, verify_fri_proof (fri/oracle.rs, fri/verifier.rs)
 polynomial  the transforms on their own: fft / ifft / coset_fft / coset_ifft / lde / lde_onto_coset (field/src/polynomial/mod.rs)
 """
 from .native import GB_BABYBEAR, GB_GOLDILOCKS, GoldibearError, ShapeError  # noqa: F401
@@ -10,3 +11,5 @@ from .native import PermArgZeroError, TooManyPermArgFailuresError, VerifyError  
 from .polynomial_batch import GpuContext, MerkleTree, PolynomialBatch  # noqa: F401
 from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  # noqa: F401
 from .prover import CircuitData, VerifierCircuitData  # noqa: F401
+from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
+from .fri import prove_openings, verify_fri_proof  # noqa: F401

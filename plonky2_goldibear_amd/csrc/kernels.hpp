@@ -288,6 +288,21 @@ template <class F>
 void eval_columns(const EvalJobs<F>& jobs, u32 njobs, size_t n, typename F::E* partial_tmp, typename F::E* out, hipStream_t st);
 template <class F>
 void reduce_polys(const PolyGroups<F>& g, size_t n, const typename F::E* apow, typename F::E* comp, hipStream_t st);
+// reduce_polys_base for up to REDUCE_SLOTS batches of any FriInstanceInfo at once: comp[s][t] = sum_j alpha^j f_{s,j}[t].  The
+// batches' polynomial lists arrive as a table of runs in DEVICE memory (written by a stream-ordered copy before the launch):
+// a run is `ncols` consecutive columns base + k n of one oracle; column k has power index apow0[s] + k in slot s, or is not in
+// slot s at all (REDUCE_ABSENT).  A column is read once per run, whichever slots it is in.
+static constexpr u32 REDUCE_SLOTS = 4, REDUCE_ABSENT = 0xFFFFFFFFu;
+template <class F>
+struct ReduceRun {
+    const typename F::T* base;
+    u32 ncols;
+    u32 apow0[REDUCE_SLOTS];
+};
+// apow: alpha^0 .. alpha^(longest batch - 1); comp: [nslots][n]
+template <class F>
+void reduce_batches(const ReduceRun<F>* runs_dev, u32 nruns, u32 nslots, size_t n, const typename F::E* apow, typename F::E* comp,
+                    hipStream_t st);
 template <class F>
 void divide_by_linear_accumulate(const typename F::E* comp, size_t n, const ExtPowTab<F>& z, const ExtPowTab<F>& zinv,
                                  typename F::E shift, int first, typename F::E* sloc_tmp, typename F::E* totals_tmp,

@@ -457,6 +457,73 @@ __global__ __launch_bounds__(256) void k_reduce_polys(PolyGroups<F> g, size_t n,
     comp[t] = acc;
 }
 
+// The same sum for up to REDUCE_SLOTS batches of any FriInstanceInfo in one pass over the columns (fri/oracle.rs:208-216 for
+// every batch of the pass): comp[s][t] = sum_j alpha^j f_{s,j}[t].  `runs` lists the referenced columns (kernels.hpp); the run
+// index, the run's fields and the alpha powers are the same in every lane, so they are read through const __restrict__ pointers
+// - scalar loads, scalar branches on the slot membership - and only the columns themselves go through the vector memory path:
+// 16 bytes per lane and load (two Goldilocks / four BabyBear coefficients), four columns in flight before the first product.
+template <class F>
+struct alignas(16) ColVec {
+    static constexpr u32 V = 16 / sizeof(typename F::T);
+    typename F::T v[V];
+};
+template <class F>
+__global__ __launch_bounds__(256) void k_reduce_batches(const ReduceRun<F>* __restrict__ runs, u32 nruns, u32 nslots, size_t n,
+                                                        const typename F::E* __restrict__ apow, typename F::E* __restrict__ comp) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 V = ColVec<F>::V;
+    const bool whole = n % V == 0;   // every column then starts on a 16-byte boundary and no vector straddles its end
+    for (size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * V; t0 < n; t0 += (size_t)gridDim.x * 256 * V) {
+        E acc[REDUCE_SLOTS][V];
+#pragma unroll
+        for (u32 s = 0; s < REDUCE_SLOTS; s++)
+#pragma unroll
+            for (u32 e = 0; e < V; e++) acc[s][e] = F::ezero();
+        auto load = [&](const T* col) {
+            ColVec<F> c;
+            if (whole) {   // (the pointer comes out of the table: say that it is global memory, or the load is a flat one)
+                typedef u32 v4u __attribute__((ext_vector_type(4)));
+                const v4u w = *(const __attribute__((address_space(1))) v4u*)(col + t0);
+                __builtin_memcpy(&c, &w, sizeof c);
+            } else {   // n < V: one lane, element by element
+#pragma unroll
+                for (u32 e = 0; e < V; e++) c.v[e] = t0 + e < n ? col[t0 + e] : F::zero();
+            }
+            return c;
+        };
+        auto mac = [&](const ReduceRun<F>& R, u32 k, const ColVec<F>& c) {
+#pragma unroll
+            for (u32 s = 0; s < REDUCE_SLOTS; s++)
+                if (R.apow0[s] != REDUCE_ABSENT) {
+                    const E a = apow[R.apow0[s] + k];
+#pragma unroll
+                    for (u32 e = 0; e < V; e++) acc[s][e] = F::eadd(acc[s][e], F::escale(a, c.v[e]));
+                }
+        };
+        for (u32 r = 0; r < nruns; r++) {
+            const ReduceRun<F> R = runs[r];
+            u32 k = 0;
+            for (; k + 4 <= R.ncols; k += 4) {
+                const T* col = R.base + (size_t)k * n;
+                const ColVec<F> c0 = load(col), c1 = load(col + n), c2 = load(col + 2 * n), c3 = load(col + 3 * n);
+                mac(R, k, c0);
+                mac(R, k + 1, c1);
+                mac(R, k + 2, c2);
+                mac(R, k + 3, c3);
+            }
+            for (; k < R.ncols; k++) mac(R, k, load(R.base + (size_t)k * n));
+        }
+#pragma unroll
+        for (u32 s = 0; s < REDUCE_SLOTS; s++)
+            if (s < nslots) {
+#pragma unroll
+                for (u32 e = 0; e < V; e++)
+                    if (t0 + e < n) comp[(size_t)s * n + t0 + e] = acc[s][e];
+            }
+    }
+}
+
 // divide_by_linear (polynomial/division.rs:75-88): q[t] = sum_{u > t} c_u z^(u-t-1) = z^-(t+1) * S_{t+1},
 // S_t = sum_{u >= t} c_u z^u.  Step 1: w_u = c_u z^u and block-local suffix sums (blocks of 1024).
 template <class F>
@@ -841,6 +908,15 @@ void reduce_polys(const PolyGroups<F>& g, size_t n, const typename F::E* apow, t
 }
 
 template <class F>
+void reduce_batches(const ReduceRun<F>* runs_dev, u32 nruns, u32 nslots, size_t n, const typename F::E* apow, typename F::E* comp,
+                    hipStream_t st) {
+    // a memory-bound pass: at most 2048 workgroups, each striding over the rows (2048 x 256 lanes x 16 bytes = one 2^20-row
+    // Goldilocks column per sweep)
+    const u32 blocks = std::min<u32>(nblk(nblk(n, ColVec<F>::V), 256), 2048u);
+    hipLaunchKernelGGL(k_reduce_batches<F>, dim3(blocks), dim3(256), 0, st, runs_dev, nruns, nslots, n, apow, comp);
+}
+
+template <class F>
 void divide_by_linear_accumulate(const typename F::E* comp, size_t n, const ExtPowTab<F>& z, const ExtPowTab<F>& zinv,
                                  typename F::E shift, int first, typename F::E* sloc_tmp, typename F::E* totals_tmp,
                                  typename F::E* final_poly, hipStream_t st) {
@@ -898,6 +974,7 @@ void query_gather(const QueryJobs<F>& jobs, u32 njobs, const u64* idx_host, cons
     template void ext_pow_tables<F>(const ExtPowTables<F>&, u32, size_t, hipStream_t);                                              \
     template void eval_columns<F>(const EvalJobs<F>&, u32, size_t, F::E*, F::E*, hipStream_t);                                      \
     template void reduce_polys<F>(const PolyGroups<F>&, size_t, const F::E*, F::E*, hipStream_t);                                   \
+    template void reduce_batches<F>(const ReduceRun<F>*, u32, u32, size_t, const F::E*, F::E*, hipStream_t);                        \
     template void divide_by_linear_accumulate<F>(const F::E*, size_t, const ExtPowTab<F>&, const ExtPowTab<F>&, F::E, int, F::E*,   \
                                                  F::E*, F::E*, hipStream_t);                                                        \
     template void ext_split<F>(const F::E*, size_t, F::T*, hipStream_t);                                                            \

@@ -6,6 +6,8 @@
 // form of an element (canonical u64 / Montgomery u32); the transcript and the proof bytes use canonical words
 // of the same width.
 
+#include <array>
+
 #include "gates.hpp"
 
 struct gb_circuit {
@@ -48,6 +50,24 @@ struct gb_circuit {
     virtual void verifier_data(void* cap_out, void* digest_out) = 0;
 };
 
+// A FriParams.reduction_arity_bits list for oracles of this shape: what gb_circuit_set_fri_reduction_arity_bits,
+// gb_fri_prove_openings and gb_fri_verify accept (the empty list included)
+static gb_status check_fri_reduction_arity_bits(gb_ctx* ctx, u32 degree_bits, u32 rate_bits, u32 cap_height, const uint32_t* arity_bits,
+                                                uint32_t num_layers) {
+    if (num_layers && !arity_bits) return fail(ctx, GB_ERR_INVALID, "null arity_bits");
+    if (num_layers > GB_MAX_FRI_LAYERS) return fail(ctx, GB_ERR_INVALID, "more than GB_MAX_FRI_LAYERS FRI reduction layers");
+    const u32 max_ab = 8u;   // a FRI leaf is 2^arity_bits extension elements; the proof format's u8 counts and the verifier stop at 2^8
+    u32 db = degree_bits;
+    for (u32 i = 0; i < num_layers; i++) {
+        const u32 ab = arity_bits[i];
+        if (ab == 0 || ab > max_ab) return fail(ctx, GB_ERR_INVALID, "FRI reduction arity outside the supported range");
+        if (ab > db) return fail(ctx, GB_ERR_INVALID, "FRI reduction arities sum past degree_bits");
+        if (db + rate_bits < cap_height + ab)
+            return fail(ctx, GB_ERR_INVALID, "cap_height should be at most log2(leaves.len()) in a FRI layer (merkle_tree.rs:154-157)");
+        db -= ab;
+    }
+    return GB_OK;
+}
 static gb_status need_arity_list(gb_circuit* c) {
     if (c && c->arity_pending)
         return fail(c->ctx, GB_ERR_INVALID, "no FRI reduction list: ConstantArityBits(arity_bits, final_poly_bits) is not defined for this circuit "
@@ -477,65 +497,117 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     return GB_OK;
 }
 
-// PolynomialBatch::prove_openings (fri/oracle.rs:187-246) for the PLONK instance get_fri_instance(zeta) (plonk/circuit_data.rs:
-// 438-520: every polynomial of the four oracles opened at zeta, the Zs also at g zeta), then fri_proof (fri/prover.rs:29-81):
-// commit phase, proof of work (minimum nonce), query rounds.  `ch` is the Challenger after observe_openings; it leaves in the
-// state the reference's leaves in.  Appends the FriProof bytes (util/serialization/mod.rs:1679-1695) to `ob`.
+// ---------------------------------------------------------------------------------------------- prove_openings
+// A FriInstanceInfo (fri/structure.rs) compiled for k_reduce_batches: the batches in passes of at most REDUCE_SLOTS consecutive
+// ones, each pass a list of runs.  A run is a maximal stretch of consecutive polynomial_index in one oracle whose columns are in
+// the same slots of the pass with consecutive powers in each - what FriPolynomialInfo::from_range yields.  Lists in any other order
+// fall apart into runs of one column, and a polynomial listed twice in one batch gets a run per mention: nothing below depends
+// on runs being merged.
+struct FriPlan {
+    struct Run {
+        u32 oracle, col, ncols;
+        u32 apow0[gbk::REDUCE_SLOTS];
+    };
+    struct Pass {
+        u32 batch0, nslots, run0, nruns;
+    };
+    std::vector<u32> batch_sizes;
+    std::vector<Pass> passes;
+    std::vector<Run> runs;
+    u32 longest = 0;   // the longest batch: alpha^0 .. alpha^(longest - 1) are needed
+};
+// polynomials: [sum of batch_sizes][2] = (oracle_index, polynomial_index), batch after batch (validated by the caller)
+static FriPlan compile_fri_instance(const u32* batch_sizes, u32 num_batches, const u32* polynomials) {
+    constexpr u32 S = gbk::REDUCE_SLOTS, ABSENT = gbk::REDUCE_ABSENT;
+    FriPlan plan;
+    plan.batch_sizes.assign(batch_sizes, batch_sizes + num_batches);
+    size_t at = 0;
+    for (u32 b0 = 0; b0 < num_batches; b0 += S) {
+        const u32 ns = std::min(S, num_batches - b0);
+        // (oracle, polynomial) -> one cell per mention that cannot share a read: its power index in every slot
+        std::map<std::pair<u32, u32>, std::vector<std::array<u32, S>>> cells;
+        for (u32 s = 0; s < ns; s++) {
+            plan.longest = std::max(plan.longest, batch_sizes[b0 + s]);
+            for (u32 j = 0; j < batch_sizes[b0 + s]; j++, at++) {
+                auto& v = cells[{polynomials[2 * at], polynomials[2 * at + 1]}];
+                size_t i = 0;
+                while (i < v.size() && v[i][s] != ABSENT) i++;
+                if (i == v.size()) { v.emplace_back(); v.back().fill(ABSENT); }
+                v[i][s] = j;
+            }
+        }
+        FriPlan::Pass pass{b0, ns, (u32)plan.runs.size(), 0};
+        for (const auto& kv : cells)
+            for (size_t i = 0; i < kv.second.size(); i++) {
+                const auto& pw = kv.second[i];
+                if (i == 0 && plan.runs.size() > pass.run0) {   // does it continue the run before it?
+                    FriPlan::Run& r = plan.runs.back();
+                    bool joins = r.oracle == kv.first.first && r.col + r.ncols == kv.first.second;
+                    for (u32 s = 0; s < S && joins; s++)
+                        joins = r.apow0[s] == ABSENT ? pw[s] == ABSENT : pw[s] == r.apow0[s] + r.ncols;
+                    if (joins) { r.ncols++; continue; }
+                }
+                FriPlan::Run r{kv.first.first, kv.first.second, 1, {}};
+                std::copy(pw.begin(), pw.end(), r.apow0);
+                plan.runs.push_back(r);
+            }
+        pass.nruns = (u32)plan.runs.size() - pass.run0;
+        plan.passes.push_back(pass);
+    }
+    return plan;
+}
+// the table k_reduce_batches reads: the plan's runs over these oracles' coefficient blocks
 template <class F>
-gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb_batch* zs, gb_batch* quot, typename F::E zeta,
-                               typename Host<F>::Challenger& ch, Bytes& ob) {
+std::vector<gbk::ReduceRun<F>> fri_run_table(const FriPlan& plan, gb_batch* const* oracles) {
+    typedef typename F::T T;
+    std::vector<gbk::ReduceRun<F>> t(plan.runs.size());
+    for (size_t i = 0; i < t.size(); i++) {
+        const FriPlan::Run& r = plan.runs[i];
+        t[i].base = (const T*)oracles[r.oracle]->coeffs + ((size_t)r.col << oracles[r.oracle]->log_n);
+        t[i].ncols = r.ncols;
+        std::copy(r.apow0, r.apow0 + gbk::REDUCE_SLOTS, t[i].apow0);
+    }
+    return t;
+}
+
+struct FriShape {   // the oracles' common shape and what fri_proof needs of FriParams
+    u32 degree_bits, rate_bits, cap_height, proof_of_work_bits, num_query_rounds;
+    const std::vector<uint32_t>* reduction_arity_bits;
+};
+
+template <class F>
+typename F::E get_ext_challenge(typename Host<F>::Challenger& chl) {  // get_extension_challenge: D base challenges -> device form
+    typename F::E e = F::ezero();
+    for (u32 k = 0; k < F::D; k++) F::set_coord(e, k, F::enc(chl.get()));
+    return e;
+}
+
+// The rest of prove_openings once final_poly = sum over the batches of alpha-shifted quotients is there (fri/oracle.rs:226-246):
+// its lde + coset_fft, then fri_proof (fri/prover.rs:29-81): commit phase, proof of work (minimum nonce), query rounds over every
+// oracle's tree.  opening_scope: the caller's "compute opening proofs" scope, open since its reduction.  Appends the FriProof bytes (util/serialization/mod.rs:1679-1695) to `ob`; `ch` leaves as the reference's does.
+template <class F>
+gb_status fri_proof_of_final_poly(gb_ctx* ctx, TmpAlloc& tmp, const FriShape& fs, gb_batch* const* oracles, u32 num_oracles,
+                                  const typename F::E* final_poly, std::unique_ptr<Scope>& opening_scope,
+                                  typename Host<F>::Challenger& ch, Bytes& ob) {
     typedef typename F::T T;
     typedef typename F::E E;
     typedef Host<F> HF;
     constexpr u32 D = F::D, H = F::H;
-    gb_ctx* ctx = c->ctx;
-    const gb_circuit_config& cfg = c->cfg;
-    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height;
-    const u32 lgN = lg + r;
+    const u32 lg = fs.degree_bits, r = fs.rate_bits, capH = fs.cap_height, lgN = lg + r;
     const size_t n = (size_t)1 << lg, N = n << r;
-    const u32 nr = cfg.num_routed_wires, nw = cfg.num_wires, qdf = cfg.max_quotient_degree_factor;
-    const u32 nchunks = (nr + qdf - 1) / qdf, num_prods = nchunks - 1;
-    const size_t ncs = c->cs->ncols, nzs = (size_t)nch * (1 + num_prods), nq = (size_t)nch * qdf;
     const size_t cap_elems = (size_t)H << capH, es = sizeof(T);
+    const std::vector<uint32_t>& arity_bits = *fs.reduction_arity_bits;
     hipStream_t st = ctx->stream;
     gb_status s;
-    auto get_ext = [](typename HF::Challenger& chl) {  // get_extension_challenge: D base challenges -> device form
-        E e = F::ezero();
-        for (u32 k = 0; k < D; k++) F::set_coord(e, k, F::enc(chl.get()));
-        return e;
-    };
-    const E zeta_next = F::escale(zeta, F::two_adic_generator(lg));
-    gbk::ExtPowTab<F> zt, zt_inv, znt, znt_inv;
-    const E fri_alpha = get_ext(ch);
-    E* apow_dev = nullptr;   // alpha^0 .. alpha^(total_polys - 1)
-    {
-        const E pts[4] = {zeta, F::einv(zeta), zeta_next, F::einv(zeta_next)};
-        const size_t ns[4] = {n, n + 1, n, n + 1};
-        gbk::ExtPowTab<F>* tabs4[4] = {&zt, &zt_inv, &znt, &znt_inv};
-        if ((s = make_ext_powtabs<F>(ctx, tmp, 4, pts, ns, tabs4, &fri_alpha, ncs + nw + nzs + nq, &apow_dev))) return s;
-    }
-    const u32 nlayers = (u32)c->arity_bits.size();
+    auto get_ext = get_ext_challenge<F>;
+    const u32 nlayers = (u32)arity_bits.size();
     std::vector<T*> layer_vals(nlayers + 1, nullptr), layer_levels(nlayers, nullptr);
     std::vector<u32> layer_lgN(nlayers + 1, 0);
     std::vector<T> fri_caps, final_coeffs;
     u64* pow_res = nullptr;
-    {
-        Scope sc(ctx, "compute opening proofs");
-        E* comp = tmp.get<E>(n);
-        E* sloc = tmp.get<E>(n);
-        E* dtot = tmp.get<E>(std::max<size_t>(1024, (n + 1023) / 1024));   // one suffix total per block of 1024 coefficients (round 6: 1024 of
-                                                                            // them overflowed into final_poly from 2^21 rows up - found by the byte comparison)
-        E* final_poly = tmp.get<E>(n);
+    {   // still inside the caller's "compute opening proofs" scope, which ends where the final polynomial has been observed
         T* fcols = tmp.get<T>(D * n);
-        if (!comp || !sloc || !dtot || !final_poly || !fcols) return fail(ctx, GB_ERR_OOM, "prove_openings workspace");
-        gbk::PolyGroups<F> g0{{(const T*)c->cs->coeffs, (const T*)wires->coeffs, (const T*)zs->coeffs, (const T*)quot->coeffs},
-                              {(u32)ncs, nw, (u32)nzs, (u32)nq}, 4};
-        gbk::PolyGroups<F> g1{{(const T*)zs->coeffs, nullptr, nullptr, nullptr}, {nch, 0, 0, 0}, 1};
-        gbk::reduce_polys<F>(g0, n, apow_dev, comp, st);
-        gbk::divide_by_linear_accumulate<F>(comp, n, zt, zt_inv, F::efrom(F::one()), 1, sloc, dtot, final_poly, st);
-        gbk::reduce_polys<F>(g1, n, apow_dev, comp, st);
-        const E sh = gbk::epow<F>(fri_alpha, nch);  // alpha.shift_poly: count of the second batch
-        gbk::divide_by_linear_accumulate<F>(comp, n, znt, znt_inv, sh, 0, sloc, dtot, final_poly, st);
+        if (!fcols) return fail(ctx, GB_ERR_OOM, "prove_openings workspace");
         gbk::ext_split<F>(final_poly, n, fcols, st);
 
         // lde + coset_fft of the final polynomial, coordinate-wise, in leaf order (oracle.rs:226-231)
@@ -554,7 +626,7 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
             layer_vals[li] = vals;
             layer_lgN[li] = cur_lg + r;
             // fri_committed_trees (fri/prover.rs:83-133)
-            const u32 ab = c->arity_bits[li];
+            const u32 ab = arity_bits[li];
             const u32 tree_lg = cur_lg + r - ab;
             const u64 L = (u64)1 << tree_lg;
             T* levels = tmp.get<T>((size_t)(2 * H) << tree_lg);
@@ -586,6 +658,7 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
         for (size_t t = 0; t < fl; t++)
             for (u32 k = 0; k < D; k++) final_coeffs[D * t + k] = (T)F::dec(fc[k * fl + t]);
         ch.observe(final_coeffs.data(), final_coeffs.size());
+        opening_scope.reset();
     }
 
     // ---- fri_proof_of_work (fri/prover.rs:136-188): the minimum nonce
@@ -596,7 +669,7 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
         std::memcpy(ps.s, ch.state, sizeof ps.s);
         for (int i = 0; i < ch.nin; i++) ps.s[i] = ch.in[i];
         ps.pos = (u32)ch.nin;
-        const u32 min_lz = cfg.proof_of_work_bits + (64 - F::ORDER_BITS);  // fri/prover.rs:147
+        const u32 min_lz = fs.proof_of_work_bits + (64 - F::ORDER_BITS);  // fri/prover.rs:147
         u64 found = 0;
         if ((s = pow_search<F>(ctx, pow_res, ps, min_lz, &found))) return s;
         pow_witness = found;
@@ -608,12 +681,11 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     // ---- query rounds (fri/prover.rs:190-255)
     {
         Scope sc(ctx, "fri query rounds");
-        const u32 nqr = cfg.num_query_rounds;
+        const u32 nqr = fs.num_query_rounds;
         std::vector<u64> idx(nqr);
         for (auto& x : idx) x = (u64)ch.get() % N;
         u64* idx_dev = nullptr;
         if (nqr > gbk::QUERY_IDX_INLINE) if ((s = upload_tmp(ctx, tmp, idx, &idx_dev))) return s;
-        gb_batch* oracles[4] = {c->cs, wires, zs, quot};
         const u32 layers0 = lgN - capH;
         // every opened row and path of the proof: one job per tree, one launch per twelve jobs, one buffer, one read-back
         std::vector<gbk::QueryJob<F>> jobs;
@@ -623,11 +695,11 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
             total += (size_t)nqr * (j.width + (size_t)j.layers * H);
             jobs.push_back(j);
         };
-        for (int o = 0; o < 4; o++)
+        for (u32 o = 0; o < num_oracles; o++)
             add_job(gbk::QueryJob<F>{(const T*)oracles[o]->lde, (const T*)oracles[o]->levels, (u64)N, 0, (u32)(oracles[o]->ncols + oracles[o]->nsalt),
                                      lgN, layers0, 0, 0, 0});
         for (u32 li = 0, shift = 0; li < nlayers; li++) {
-            const u32 ab = c->arity_bits[li];
+            const u32 ab = arity_bits[li];
             shift += ab;
             const u32 tree_lg = layer_lgN[li] - ab;
             add_job(gbk::QueryJob<F>{layer_vals[li], layer_levels[li], (u64)1 << layer_lgN[li], 0, (u32)(D << ab), tree_lg, tree_lg - capH, shift, ab, 1});
@@ -661,6 +733,113 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     }
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
     return GB_OK;
+}
+
+
+// PolynomialBatch::prove_openings (fri/oracle.rs:187-246) on a compiled instance: oracles[num_oracles] with the shape `fs`, batch b
+// opened at points[b].  One k_reduce_batches pass per REDUCE_SLOTS batches, then per batch, in instance order, divide_by_linear and
+// alpha.shift_poly(final_poly) += quotient (:216-223).  The instance's run table is made and uploaded here, for the call.
+template <class F>
+gb_status fri_prove_instance(gb_ctx* ctx, TmpAlloc& tmp, const FriShape& fs, const FriPlan& plan, gb_batch* const* oracles, u32 num_oracles, const typename F::E* points,
+                             typename Host<F>::Challenger& ch, Bytes& ob) {
+    typedef typename F::E E;
+    const size_t n = (size_t)1 << fs.degree_bits;
+    const u32 nb = (u32)plan.batch_sizes.size();
+    hipStream_t st = ctx->stream;
+    gb_status s;
+    const E fri_alpha = get_ext_challenge<F>(ch);
+    // every point's powers and those of its inverse (the division runs on z^-1), EXT_POW_JOBS tables per launch
+    std::vector<gbk::ExtPowTab<F>> ztab(2 * (size_t)nb);
+    E* apow_dev = nullptr;   // alpha^0 .. alpha^(longest batch - 1)
+    {
+        std::vector<E> pts(2 * (size_t)nb);
+        std::vector<size_t> ns(2 * (size_t)nb);
+        std::vector<gbk::ExtPowTab<F>*> out(2 * (size_t)nb);
+        for (u32 b = 0; b < nb; b++) {
+            pts[2 * b] = points[b]; pts[2 * b + 1] = F::einv(points[b]);
+            ns[2 * b] = n; ns[2 * b + 1] = n + 1;
+            out[2 * b] = &ztab[2 * b]; out[2 * b + 1] = &ztab[2 * b + 1];
+        }
+        for (size_t i = 0; i < pts.size();) {   // (the first launch also carries alpha's plain list)
+            const u32 cnt = (u32)std::min<size_t>(pts.size() - i, gbk::EXT_POW_JOBS - (i ? 0 : 1));
+            if (i == 0) s = make_ext_powtabs<F>(ctx, tmp, cnt, pts.data(), ns.data(), out.data(), &fri_alpha, plan.longest, &apow_dev);
+            else s = make_ext_powtabs<F>(ctx, tmp, cnt, pts.data() + i, ns.data() + i, out.data() + i);
+            if (s) return s;
+            i += cnt;
+        }
+    }
+    E* final_poly = tmp.get<E>(n);
+    std::unique_ptr<Scope> opening_scope(new Scope(ctx, "compute opening proofs"));
+    {
+        E* comp = tmp.get<E>(gbk::REDUCE_SLOTS * n);
+        E* sloc = tmp.get<E>(n);
+        E* dtot = tmp.get<E>(std::max<size_t>(1024, (n + 1023) / 1024));   // one suffix total per block of 1024 coefficients
+        if (!comp || !sloc || !dtot || !final_poly) return fail(ctx, GB_ERR_OOM, "prove_openings workspace");
+        gbk::ReduceRun<F>* runs_dev = nullptr;
+        if ((s = upload_tmp(ctx, tmp, fri_run_table<F>(plan, oracles), &runs_dev))) return s;
+        for (const FriPlan::Pass& pass : plan.passes) {
+            gbk::reduce_batches<F>(runs_dev + pass.run0, pass.nruns, pass.nslots, n, apow_dev, comp, st);
+            for (u32 k = 0; k < pass.nslots; k++) {
+                const u32 b = pass.batch0 + k;
+                const E sh = gbk::epow<F>(fri_alpha, plan.batch_sizes[b]);   // alpha.shift_poly: the count of the batch just reduced
+                gbk::divide_by_linear_accumulate<F>(comp + (size_t)k * n, n, ztab[2 * b], ztab[2 * b + 1], sh, b == 0, sloc, dtot, final_poly, st);
+            }
+        }
+    }
+    return fri_proof_of_final_poly<F>(ctx, tmp, fs, oracles, num_oracles, final_poly, opening_scope, ch, ob);
+}
+
+// PolynomialBatch::prove_openings (fri/oracle.rs:187-246) for the PLONK instance get_fri_instance(zeta) (plonk/circuit_data.rs:
+// 438-520: every polynomial of the four oracles opened at zeta, the Zs also at g zeta), then fri_proof (fri/prover.rs:29-81):
+// commit phase, proof of work (minimum nonce), query rounds.  `ch` is the Challenger after observe_openings; it leaves in the
+// state the reference's leaves in.  Appends the FriProof bytes (util/serialization/mod.rs:1679-1695) to `ob`.  Its two batches
+// are fixed, so they are reduced by the two launches of k_reduce_polys; everything behind the final polynomial is the routine
+// fri_prove_instance ends in as well.
+template <class F>
+gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb_batch* zs, gb_batch* quot, typename F::E zeta,
+                               typename Host<F>::Challenger& ch, Bytes& ob) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    gb_ctx* ctx = c->ctx;
+    const gb_circuit_config& cfg = c->cfg;
+    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height;
+    const size_t n = (size_t)1 << lg;
+    const u32 nr = cfg.num_routed_wires, nw = cfg.num_wires, qdf = cfg.max_quotient_degree_factor;
+    const u32 nchunks = (nr + qdf - 1) / qdf, num_prods = nchunks - 1;
+    const size_t ncs = c->cs->ncols, nzs = (size_t)nch * (1 + num_prods), nq = (size_t)nch * qdf;
+    hipStream_t st = ctx->stream;
+    gb_status s;
+    auto get_ext = get_ext_challenge<F>;
+    const E zeta_next = F::escale(zeta, F::two_adic_generator(lg));
+    gbk::ExtPowTab<F> zt, zt_inv, znt, znt_inv;
+    const E fri_alpha = get_ext(ch);
+    E* apow_dev = nullptr;   // alpha^0 .. alpha^(total_polys - 1)
+    {
+        const E pts[4] = {zeta, F::einv(zeta), zeta_next, F::einv(zeta_next)};
+        const size_t ns[4] = {n, n + 1, n, n + 1};
+        gbk::ExtPowTab<F>* tabs4[4] = {&zt, &zt_inv, &znt, &znt_inv};
+        if ((s = make_ext_powtabs<F>(ctx, tmp, 4, pts, ns, tabs4, &fri_alpha, ncs + nw + nzs + nq, &apow_dev))) return s;
+    }
+    E* final_poly = tmp.get<E>(n);
+    std::unique_ptr<Scope> opening_scope(new Scope(ctx, "compute opening proofs"));
+    {
+        E* comp = tmp.get<E>(n);
+        E* sloc = tmp.get<E>(n);
+        E* dtot = tmp.get<E>(std::max<size_t>(1024, (n + 1023) / 1024));   // one suffix total per block of 1024 coefficients (round 6: 1024 of
+                                                                            // them overflowed into final_poly from 2^21 rows up - found by the byte comparison)
+        if (!comp || !sloc || !dtot || !final_poly) return fail(ctx, GB_ERR_OOM, "prove_openings workspace");
+        gbk::PolyGroups<F> g0{{(const T*)c->cs->coeffs, (const T*)wires->coeffs, (const T*)zs->coeffs, (const T*)quot->coeffs},
+                              {(u32)ncs, nw, (u32)nzs, (u32)nq}, 4};
+        gbk::PolyGroups<F> g1{{(const T*)zs->coeffs, nullptr, nullptr, nullptr}, {nch, 0, 0, 0}, 1};
+        gbk::reduce_polys<F>(g0, n, apow_dev, comp, st);
+        gbk::divide_by_linear_accumulate<F>(comp, n, zt, zt_inv, F::efrom(F::one()), 1, sloc, dtot, final_poly, st);
+        gbk::reduce_polys<F>(g1, n, apow_dev, comp, st);
+        const E sh = gbk::epow<F>(fri_alpha, nch);  // alpha.shift_poly: count of the second batch
+        gbk::divide_by_linear_accumulate<F>(comp, n, znt, znt_inv, sh, 0, sloc, dtot, final_poly, st);
+    }
+    gb_batch* oracles[4] = {c->cs, wires, zs, quot};
+    const FriShape fs{lg, r, capH, cfg.proof_of_work_bits, cfg.num_query_rounds, &c->arity_bits};
+    return fri_proof_of_final_poly<F>(ctx, tmp, fs, oracles, 4, final_poly, opening_scope, ch, ob);
 }
 
 // ---------------------------------------------------------------------------------------------- prove()
@@ -1100,23 +1279,12 @@ static gb_status abi_quotient_polys(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     return GB_OK;
 }
 
+// Challenger<F, H> by value (gb_challenger_state) <-> the host transcript
 template <class F>
-static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs, gb_batch* quot, const void* zeta_canon,
-                                    gb_challenger_state* chs, void* out, size_t out_cap, size_t* out_len) {
+static gb_status challenger_from_state(gb_ctx* ctx, const gb_challenger_state* chs, typename Host<F>::Challenger& ch) {
     typedef typename F::T T;
-    typedef typename F::E E;
-    typedef Host<F> HF;
     constexpr u32 W = F::SPONGE_W;  // SPONGE_WIDTH of the configuration's hasher
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const gb_circuit_config& cfg = c->cfg;
-    const u32 nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
-    const size_t nzs = (size_t)nch * ((nr + qdf - 1) / qdf), nq = (size_t)nch * qdf;
-    if (gb_status s = check_stage_batch<F>(c, wires, cfg.num_wires, "wires")) return s;
-    if (gb_status s = check_stage_batch<F>(c, zs, nzs, "zs_partial_products")) return s;
-    if (gb_status s = check_stage_batch<F>(c, quot, nq, "quotient")) return s;
     if (chs->input_len >= 8 || chs->output_len > 8) return fail(ctx, GB_ERR_INVALID, "challenger buffers hold at most SPONGE_RATE elements");
-    typename HF::Challenger ch;
     for (u32 i = 0; i < W; i++) {
         if (chs->sponge_state[i] >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical challenger state");
         ch.state[i] = (T)chs->sponge_state[i];
@@ -1128,6 +1296,34 @@ static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     ch.nout = (int)chs->output_len;
     for (int i = 0; i < ch.nin; i++) ch.in[i] = (T)chs->input_buffer[i];
     for (int i = 0; i < ch.nout; i++) ch.out[i] = (T)chs->output_buffer[i];
+    return GB_OK;
+}
+template <class F>
+static void challenger_to_state(const typename Host<F>::Challenger& ch, gb_challenger_state* chs) {
+    std::memset(chs, 0, sizeof *chs);
+    for (u32 i = 0; i < F::SPONGE_W; i++) chs->sponge_state[i] = ch.state[i];
+    chs->input_len = (uint32_t)ch.nin;
+    chs->output_len = (uint32_t)ch.nout;
+    for (int i = 0; i < ch.nin; i++) chs->input_buffer[i] = ch.in[i];
+    for (int i = 0; i < ch.nout; i++) chs->output_buffer[i] = ch.out[i];
+}
+
+template <class F>
+static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs, gb_batch* quot, const void* zeta_canon,
+                                    gb_challenger_state* chs, void* out, size_t out_cap, size_t* out_len) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    typedef Host<F> HF;
+    gb_ctx* ctx = c->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const gb_circuit_config& cfg = c->cfg;
+    const u32 nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
+    const size_t nzs = (size_t)nch * ((nr + qdf - 1) / qdf), nq = (size_t)nch * qdf;
+    if (gb_status s = check_stage_batch<F>(c, wires, cfg.num_wires, "wires")) return s;
+    if (gb_status s = check_stage_batch<F>(c, zs, nzs, "zs_partial_products")) return s;
+    if (gb_status s = check_stage_batch<F>(c, quot, nq, "quotient")) return s;
+    typename HF::Challenger ch;
+    if (gb_status s = challenger_from_state<F>(ctx, chs, ch)) return s;
     E zeta = F::ezero();
     for (u32 k = 0; k < F::D; k++) {
         const T z = static_cast<const T*>(zeta_canon)[k];
@@ -1146,12 +1342,63 @@ static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     // the caller's Challenger advances only with the proof it belongs to: after a size query (GB_ERR_BUFFER_TOO_SMALL) or any other
     // error *chs is untouched, so the retry with a big enough buffer draws the same fri_alpha / betas / PoW and returns these bytes
     if (!out || ob.len > out_cap) return fail(ctx, GB_ERR_BUFFER_TOO_SMALL, "FriProof buffer too small");
-    std::memset(chs, 0, sizeof *chs);
-    for (u32 i = 0; i < W; i++) chs->sponge_state[i] = ch.state[i];
-    chs->input_len = (uint32_t)ch.nin;
-    chs->output_len = (uint32_t)ch.nout;
-    for (int i = 0; i < ch.nin; i++) chs->input_buffer[i] = ch.in[i];
-    for (int i = 0; i < ch.nout; i++) chs->output_buffer[i] = ch.out[i];
+    challenger_to_state<F>(ch, chs);
+    return GB_OK;
+}
+
+// The description of a FriInstanceInfo as it crosses the ABI (flat arrays), checked against `num_polys[o]` polynomials per oracle
+static gb_status check_fri_instance_lists(gb_ctx* ctx, const uint32_t* num_polys, uint32_t num_oracles, const uint32_t* batch_sizes,
+                                          uint32_t num_batches, const uint32_t* polynomials) {
+    if (!num_oracles) return fail(ctx, GB_ERR_INVALID, "a FRI instance needs at least one oracle");
+    if (!num_batches) return fail(ctx, GB_ERR_INVALID, "a FRI instance needs at least one batch");
+    if (!batch_sizes || !polynomials) return fail(ctx, GB_ERR_INVALID, "null argument");
+    size_t at = 0;
+    for (u32 b = 0; b < num_batches; b++) {
+        if (!batch_sizes[b]) return fail(ctx, GB_ERR_INVALID, "batch " + std::to_string(b) + " opens no polynomial");
+        for (u32 j = 0; j < batch_sizes[b]; j++, at++) {
+            const u32 o = polynomials[2 * at], k = polynomials[2 * at + 1];
+            if (o >= num_oracles)
+                return fail(ctx, GB_ERR_INVALID, "batch " + std::to_string(b) + ": oracle_index " + std::to_string(o) + " out of range");
+            if (k >= num_polys[o])
+                return fail(ctx, GB_ERR_INVALID, "batch " + std::to_string(b) + ": polynomial_index " + std::to_string(k) + " out of range for oracle " +
+                                                     std::to_string(o) + " (salt columns are not polynomials)");
+        }
+    }
+    return GB_OK;
+}
+
+template <class F>
+static gb_status abi_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, u32 num_oracles, const void* points_canon,
+                                        const uint32_t* batch_sizes, u32 num_batches, const uint32_t* polynomials,
+                                        const std::vector<uint32_t>& arity_bits, u32 pow_bits, u32 nqr, gb_challenger_state* chs,
+                                        void* out, size_t out_cap, size_t* out_len) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    typedef Host<F> HF;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    typename HF::Challenger ch;
+    if (gb_status s = challenger_from_state<F>(ctx, chs, ch)) return s;
+    std::vector<E> points(num_batches);
+    for (u32 b = 0; b < num_batches; b++) {
+        E z = F::ezero();
+        bool zero = true;
+        for (u32 k = 0; k < F::D; k++) {
+            const T w = static_cast<const T*>(points_canon)[(size_t)b * F::D + k];
+            if ((u64)w >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical coordinate in the point of batch " + std::to_string(b));
+            zero = zero && w == 0;
+            F::set_coord(z, k, F::enc(w));
+        }
+        if (zero) return fail(ctx, GB_ERR_UNSUPPORTED, "the point of batch " + std::to_string(b) + " is zero: the division by X - z runs on 1 / z");
+        points[b] = z;
+    }
+    const FriPlan plan = compile_fri_instance(batch_sizes, num_batches, polynomials);
+    const FriShape fs{oracles[0]->log_n, oracles[0]->rate_bits, oracles[0]->cap_height, pow_bits, nqr, &arity_bits};
+    TmpAlloc tmp(ctx);
+    Bytes ob(out, out_cap);
+    if (gb_status s = fri_prove_instance<F>(ctx, tmp, fs, plan, oracles, num_oracles, points.data(), ch, ob)) return s;
+    *out_len = ob.len;
+    if (!out || ob.len > out_cap) return fail(ctx, GB_ERR_BUFFER_TOO_SMALL, "FriProof buffer too small");   // *chs untouched, as gb_prove_openings
+    challenger_to_state<F>(ch, chs);
     return GB_OK;
 }
 
@@ -1422,19 +1669,7 @@ gb_status gb_circuit_verifier_data(gb_circuit* c, void* cap_out, void* digest_ou
 gb_status gb_circuit_set_fri_reduction_arity_bits(gb_circuit* c, const uint32_t* arity_bits, uint32_t num_layers) try {
     if (!c) return fail(nullptr, GB_ERR_INVALID, "null circuit");
     gb_ctx* ctx = c->ctx;
-    if (num_layers && !arity_bits) return fail(ctx, GB_ERR_INVALID, "null arity_bits");
-    if (num_layers > GB_MAX_FRI_LAYERS) return fail(ctx, GB_ERR_INVALID, "more than GB_MAX_FRI_LAYERS FRI reduction layers");
-    const gb_circuit_config& cfg = c->cfg;
-    const u32 max_ab = 8u;   // a FRI leaf is 2^arity_bits extension elements; the proof format's u8 counts and the verifier stop at 2^8
-    u32 db = cfg.degree_bits;
-    for (u32 i = 0; i < num_layers; i++) {
-        const u32 ab = arity_bits[i];
-        if (ab == 0 || ab > max_ab) return fail(ctx, GB_ERR_INVALID, "FRI reduction arity outside the supported range");
-        if (ab > db) return fail(ctx, GB_ERR_INVALID, "FRI reduction arities sum past degree_bits");
-        if (db + cfg.rate_bits < cfg.cap_height + ab)
-            return fail(ctx, GB_ERR_INVALID, "cap_height should be at most log2(leaves.len()) in a FRI layer (merkle_tree.rs:154-157)");
-        db -= ab;
-    }
+    if (gb_status s = check_fri_reduction_arity_bits(ctx, c->cfg.degree_bits, c->cfg.rate_bits, c->cfg.cap_height, arity_bits, num_layers)) return s;
     c->arity_bits.assign(arity_bits, arity_bits + num_layers);
     c->arity_pending = false;
     return GB_OK;
@@ -1570,5 +1805,38 @@ gb_status gb_prove_openings(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial
                ? abi_prove_openings<GlF>(static_cast<Circuit<GlF>*>(c), wires, zs_partial_products, quotient, zeta, challenger, fri_proof_out, fri_proof_cap, fri_proof_len)
                : abi_prove_openings<BbF>(static_cast<Circuit<BbF>*>(c), wires, zs_partial_products, quotient, zeta, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
 } GB_CATCH_CIRCUIT(c)
+
+gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t num_oracles, const void* points,
+                                const uint32_t* batch_sizes, uint32_t num_batches, const uint32_t* polynomials,
+                                const uint32_t* reduction_arity_bits, uint32_t num_layers, uint32_t proof_of_work_bits,
+                                uint32_t num_query_rounds, gb_challenger_state* challenger, void* fri_proof_out,
+                                size_t fri_proof_cap, size_t* fri_proof_len) try {
+    if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null context");
+    if (!num_oracles) return fail(ctx, GB_ERR_INVALID, "a FRI instance needs at least one oracle");
+    if (!oracles || !points || !challenger || !fri_proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    std::vector<uint32_t> num_polys(num_oracles);
+    for (u32 o = 0; o < num_oracles; o++) {
+        const gb_batch* b = oracles[o];
+        const std::string what = "oracle " + std::to_string(o);
+        if (!b) return fail(ctx, GB_ERR_INVALID, what + " is null");
+        if (b->ctx != ctx || b->field != oracles[0]->field) return fail(ctx, GB_ERR_INVALID, what + " belongs to another context or field");
+        if (!b->coeffs) return fail(ctx, GB_ERR_INVALID, what + " is a stand-alone Merkle tree, not a polynomial batch");
+        if (b->log_n != oracles[0]->log_n || b->rate_bits != oracles[0]->rate_bits || b->cap_height != oracles[0]->cap_height)
+            return fail(ctx, GB_ERR_INVALID, what + " differs from oracle 0 in degree_bits, rate_bits or cap_height");
+        num_polys[o] = (uint32_t)b->ncols;
+    }
+    if (gb_status s = check_fri_instance_lists(ctx, num_polys.data(), num_oracles, batch_sizes, num_batches, polynomials)) return s;
+    const gb_batch* b0 = oracles[0];
+    if (gb_status s = check_fri_reduction_arity_bits(ctx, b0->log_n, b0->rate_bits, b0->cap_height, reduction_arity_bits, num_layers)) return s;
+    if (proof_of_work_bits > 31) return fail(ctx, GB_ERR_INVALID, "proof_of_work_bits above 31");
+    if (num_query_rounds == 0) return fail(ctx, GB_ERR_INVALID, "num_query_rounds is zero: a proof without queries proves nothing");
+    if (num_query_rounds > GB_MAX_FRI_QUERY_ROUNDS) return fail(ctx, GB_ERR_INVALID, "more than GB_MAX_FRI_QUERY_ROUNDS query rounds");
+    const std::vector<uint32_t> arity(reduction_arity_bits, reduction_arity_bits + num_layers);
+    return b0->field == GB_GOLDILOCKS
+               ? abi_fri_prove_openings<GlF>(ctx, oracles, num_oracles, points, batch_sizes, num_batches, polynomials, arity, proof_of_work_bits,
+                                             num_query_rounds, challenger, fri_proof_out, fri_proof_cap, fri_proof_len)
+               : abi_fri_prove_openings<BbF>(ctx, oracles, num_oracles, points, batch_sizes, num_batches, polynomials, arity, proof_of_work_bits,
+                                             num_query_rounds, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
+} GB_CATCH(ctx)
 
 }  // extern "C"

@@ -155,7 +155,7 @@ struct ParsedProof {
     std::vector<T> t_const, t_sig, t_w, t_z, t_zn, t_pp, t_q;  // canonical words, transcript order inside each list
     std::vector<std::vector<T>> layer_caps;
     struct Query {
-        std::vector<T> rows[4], paths[4];
+        std::vector<std::vector<T>> rows = std::vector<std::vector<T>>(4), paths = rows;   // per oracle (four in a PLONK proof)
         std::vector<std::vector<T>> step_rows, step_paths;  // step_rows: D * arity canonical words
     };
     std::vector<Query> queries;
@@ -164,6 +164,37 @@ struct ParsedProof {
     T pow_witness = 0;
     std::vector<T> pis;
 };
+
+// FriProof (util/serialization/mod.rs:1679-1695 read side) in two pieces - a compressed proof shares only the first:
+// commit_phase_merkle_caps, then query_round_proofs, final_poly and pow_witness.  row_widths[o]: the leaf width of oracle o.
+template <class F>
+void parse_fri_caps(ProofReader<F>& rd, u32 nlayers, size_t cap_elems, ParsedProof<F>& p) {
+    p.layer_caps.resize(nlayers);
+    for (auto& lc : p.layer_caps) rd.canon_vec(lc, cap_elems);
+}
+template <class F>
+void parse_fri_queries(ProofReader<F>& rd, const size_t* row_widths, u32 num_oracles, const std::vector<uint32_t>& arity_bits, u32 nqr,
+                       size_t final_len, ParsedProof<F>& p) {
+    constexpr u32 D = F::D, H = F::H;
+    const u32 nlayers = (u32)arity_bits.size();
+    p.queries.resize(nqr);
+    for (auto& q : p.queries) {
+        q.rows.resize(num_oracles);
+        q.paths.resize(num_oracles);
+        for (u32 o = 0; o < num_oracles; o++) {
+            rd.canon_vec(q.rows[o], row_widths[o]);
+            rd.canon_vec(q.paths[o], (size_t)rd.u8() * H);
+        }
+        q.step_rows.resize(nlayers);
+        q.step_paths.resize(nlayers);
+        for (u32 li = 0; li < nlayers; li++) {
+            rd.canon_vec(q.step_rows[li], (size_t)D << arity_bits[li]);
+            rd.canon_vec(q.step_paths[li], (size_t)rd.u8() * H);
+        }
+    }
+    rd.ext_vec(p.final_poly, p.t_final, final_len);
+    p.pow_witness = rd.field_canonical();
+}
 
 template <class F>
 void parse_caps_and_openings(ProofReader<F>& rd, const ProofShape<F>& sh, ParsedProof<F>& p) {
@@ -177,31 +208,15 @@ void parse_caps_and_openings(ProofReader<F>& rd, const ProofShape<F>& sh, Parsed
     rd.ext_vec(p.o_zn, p.t_zn, sh.nch);
     rd.ext_vec(p.o_pp, p.t_pp, (size_t)sh.nch * sh.num_prods);
     rd.ext_vec(p.o_q, p.t_q, sh.nq);
-    p.layer_caps.resize(sh.nlayers);
-    for (auto& lc : p.layer_caps) rd.canon_vec(lc, sh.cap_elems);
+    parse_fri_caps(rd, sh.nlayers, sh.cap_elems, p);
 }
 
 // util/serialization/mod.rs:2103-2151 read side
 template <class F>
 void parse_proof(const Circuit<F>* c, const ProofShape<F>& sh, const uint8_t* bytes, size_t len, ParsedProof<F>& p) {
-    constexpr u32 D = F::D, H = F::H;
     ProofReader<F> rd{bytes, len};
     parse_caps_and_openings(rd, sh, p);
-    p.queries.resize(sh.nqr);
-    for (auto& q : p.queries) {
-        for (int o = 0; o < 4; o++) {
-            rd.canon_vec(q.rows[o], sh.row_widths[o]);
-            rd.canon_vec(q.paths[o], (size_t)rd.u8() * H);
-        }
-        q.step_rows.resize(sh.nlayers);
-        q.step_paths.resize(sh.nlayers);
-        for (u32 li = 0; li < sh.nlayers; li++) {
-            rd.canon_vec(q.step_rows[li], (size_t)D << c->arity_bits[li]);
-            rd.canon_vec(q.step_paths[li], (size_t)rd.u8() * H);
-        }
-    }
-    rd.ext_vec(p.final_poly, p.t_final, sh.final_len);
-    p.pow_witness = rd.field_canonical();
+    parse_fri_queries(rd, sh.row_widths, 4, c->arity_bits, sh.nqr, sh.final_len, p);
     const u64 npis = rd.usize();
     if (npis > (1u << 20)) throw VerifyFail{GB_ERR_INVALID, "implausible public input count"};
     // validate_proof_with_pis_shape (plonk/validate_shape.rs:22-25): hash_no_pad does not pad, so a proof re-serialised with
@@ -223,6 +238,21 @@ struct Challenges {
     u64 pow_response;
     std::vector<u64> x_indices;
 };
+// fri/challenges.rs:24-68 from the transcript after the openings were observed
+template <class F>
+void get_fri_challenges(typename Host<F>::Challenger& ch, const ParsedProof<F>& p, u32 nqr, u64 N, Challenges<F>& out) {
+    out.fri_alpha = get_ext_challenge<F>(ch);
+    out.fri_betas.resize(p.layer_caps.size());
+    for (size_t li = 0; li < p.layer_caps.size(); li++) {
+        ch.observe(p.layer_caps[li].data(), p.layer_caps[li].size());
+        out.fri_betas[li] = get_ext_challenge<F>(ch);
+    }
+    ch.observe(p.t_final.data(), p.t_final.size());
+    ch.observe(p.pow_witness);
+    out.pow_response = ch.get();
+    out.x_indices.resize(nqr);
+    for (auto& x : out.x_indices) x = (u64)ch.get() % N;
+}
 template <class F>
 void get_challenges(const Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>& p, Challenges<F>& out) {
     typedef typename F::E E;
@@ -253,17 +283,42 @@ void get_challenges(const Circuit<F>* c, const ProofShape<F>& sh, const ParsedPr
     ch.observe(p.t_pp.data(), p.t_pp.size());
     ch.observe(p.t_q.data(), p.t_q.size());
     ch.observe(p.t_zn.data(), p.t_zn.size());
-    out.fri_alpha = get_ext();
-    out.fri_betas.resize(sh.nlayers);
-    for (u32 li = 0; li < sh.nlayers; li++) {
-        ch.observe(p.layer_caps[li].data(), p.layer_caps[li].size());
-        out.fri_betas[li] = get_ext();
-    }
-    ch.observe(p.t_final.data(), p.t_final.size());
-    ch.observe(p.pow_witness);
-    out.pow_response = ch.get();
-    out.x_indices.resize(sh.nqr);
-    for (auto& x : out.x_indices) x = (u64)ch.get() % sh.N;
+    get_fri_challenges<F>(ch, p, sh.nqr, sh.N, out);
+}
+
+// FriInstanceInfo (fri/structure.rs) with what the checks need of FriParams
+template <class F>
+struct FriInstance {
+    u32 lg = 0, r = 0, capH = 0, lgN = 0;
+    std::vector<size_t> widths, row_widths;   // per oracle: its polynomials; its leaf width (salted = hiding && blinding: + SALT_SIZE)
+    struct Batch {
+        typename F::E point;
+        std::vector<std::pair<u32, u32>> polys;   // (oracle_index, polynomial_index)
+    };
+    std::vector<Batch> batches;
+};
+// get_fri_instance(zeta) (plonk/circuit_data.rs:438-520): every polynomial of the four oracles at zeta, the Zs also at g zeta -
+// and the proof's opening set in that order (FriOpenings, plonk/proof.rs:388-440)
+template <class F>
+FriInstance<F> plonk_fri_instance(const ProofShape<F>& sh, typename F::E zeta) {
+    FriInstance<F> in;
+    in.lg = sh.lg; in.r = sh.r; in.capH = sh.capH; in.lgN = sh.lgN;
+    in.widths.assign(sh.widths, sh.widths + 4);
+    in.row_widths.assign(sh.row_widths, sh.row_widths + 4);
+    in.batches.resize(2);
+    in.batches[0].point = zeta;
+    for (u32 o = 0; o < 4; o++)
+        for (u32 i = 0; i < sh.widths[o]; i++) in.batches[0].polys.emplace_back(o, i);
+    in.batches[1].point = F::escale(zeta, F::two_adic_generator(sh.lg));
+    for (u32 i = 0; i < sh.nch; i++) in.batches[1].polys.emplace_back(2u, i);
+    return in;
+}
+template <class F>
+std::vector<std::vector<typename F::E>> plonk_fri_openings(const ParsedProof<F>& p) {
+    std::vector<std::vector<typename F::E>> o(2);
+    for (const auto* l : {&p.o_const, &p.o_sig, &p.o_w, &p.o_z, &p.o_pp, &p.o_q}) o[0].insert(o[0].end(), l->begin(), l->end());
+    o[1] = p.o_zn;
+    return o;
 }
 
 // The arithmetic of one FRI query (fri/verifier.rs:23-49, 121-165): the combined initial evaluation and the fold of a coset
@@ -271,35 +326,35 @@ template <class F>
 struct FriQueryMath {
     typedef typename F::T T;
     typedef typename F::E E;
-    const ProofShape<F>& sh;
-    const Challenges<F>& ch;
-    E red_open0, red_open1, alpha_shift1, zeta_next;
+    const FriInstance<F> inst;
+    const E fri_alpha;
+    std::vector<E> red_open, alpha_shift;   // per batch: reduce(openings) (PrecomputedReducedOpenings), alpha^(size of the batch)
     T wN;
-    FriQueryMath(const ProofShape<F>& s, const ParsedProof<F>& p, const Challenges<F>& c) : sh(s), ch(c) {
-        // the batches of the FRI instance (plonk/circuit_data.rs:658-800): all polynomials at zeta, the Zs at g * zeta
-        zeta_next = F::escale(ch.zeta, F::two_adic_generator(sh.lg));
-        auto reduce = [&](const std::vector<const std::vector<E>*>& lists) {  // ReducingFactor::reduce (util/reducing.rs:56-59)
-            E acc = F::ezero();
-            for (size_t li = lists.size(); li-- > 0;)
-                for (size_t i = lists[li]->size(); i-- > 0;) acc = F::eadd(F::emul(ch.fri_alpha, acc), (*lists[li])[i]);
-            return acc;
-        };
-        red_open0 = reduce({&p.o_const, &p.o_sig, &p.o_w, &p.o_z, &p.o_pp, &p.o_q});
-        red_open1 = reduce({&p.o_zn});
-        alpha_shift1 = gbk::epow<F>(ch.fri_alpha, sh.nch);  // alpha.shift over the second batch's count
-        wN = F::two_adic_generator(sh.lgN);
+    // openings[b]: the claimed values of batch b's polynomials at its point, in the batch's order
+    FriQueryMath(FriInstance<F> in, const std::vector<std::vector<E>>& openings, E alpha) : inst(std::move(in)), fri_alpha(alpha) {
+        for (size_t b = 0; b < inst.batches.size(); b++) {
+            E acc = F::ezero();   // ReducingFactor::reduce (util/reducing.rs:56-59)
+            for (size_t i = openings[b].size(); i-- > 0;) acc = F::eadd(F::emul(fri_alpha, acc), openings[b][i]);
+            red_open.push_back(acc);
+            alpha_shift.push_back(gbk::epow<F>(fri_alpha, inst.batches[b].polys.size()));
+        }
+        wN = F::two_adic_generator(inst.lgN);
     }
-    T subgroup_x(u64 x_index) const { return F::mul(F::generator(), F::pow(wN, rev_bits64(x_index, sh.lgN))); }
-    // fri_combine_initial: rows[o] = the opened leaf of oracle o (salts, if any, at the end and skipped)
+    FriQueryMath(const ProofShape<F>& s, const ParsedProof<F>& p, const Challenges<F>& c)
+        : FriQueryMath(plonk_fri_instance<F>(s, c.zeta), plonk_fri_openings<F>(p), c.fri_alpha) {}
+    T subgroup_x(u64 x_index) const { return F::mul(F::generator(), F::pow(wN, rev_bits64(x_index, inst.lgN))); }
+    // fri_combine_initial: rows[o] = the opened leaf of oracle o (salts, if any, at the end and never indexed)
     E combine_initial(const std::vector<T>* rows, T x) const {
-        E acc = F::ezero();
-        for (int o = 3; o >= 0; o--)
-            for (size_t i = sh.widths[o]; i-- > 0;) acc = F::eadd(F::emul(ch.fri_alpha, acc), F::efrom(F::enc(rows[o][i])));
-        E total = F::emul(F::esub(acc, red_open0), F::einv(F::esub(F::efrom(x), ch.zeta)));
-        E acc1 = F::ezero();
-        for (size_t i = sh.nch; i-- > 0;) acc1 = F::eadd(F::emul(ch.fri_alpha, acc1), F::efrom(F::enc(rows[2][i])));
-        total = F::emul(alpha_shift1, total);
-        return F::eadd(total, F::emul(F::esub(acc1, red_open1), F::einv(F::esub(F::efrom(x), zeta_next))));
+        E sum = F::ezero();
+        for (size_t b = 0; b < inst.batches.size(); b++) {
+            const typename FriInstance<F>::Batch& bt = inst.batches[b];
+            E acc = F::ezero();
+            for (size_t i = bt.polys.size(); i-- > 0;)
+                acc = F::eadd(F::emul(fri_alpha, acc), F::efrom(F::enc(rows[bt.polys[i].first][bt.polys[i].second])));
+            const E term = F::emul(F::esub(acc, red_open[b]), F::einv(F::esub(F::efrom(x), bt.point)));
+            sum = F::eadd(F::emul(alpha_shift[b], sum), term);   // alpha.shift(sum) + numerator / denominator
+        }
+        return sum;
     }
     // compute_evaluation: interpolate the coset's values (bit-reversed order) at beta
     static E compute_evaluation(T x, u64 within, u32 ab, const std::vector<E>& evals, E beta) {
@@ -334,6 +389,53 @@ struct FriQueryMath {
     }
 };
 
+// verify_fri_proof (fri/verifier.rs:67-250) after the transcript: proof of work, then per query round the initial Merkle paths,
+// fri_combine_initial and the folding checks down to the final polynomial.  initial_caps[o]: the cap of oracle o.
+template <class F>
+void verify_fri_parsed(const FriQueryMath<F>& fri, const typename F::T* const* initial_caps, const std::vector<uint32_t>& arity_bits,
+                       u32 proof_of_work_bits, const ParsedProof<F>& pp, const Challenges<F>& chal) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 H = F::H;
+    const FriInstance<F>& in = fri.inst;
+    const u32 nlayers = (u32)arity_bits.size();
+    {
+        const u32 min_lz = proof_of_work_bits + (64 - F::ORDER_BITS);
+        const u32 lz = chal.pow_response ? (u32)__builtin_clzll(chal.pow_response) : 64;
+        GB_VCHECK(lz >= min_lz, "Invalid proof of work witness. (fri/verifier.rs:51-65)");
+    }
+    for (size_t qi = 0; qi < pp.queries.size(); qi++) {
+        const typename ParsedProof<F>::Query& q = pp.queries[qi];
+        const u64 x_index = chal.x_indices[qi];
+        for (size_t o = 0; o < in.widths.size(); o++) {
+            // the path length is part of the statement (hash/merkle_proofs.rs:62-75 indexes the cap with what is left of the index)
+            if (q.paths[o].size() != (size_t)H * (in.lgN - in.capH)) throw VerifyFail{GB_ERR_INVALID, "Merkle path of the wrong length"};
+            GB_VCHECK(merkle_verify<F>(q.rows[o], x_index, initial_caps[o], q.paths[o]), "initial Merkle path does not lead to the cap");
+        }
+        T subgroup_x = fri.subgroup_x(x_index);
+        E old_eval = fri.combine_initial(q.rows.data(), subgroup_x);
+        u64 xi = x_index;
+        u32 height = in.lgN;
+        for (u32 li = 0; li < nlayers; li++) {
+            const u32 ab = arity_bits[li], arity = 1u << ab;
+            const u64 coset_index = xi >> ab, within = xi & (arity - 1);
+            const std::vector<E> evals = FriQueryMath<F>::to_ext(q.step_rows[li]);
+            GB_VCHECK(eeq<F>(evals[within], old_eval), "FRI consistency check failed (fri/verifier.rs:213-216)");
+            old_eval = FriQueryMath<F>::compute_evaluation(subgroup_x, within, ab, evals, chal.fri_betas[li]);
+            height -= ab;
+            if (height < in.capH || q.step_paths[li].size() != (size_t)H * (height - in.capH))
+                throw VerifyFail{GB_ERR_INVALID, "FRI layer Merkle path of the wrong length"};
+            GB_VCHECK(merkle_verify<F>(q.step_rows[li], coset_index, pp.layer_caps[li].data(), q.step_paths[li]),
+                      "FRI layer Merkle path does not lead to the cap");
+            subgroup_x = F::pow(subgroup_x, (u64)1 << ab);
+            xi = coset_index;
+        }
+        E acc = F::ezero();
+        for (size_t i = pp.final_poly.size(); i-- > 0;) acc = F::eadd(F::escale(acc, subgroup_x), pp.final_poly[i]);
+        GB_VCHECK(eeq<F>(acc, old_eval), "Final polynomial evaluation is invalid. (fri/verifier.rs:240-247)");
+    }
+}
+
 template <class F>
 void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>& pp) {
     typedef typename F::T T;
@@ -341,7 +443,6 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
     constexpr u32 H = F::H;
     const gb_circuit_config& cfg = c->cfg;
     const u32 lg = sh.lg, nch = sh.nch, nr = sh.nr, qdf = sh.qdf, nchunks = sh.nchunks, num_prods = sh.num_prods;
-    const u32 nlayers = sh.nlayers, nqr = sh.nqr;
     const u64 n = sh.n;
     const E one = F::efrom(F::one());
     Challenges<F> chal;
@@ -351,7 +452,6 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
     const std::vector<T>&betas = chal.betas, &gammas = chal.gammas, &alphas = chal.alphas;
     const E zeta = chal.zeta;
     const T* pi_hash = chal.pi_hash;
-    const u64 pow_response = chal.pow_response;
 
     // ---- vanishing(zeta) == Z_H(zeta) * quotient(zeta)  (plonk/verifier.rs:60-95, vanishing_poly.rs:40-170)
     {
@@ -409,44 +509,10 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
         }
     }
 
-    // ---- FRI (fri/verifier.rs:67-250)
-    {
-        const u32 min_lz = cfg.proof_of_work_bits + (64 - F::ORDER_BITS);
-        const u32 lz = pow_response ? (u32)__builtin_clzll(pow_response) : 64;
-        GB_VCHECK(lz >= min_lz, "Invalid proof of work witness. (fri/verifier.rs:51-65)");
-    }
+    // ---- FRI (fri/verifier.rs:67-250) on the PLONK instance
     const FriQueryMath<F> fri(sh, pp, chal);
     const T* initial_caps[4] = {c->cap_host.data(), pp.wires_cap.data(), pp.zs_cap.data(), pp.quot_cap.data()};
-    for (u32 qi = 0; qi < nqr; qi++) {
-        const typename ParsedProof<F>::Query& q = pp.queries[qi];
-        const u64 x_index = chal.x_indices[qi];
-        for (int o = 0; o < 4; o++) {
-            // the path length is part of the statement (hash/merkle_proofs.rs:62-75 indexes the cap with what is left of the index)
-            if (q.paths[o].size() != (size_t)H * (sh.lgN - sh.capH)) throw VerifyFail{GB_ERR_INVALID, "Merkle path of the wrong length"};
-            GB_VCHECK(merkle_verify<F>(q.rows[o], x_index, initial_caps[o], q.paths[o]), "initial Merkle path does not lead to the cap");
-        }
-        T subgroup_x = fri.subgroup_x(x_index);
-        E old_eval = fri.combine_initial(q.rows, subgroup_x);
-        u64 xi = x_index;
-        u32 height = sh.lgN;
-        for (u32 li = 0; li < nlayers; li++) {
-            const u32 ab = c->arity_bits[li], arity = 1u << ab;
-            const u64 coset_index = xi >> ab, within = xi & (arity - 1);
-            const std::vector<E> evals = FriQueryMath<F>::to_ext(q.step_rows[li]);
-            GB_VCHECK(eeq<F>(evals[within], old_eval), "FRI consistency check failed (fri/verifier.rs:213-216)");
-            old_eval = FriQueryMath<F>::compute_evaluation(subgroup_x, within, ab, evals, chal.fri_betas[li]);
-            height -= ab;
-            if (height < sh.capH || q.step_paths[li].size() != (size_t)H * (height - sh.capH))
-                throw VerifyFail{GB_ERR_INVALID, "FRI layer Merkle path of the wrong length"};
-            GB_VCHECK(merkle_verify<F>(q.step_rows[li], coset_index, pp.layer_caps[li].data(), q.step_paths[li]),
-                      "FRI layer Merkle path does not lead to the cap");
-            subgroup_x = F::pow(subgroup_x, (u64)1 << ab);
-            xi = coset_index;
-        }
-        E acc = F::ezero();
-        for (size_t i = pp.final_poly.size(); i-- > 0;) acc = F::eadd(F::escale(acc, subgroup_x), pp.final_poly[i]);
-        GB_VCHECK(eeq<F>(acc, old_eval), "Final polynomial evaluation is invalid. (fri/verifier.rs:240-247)");
-    }
+    verify_fri_parsed<F>(fri, initial_caps, c->arity_bits, cfg.proof_of_work_bits, pp, chal);
 }
 
 template <class F>
@@ -457,9 +523,104 @@ void verify_impl(Circuit<F>* c, const uint8_t* bytes, size_t len) {
     verify_parsed(c, sh, pp);
 }
 
+// verify_fri_proof (fri/verifier.rs:67-250) on an instance described by flat arrays (include/goldibear_gpu.h); the lists have been
+// checked, `ch` is the caller's transcript by value
+template <class F>
+void fri_verify_impl(u32 degree_bits, u32 rate_bits, u32 cap_height, bool hiding, const uint32_t* num_polys, const uint32_t* blinding,
+                     u32 num_oracles, const void* points, const uint32_t* batch_sizes, u32 num_batches, const uint32_t* polynomials,
+                     const void* openings, const void* caps, const std::vector<uint32_t>& arity_bits, u32 proof_of_work_bits, u32 nqr,
+                     typename Host<F>::Challenger ch, const uint8_t* bytes, size_t len) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 D = F::D;
+    FriInstance<F> in;
+    in.lg = degree_bits; in.r = rate_bits; in.capH = cap_height; in.lgN = degree_bits + rate_bits;
+    for (u32 o = 0; o < num_oracles; o++) {
+        in.widths.push_back(num_polys[o]);
+        in.row_widths.push_back(num_polys[o] + (hiding && blinding[o] ? (size_t)GB_SALT_SIZE : 0));   // salted = hiding && blinding
+    }
+    auto ext_at = [](const void* base, size_t i, const char* what) {
+        E e = F::ezero();
+        for (u32 k = 0; k < D; k++) {
+            const T w = static_cast<const T*>(base)[i * D + k];
+            if ((u64)w >= F::ORDER) throw VerifyFail{GB_ERR_INVALID, std::string("non-canonical field element in ") + what};
+            F::set_coord(e, k, F::enc(w));
+        }
+        return e;
+    };
+    std::vector<std::vector<E>> open(num_batches);
+    in.batches.resize(num_batches);
+    size_t at = 0;
+    for (u32 b = 0; b < num_batches; b++) {
+        in.batches[b].point = ext_at(points, b, "the points");
+        for (u32 j = 0; j < batch_sizes[b]; j++, at++) {
+            in.batches[b].polys.emplace_back(polynomials[2 * at], polynomials[2 * at + 1]);
+            open[b].push_back(ext_at(openings, at, "the openings"));
+        }
+    }
+    const size_t cap_elems = (size_t)F::H << cap_height;
+    std::vector<const T*> cap_ptrs(num_oracles);
+    for (u32 o = 0; o < num_oracles; o++) {
+        cap_ptrs[o] = static_cast<const T*>(caps) + o * cap_elems;
+        for (size_t i = 0; i < cap_elems; i++)
+            if ((u64)cap_ptrs[o][i] >= F::ORDER) throw VerifyFail{GB_ERR_INVALID, "non-canonical field element in the initial caps"};
+    }
+    u32 total_arity = 0;
+    for (u32 ab : arity_bits) total_arity += ab;
+    ParsedProof<F> pp;
+    ProofReader<F> rd{bytes, len};
+    parse_fri_caps(rd, (u32)arity_bits.size(), cap_elems, pp);
+    parse_fri_queries(rd, in.row_widths.data(), num_oracles, arity_bits, nqr, (size_t)1 << (degree_bits - total_arity), pp);
+    if (rd.off != len) throw VerifyFail{GB_ERR_INVALID, "trailing bytes in proof"};
+    Challenges<F> chal;
+    get_fri_challenges<F>(ch, pp, nqr, (u64)1 << in.lgN, chal);
+    const FriQueryMath<F> fri(std::move(in), open, chal.fri_alpha);
+    verify_fri_parsed<F>(fri, cap_ptrs.data(), arity_bits, proof_of_work_bits, pp, chal);
+}
+
 }  // namespace
 
 extern "C" {
+
+gb_status gb_fri_verify(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t hiding,
+                        const uint32_t* oracle_num_polys, const uint32_t* oracle_blinding, uint32_t num_oracles, const void* points,
+                        const uint32_t* batch_sizes, uint32_t num_batches, const uint32_t* polynomials, const void* openings,
+                        const void* initial_caps, const uint32_t* reduction_arity_bits, uint32_t num_layers,
+                        uint32_t proof_of_work_bits, uint32_t num_query_rounds, const gb_challenger_state* challenger,
+                        const void* fri_proof, size_t fri_proof_len) try {
+    if (field != GB_GOLDILOCKS && field != GB_BABYBEAR) return fail(ctx, GB_ERR_INVALID, "unknown field");
+    if (!oracle_num_polys || !oracle_blinding || !points || !openings || !initial_caps || !challenger || !fri_proof)
+        return fail(ctx, GB_ERR_INVALID, "null argument");
+    const u32 two_adicity = field == GB_GOLDILOCKS ? GlF::TWO_ADICITY : BbF::TWO_ADICITY;
+    if (degree_bits > two_adicity || rate_bits > two_adicity || degree_bits + rate_bits > two_adicity)
+        return fail(ctx, GB_ERR_INVALID, "LDE size exceeds the field's two-adicity");
+    if (cap_height > degree_bits + rate_bits) return fail(ctx, GB_ERR_INVALID, "cap_height should be at most log2(leaves.len())");
+    if (gb_status s = check_fri_instance_lists(ctx, oracle_num_polys, num_oracles, batch_sizes, num_batches, polynomials)) return s;
+    if (gb_status s = check_fri_reduction_arity_bits(ctx, degree_bits, rate_bits, cap_height, reduction_arity_bits, num_layers)) return s;
+    if (proof_of_work_bits > 31) return fail(ctx, GB_ERR_INVALID, "proof_of_work_bits above 31");
+    // every query round is at least one opened word per oracle: a count the bytes cannot hold is refused before anything is sized by it
+    if (num_query_rounds == 0) return fail(ctx, GB_ERR_INVALID, "num_query_rounds is zero: a proof without queries proves nothing");
+    if (num_query_rounds > GB_MAX_FRI_QUERY_ROUNDS) return fail(ctx, GB_ERR_INVALID, "more than GB_MAX_FRI_QUERY_ROUNDS query rounds");
+    if (num_query_rounds > fri_proof_len) return fail(ctx, GB_ERR_INVALID, "proof bytes are truncated: fewer bytes than query rounds");
+    const std::vector<uint32_t> arity(reduction_arity_bits, reduction_arity_bits + num_layers);
+    const uint8_t* bytes = static_cast<const uint8_t*>(fri_proof);
+    try {
+        if (field == GB_GOLDILOCKS) {
+            Host<GlF>::Challenger ch;
+            if (gb_status s = challenger_from_state<GlF>(ctx, challenger, ch)) return s;
+            fri_verify_impl<GlF>(degree_bits, rate_bits, cap_height, hiding != 0, oracle_num_polys, oracle_blinding, num_oracles, points, batch_sizes,
+                                 num_batches, polynomials, openings, initial_caps, arity, proof_of_work_bits, num_query_rounds, ch, bytes, fri_proof_len);
+        } else {
+            Host<BbF>::Challenger ch;
+            if (gb_status s = challenger_from_state<BbF>(ctx, challenger, ch)) return s;
+            fri_verify_impl<BbF>(degree_bits, rate_bits, cap_height, hiding != 0, oracle_num_polys, oracle_blinding, num_oracles, points, batch_sizes,
+                                 num_batches, polynomials, openings, initial_caps, arity, proof_of_work_bits, num_query_rounds, ch, bytes, fri_proof_len);
+        }
+    } catch (const VerifyFail& f) {
+        return fail(ctx, f.code, f.msg);
+    }
+    return GB_OK;
+} GB_CATCH(ctx)
 
 gb_status gb_verify(gb_circuit* c, const void* proof, size_t proof_len) try {
     if (!c) return fail(nullptr, GB_ERR_INVALID, "null circuit");

@@ -75,6 +75,10 @@ SIGNATURES = {
     "gb_zs_partial_products": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "gb_quotient_polys": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "gb_prove_openings": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "gb_fri_prove_openings": (_i32, [_vp, _pvp, _u32, _vp, C.POINTER(_u32), _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _u32, _vp, _vp,
+                                     _sz, C.POINTER(_sz)]),
+    "gb_fri_verify": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, _vp, C.POINTER(_u32), _u32,
+                             C.POINTER(_u32), _vp, _vp, C.POINTER(_u32), _u32, _u32, _u32, _vp, _vp, _sz]),
     "gb_prove": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_circuit_drop_retry": (_i32, [_vp]),

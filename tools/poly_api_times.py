@@ -13,6 +13,8 @@ One process; every call is timed with device events on the context's stream afte
 under its own time limit (--step-timeout seconds: the process ends there, nothing is started after an overrun).
     timeout -k 10 600 python tools/poly_api_times.py --out profiles/poly_api_times.txt
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/poly_api_times.py --only goldilocks:fft_r3 --reps 1   (a run of its own)
+    timeout -k 10 300 python tools/poly_api_times.py --fri      (the opening proof, see fri_openings; APPENDS to profiles/fri_instance_times.txt)
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/poly_api_times.py --fri --only goldilocks:fri --reps 3
 """
 import argparse
 import ctypes as C
@@ -36,14 +38,68 @@ def _overrun(signum, frame):
     os._exit(124)
 
 
+FRI_SHAPES = {   # the benchmark's circuits: (field tag, wires, routed wires, challenges, FRI arity bits)
+    "goldilocks": (0, 135, 80, 3, 4), "babybear": (1, 167, 41, 10, 3)}
+
+
+def fri_openings(args, ctx, timed, rand, say):
+    """--fri: the opening proof of the benchmark's FRI instance at 2^20 rows - four oracles of the circuit's widths over random
+    device-resident columns (272 columns for Goldilocks) - through gb_prove_openings and through gb_fri_prove_openings with the
+    same instance written out as oracles and batches; both give the same bytes.  --only FIELD:fri runs the general call alone."""
+    from oracle.fields import BB, GL
+    from plonky2_goldibear_amd import CircuitData, PolynomialBatch, prove_openings
+    from plonky2_goldibear_amd.fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo
+    say("fri openings  2^%d rows, rate %d, cap %d, device-resident oracles; reps %d (median), warm-up %d" % (LOG_N, RATE, CAP, args.reps, args.warmup))
+    for name, (tag, nw, nr, nch, ab) in FRI_SHAPES.items():
+        want = args.only.split(":") if args.only else None
+        if want and want[0] != name:
+            continue
+        _, _, _, idt, p = FIELDS[name]
+        n, d, w = 1 << LOG_N, (2, 4)[tag], (12, 16)[tag]
+        widths = [1 + 2 + nr, nw, nch * -(-nr // 8), nch * 8]
+        k_is = np.array([7 * i % p for i in range(1, nr + 1)], dtype=np.uint64 if tag == 0 else np.uint32)
+        gpu = CircuitData(ctx, LOG_N, rand((widths[0], n), idt, p), k_is, num_wires=nw, num_routed_wires=nr, num_challenges=nch,
+                          arity_bits=ab, field=tag)
+        oracles = [gpu.constants_sigmas_commitment] + [
+            (PolynomialBatch.from_coeffs if i == 3 else PolynomialBatch.from_values)(ctx, rand((widths[i], n), idt, p), RATE, CAP, field=tag)
+            for i in (1, 2, 3)]
+        zeta = [0x9E3779B1 * i % p for i in range(3, 3 + d)]
+        zeta_next = [int(x) * (GL, BB)[tag].two_adic_generator(LOG_N) % p for x in zeta]   # g zeta
+        every = [q for i in range(4) for q in FriPolynomialInfo.from_range(i, range(widths[i]))]
+        inst = FriInstanceInfo([FriOracleInfo(x, False) for x in widths],
+                               [FriBatchInfo(zeta, every), FriBatchInfo(zeta_next, FriPolynomialInfo.from_range(2, range(nch)))])
+        params = FriParams(FriConfig(RATE, CAP, 16, 28), False, LOG_N, gpu.reduction_arity_bits)
+        chal = ([5] * w, [], [])
+        general = lambda: prove_openings(inst, oracles, chal, params)
+        if want:
+            for _ in range(args.reps):
+                general()
+            ctx.synchronize()
+            return
+        plonk = lambda: gpu.prove_openings(oracles[1], oracles[2], oracles[3], zeta, chal)
+        same = general()[0] == plonk()[0]
+        tg, tp = timed(general), timed(plonk)
+        cols = sum(widths)
+        say("%s  %d columns in 4 oracles: gb_prove_openings %.3f ms, gb_fri_prove_openings %.3f ms, same bytes: %s" % (name, cols, tp, tg, same))
+        nbytes = cols * n * (8, 4)[tag] + 2 * n * d * (8, 4)[tag]   # every column once, two slots written
+        say("%s  k_reduce_batches expected traffic %.2f GB = %.3f ms at 5.4 TB/s" % (name, nbytes / 1e9, nbytes / 5.4e9))
+        for b in oracles[1:]:
+            b.free()
+        gpu.free()
+        ctx.trim()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "poly_api_times.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/poly_api_times.txt (rewritten); with --fri profiles/fri_instance_times.txt (appended to)")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--step-timeout", type=int, default=120)
     ap.add_argument("--only", default=None, help="FIELD:STEP - run one step (for a profiler run); nothing is written")
+    ap.add_argument("--fri", action="store_true", help="time gb_fri_prove_openings next to gb_prove_openings instead (see fri_openings)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fri_instance_times.txt" if args.fri else "poly_api_times.txt")
 
     import torch
     from csrc_hash import csrc_sha16
@@ -108,6 +164,13 @@ def main():
         return (torch.randint(0, min(p, 1 << 62), shape, generator=g, device="cuda", dtype=torch.int64) % p).to(
             torch.int64 if idt == np.int64 else torch.int32)
 
+    if args.fri:
+        fri_openings(args, ctx, timed, rand, say)
+        if not args.only:
+            with open(args.out, "a") as f:   # next to the alternation's figures, which stay
+                f.write("\n" + "\n".join(lines) + "\n")
+        ctx.close()
+        return
     say("poly_api_times  csrc %s  reps %d (median), warm-up %d, device events on the context's stream" % (csrc_sha16(), args.reps, args.warmup))
     for name, (tag, ncols, width, idt, p) in FIELDS.items():
         n = 1 << LOG_N
