@@ -167,14 +167,16 @@ gb_status gb_batch_device_ptrs(gb_batch* b, void** coeffs, void** lde, void** di
  * gb_circuit_create takes the gate set of the reference's dummy circuit: gates sorted by
  * (degree, id) = [NoopGate, ConstantGate{num_constants}, PublicInputGate<H>], one selector column
  * (gates/selectors.rs:142-159), evaluated inside the quotient kernel.  gb_circuit_create_gates (below) takes any gate set
- * over the eighteen gate kinds GB_GATE_* with any selector grouping - every gate DefaultGateSerializer knows except
- * LookupGate / LookupTableGate, which are GB_ERR_UNSUPPORTED - and evaluates it on the GPU as well.
+ * over the eighteen built-in gate kinds GB_GATE_* with any selector grouping - every gate DefaultGateSerializer knows except
+ * LookupGate / LookupTableGate, which are GB_ERR_UNSUPPORTED - and evaluates it on the GPU as well; gb_circuit_create_programs
+ * adds gates of the caller's own as constraint programs (GB_GATE_PROGRAM).
  * Both of the reference's configurations are served (plonk/config.rs:119-150): GB_GOLDILOCKS = D 2, H 4,
  * Poseidon-12, 8-byte elements; GB_BABYBEAR = D 4 (x^4 - 11), H 8, Poseidon2-16, 4-byte elements.
  * Configuration range of the prover: degree_bits from 2 up to the field's two-adicity less rate_bits (32 / 27: the reference has no
  * other cap, plonk/prover.rs:228-447; 2^21 and 2^22 rows run the library's own transform passes, larger ones an outer radix step
  * around them, and what does not fit the device is GB_ERR_OOM - a 2^23-row Goldilocks proof holds ~170 GB of commitments);
- * max_quotient_degree_factor 8 (Goldilocks also 16); rate_bits from
+ * max_quotient_degree_factor 2, 4, 8 or 16 for either field, with ceil(num_routed_wires / factor) <= 32 partial-product chunks
+ * (MAX_CHUNKS); rate_bits from
  * log2 of that factor up to 8 - above it the quotient is computed on every 2^(rate_bits - log2 factor)-th point of the LDE, as
  * plonk/prover.rs:735-749 does (the reference's size-optimised recursion proofs use rate_bits 7 and 8,
  * recursion/recursive_verifier.rs:573-611); num_challenges 1 .. 16 (BabyBear from 4: circuit_builder.rs:1190-1192 demands
@@ -248,6 +250,10 @@ gb_status gb_circuit_free(gb_circuit* c);
 #define GB_GATE_ADD_MANY 15            /* gates/add_many.rs               param = num_addends, param2 = num_ops */
 #define GB_GATE_APPLY_MAT4 16          /* gates/apply_mat4.rs             param = num_ops */
 #define GB_GATE_POSEIDON2_INTERNAL_PERMUTATION 17 /* gates/poseidon2_internal_permutation.rs (BabyBear) */
+/* Any other gate, as data: a constraint program - the gate's eval_unfiltered (gates/gate.rs:53-272) as a straight-line program
+ * of add / sub / mul over the row's wires and constants.  param = the index of the gate's program in the table handed to
+ * gb_circuit_create_programs / gb_verifier_create_programs; the create functions without a table answer GB_ERR_INVALID. */
+#define GB_GATE_PROGRAM 18
 typedef struct gb_gate {
     uint32_t kind;            /* GB_GATE_* */
     uint32_t param;           /* ConstantGate num_consts / ArithmeticGate, Poseidon2BabyBearGate num_ops; see above; 0 otherwise */
@@ -259,6 +265,48 @@ gb_status gb_circuit_create_gates(gb_ctx* ctx, const gb_circuit_config* cfg, con
                                   const void* constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out);
 gb_status gb_circuit_create_gates_cols(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
                                        const void* const* constants_sigmas_cols, const void* k_is, uint32_t flags, gb_circuit** out);
+/* ---- constraint programs (GB_GATE_PROGRAM) ----
+ * The programs of a circuit cross the ABI as one flat array of 64-bit words, program i being
+ * program_words[program_offsets[i] .. program_offsets[i + 1]); program_offsets has num_programs + 1 ascending entries, the first 0.
+ * One program:
+ *   word 0   num_wires | num_constants << 32      wire columns 0 .. num_wires-1 and constants 0 .. num_constants-1 may be read
+ *   word 1   num_constraints | degree << 32       Gate::num_constraints() / Gate::degree()
+ *   word 2   num_regs | num_literals << 32
+ *   word 3   num_instrs                           (the high half is zero)
+ *   then num_literals canonical field elements, one per word (converted once at create to the device form),
+ *   then num_instrs instruction words:
+ *     bits 0-1    op: 0 ADD, 1 SUB, 2 MUL (reg[dst] = a OP b), 3 EMIT (the next constraint is a; dst and b are zero)
+ *     bits 2-7    dst register
+ *     bits 8-31   operand a: bits 8-9 its space (0 register, 1 wire column, 2 constant column after the selectors, 3 literal),
+ *                 bits 10-31 its index
+ *     bits 32-55  operand b, the same way
+ *     bits 56-63  zero
+ * EMIT yields the constraints in the order of eval_unfiltered.  At the verifier's zeta the same instructions run on extension
+ * elements; a product of D-tuples of wires in F[x]/(x^D - W) is spelled out in base operations with W as a literal.
+ * Limits: GB_MAX_PROGRAMS per circuit; per program GB_MAX_PROGRAM_INSTRS instructions, GB_MAX_PROGRAM_REGS registers,
+ * GB_MAX_PROGRAM_LITERALS literals, GB_MAX_PROGRAM_CONSTRAINTS constraints.
+ * GB_ERR_INVALID at create, the message naming the program and the instruction: a header over the limits or a length that does
+ * not match it; a register read before it is written; a register, wire, constant or literal index out of range; a literal >= p;
+ * a count of EMITs other than num_constraints; a gb_gate.param >= num_programs; a constraint whose degree bound (literal 0,
+ * wire and constant 1, ADD / SUB the maximum, MUL the sum) exceeds `degree`; degree plus the degree of the gate's filter
+ * (gates/gate.rs:391-404: one factor per other gate of its selector group, one more with several selector columns) above
+ * max_quotient_degree_factor + 1 - the bound gates/selectors.rs:125-209 keeps for every gate it groups.
+ * With num_programs = 0 (program_words and program_offsets may be NULL) the functions are the ones without a table.  The
+ * prover evaluates program gates in a launch of their own (k_gate_programs, an interpreter with its registers in LDS); a circuit
+ * without them runs exactly the kernels it ran before.  Measured cost: the interpreted gates take 5.6x
+ * (Goldilocks) / 7.4x (BabyBear) the kernel time of the same gates compiled, 1.7x / 1.9x over the quotient stage at 2^14 rows. */
+#define GB_MAX_PROGRAMS 16
+#define GB_MAX_PROGRAM_INSTRS 4096
+#define GB_MAX_PROGRAM_REGS 32
+#define GB_MAX_PROGRAM_LITERALS 256
+#define GB_MAX_PROGRAM_CONSTRAINTS 1024
+gb_status gb_circuit_create_programs(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                     const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                     const void* constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out);
+gb_status gb_circuit_create_programs_cols(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                          const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                          const void* const* constants_sigmas_cols, const void* k_is, uint32_t flags,
+                                          gb_circuit** out);
 /* ProverOnlyCircuitData.constants_sigmas_commitment (plonk/circuit_data.rs:532-534), the PolynomialBatch built by
  * gb_circuit_create*: a BORROWED handle - owned by the circuit, valid until gb_circuit_free, never passed to gb_batch_free.  The
  * reference's prover reads it for the opening set (plonk/proof.rs:359-377) and the query rounds. */
@@ -350,6 +398,11 @@ gb_status gb_verify_compressed(gb_circuit* c, const void* compressed, size_t com
  * RECURSIVE_VERIFIER_GL regression proof (recursion/regression_test_data.rs) through it.  Free with gb_circuit_free. */
 gb_status gb_verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates, const void* k_is,
                              const void* constants_sigmas_cap, const void* circuit_digest, gb_circuit** out);
+/* the same for a gate set with GB_GATE_PROGRAM entries (see "constraint programs" above) */
+gb_status gb_verifier_create_programs(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                      const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                      const void* k_is, const void* constants_sigmas_cap, const void* circuit_digest,
+                                      gb_circuit** out);
 
 /* ---- the stages of prove(), one at a time ---------------------------------------------------------------------------------
  * For a host that keeps the reference's prover loop (plonk/prover.rs:228-447) and its Challenger and swaps in the heavy calls

@@ -135,6 +135,13 @@ extern "C" {
     fn gb_circuit_create_gates_cols(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
                                     constants_sigmas_cols: *const *const c_void, k_is: *const c_void, flags: u32,
                                     out: *mut *mut gb_circuit) -> i32;
+    fn gb_circuit_create_programs(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
+                                  program_words: *const u64, program_offsets: *const u32, num_programs: u32,
+                                  constants_sigmas: *const c_void, k_is: *const c_void, flags: u32, out: *mut *mut gb_circuit) -> i32;
+    fn gb_circuit_create_programs_cols(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
+                                       program_words: *const u64, program_offsets: *const u32, num_programs: u32,
+                                       constants_sigmas_cols: *const *const c_void, k_is: *const c_void, flags: u32,
+                                       out: *mut *mut gb_circuit) -> i32;
     fn gb_circuit_free(c: *mut gb_circuit) -> i32;
     fn gb_circuit_verifier_data(c: *mut gb_circuit, cap_out: *mut c_void, digest_out: *mut c_void) -> i32;
     fn gb_circuit_set_fri_reduction_arity_bits(c: *mut gb_circuit, arity_bits: *const u32, num_layers: u32) -> i32;
@@ -169,6 +176,9 @@ extern "C" {
                        salts: *const c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> i32;
     fn gb_verifier_create(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32, k_is: *const c_void,
                           constants_sigmas_cap: *const c_void, circuit_digest: *const c_void, out: *mut *mut gb_circuit) -> i32;
+    fn gb_verifier_create_programs(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
+                                   program_words: *const u64, program_offsets: *const u32, num_programs: u32, k_is: *const c_void,
+                                   constants_sigmas_cap: *const c_void, circuit_digest: *const c_void, out: *mut *mut gb_circuit) -> i32;
     fn gb_verify_compressed(c: *mut gb_circuit, compressed: *const c_void, len: usize) -> i32;
     fn gb_proof_compress(c: *mut gb_circuit, proof: *const c_void, len: usize, out: *mut c_void, cap: usize, out_len: *mut usize) -> i32;
     fn gb_proof_decompress(c: *mut gb_circuit, compressed: *const c_void, len: usize, out: *mut c_void, cap: usize,
@@ -637,6 +647,13 @@ pub enum ProveOutcome {
     PermArgZero,
 }
 
+/// The library reads program_words up to the last offset: the offsets must ascend from 0 to program_words.len().
+fn program_table_len(program_words: &[u64], program_offsets: &[u32]) -> Result<u32, GpuError> {
+    let ascending = program_offsets.windows(2).all(|w| w[0] <= w[1]) && program_offsets.first().map_or(true, |&o| o == 0);
+    need("program_words", program_words.len(), if ascending { program_offsets.last().map_or(0, |&o| o as usize) } else { usize::MAX })?;
+    Ok(program_offsets.len().saturating_sub(1) as u32)
+}
+
 impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
     pub fn new(ctx: &'c GpuContext, mut config: gb_circuit_config, constants_sigmas: &[W], k_is: &[W]) -> Result<Self, GpuError> {
         config.field = field_tag::<W>();
@@ -655,6 +672,37 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         check(ctx.0, unsafe {
             gb_circuit_create_gates(ctx.0, &config, gates.as_ptr(), gates.len() as u32, constants_sigmas.as_ptr() as *const c_void,
                                     k_is.as_ptr() as *const c_void, GB_INPUT_HOST, &mut h)
+        })?;
+        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+    }
+    /// `with_gates` for a gate set with gates of the host's own (`kind` = GB_GATE_PROGRAM, `param` = index of the gate's program):
+    /// the programs lie end to end in `program_words`, program i at program_offsets[i] .. program_offsets[i + 1]; a program is the
+    /// gate's eval_unfiltered as the words include/goldibear_gpu.h describes ("constraint programs"); INTEGRATION.md shows how a
+    /// host records them from `eval_unfiltered_circuit`.
+    pub fn with_programs(ctx: &'c GpuContext, mut config: gb_circuit_config, gates: &[gb_gate], program_words: &[u64], program_offsets: &[u32],
+                         constants_sigmas: &[W], k_is: &[W]) -> Result<Self, GpuError> {
+        config.field = field_tag::<W>();
+        let num_programs = program_table_len(program_words, program_offsets)?;
+        let mut h = ptr::null_mut();
+        check(ctx.0, unsafe {
+            gb_circuit_create_programs(ctx.0, &config, gates.as_ptr(), gates.len() as u32, program_words.as_ptr(), program_offsets.as_ptr(),
+                                       num_programs, constants_sigmas.as_ptr() as *const c_void, k_is.as_ptr() as *const c_void,
+                                       GB_INPUT_HOST, &mut h)
+        })?;
+        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+    }
+    /// `with_programs` over one column per `Vec` (`gb_circuit_create_programs_cols`)
+    pub fn with_programs_columns<C: AsRef<[W]>>(ctx: &'c GpuContext, mut config: gb_circuit_config, gates: &[gb_gate],
+                                                program_words: &[u64], program_offsets: &[u32], constants_sigmas: &[C], k_is: &[W]) -> Result<Self, GpuError> {
+        config.field = field_tag::<W>();
+        need("constants_sigmas", constants_sigmas.len(), (config.num_selectors + config.num_constants + config.num_routed_wires) as usize)?;
+        need("k_is", k_is.len(), config.num_routed_wires as usize)?;
+        let table = column_table("constants_sigmas", constants_sigmas, 1usize << config.degree_bits)?;
+        let num_programs = program_table_len(program_words, program_offsets)?;
+        let mut h = ptr::null_mut();
+        check(ctx.0, unsafe {
+            gb_circuit_create_programs_cols(ctx.0, &config, gates.as_ptr(), gates.len() as u32, program_words.as_ptr(), program_offsets.as_ptr(),
+                                            num_programs, table.as_ptr(), k_is.as_ptr() as *const c_void, GB_INPUT_HOST, &mut h)
         })?;
         Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
     }
@@ -934,6 +982,20 @@ impl<W: Copy + Default> Verifier<W> {
         check(ptr::null(), unsafe {
             gb_verifier_create(ptr::null_mut(), &config, gates.as_ptr(), gates.len() as u32, k_is.as_ptr() as *const c_void,
                                constants_sigmas_cap.as_ptr() as *const c_void, circuit_digest.as_ptr() as *const c_void, &mut h)
+        })?;
+        Ok(Self { handle: h, _w: std::marker::PhantomData })
+    }
+    /// `new` for a gate set with GB_GATE_PROGRAM entries (`gb_verifier_create_programs`): the program table as in
+    /// `GpuCircuit::with_programs`
+    pub fn with_programs(mut config: gb_circuit_config, gates: &[gb_gate], program_words: &[u64], program_offsets: &[u32], k_is: &[W],
+                         constants_sigmas_cap: &[W], circuit_digest: &[W]) -> Result<Self, GpuError> {
+        config.field = field_tag::<W>();
+        let num_programs = program_table_len(program_words, program_offsets)?;
+        let mut h = ptr::null_mut();
+        check(ptr::null(), unsafe {
+            gb_verifier_create_programs(ptr::null_mut(), &config, gates.as_ptr(), gates.len() as u32, program_words.as_ptr(),
+                                        program_offsets.as_ptr(), num_programs, k_is.as_ptr() as *const c_void,
+                                        constants_sigmas_cap.as_ptr() as *const c_void, circuit_digest.as_ptr() as *const c_void, &mut h)
         })?;
         Ok(Self { handle: h, _w: std::marker::PhantomData })
     }

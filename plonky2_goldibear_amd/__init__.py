@@ -13,3 +13,4 @@ from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  #
 from .prover import CircuitData, VerifierCircuitData  # noqa: F401
 from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
 from .fri import prove_openings, verify_fri_proof  # noqa: F401
+from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401

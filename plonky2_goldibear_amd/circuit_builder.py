@@ -645,11 +645,20 @@ class CircuitBuilder:
             if row in incomplete:
                 gg = gg[:incomplete[row]]
             gens += gg
-        gate_table = [(g.kind, g.param, selector_indices[i], groups[selector_indices[i]][0], groups[selector_indices[i]][1],
+        # the constraint programs of the gate set's program gates (gate_program.ProgramGate), numbered in sorted order
+        # (a program gate's `param` is its index here; the gate object may serve other builders and is left as it is)
+        programs, params = [], []
+        for g in gates:
+            if getattr(g, "program", None) is not None:
+                params.append(len(programs))
+                programs.append(g.program)
+            else:
+                params.append(g.param)
+        gate_table = [(g.kind, params[i], selector_indices[i], groups[selector_indices[i]][0], groups[selector_indices[i]][1],
                        getattr(g, "param2", 0), getattr(g, "param3", 0)) for i, g in enumerate(gates)]
         return BuiltCircuit(ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, len(groups), max_constants, gens, find,
                             list(self.public_inputs), self.random_wire, [g.id for g in gates],
-                            sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}))
+                            sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None)
 
     def _forest(self):
         """Disjoint sets over the targets that appear in copy constraints (plonk/permutation_argument.rs:13-101)."""
@@ -720,8 +729,8 @@ class BuiltCircuit:
     """CircuitData (plonk/circuit_data.rs:153-300) for a built circuit: prove(PartialWitness) / verify(proof)."""
 
     def __init__(self, ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, num_selectors, max_constants, generators, find,
-                 public_inputs, random_wire, gate_ids, copy_wires):
-        self.config, self.F, self.degree_bits = cfg, F, degree_bits
+                 public_inputs, random_wire, gate_ids, copy_wires, programs=None):
+        self.config, self.F, self.degree_bits, self.programs = cfg, F, degree_bits, programs
         self.constants_sigmas, self.k_is, self.gate_table, self.gate_ids = constants_sigmas, k_is, gate_table, gate_ids
         self.num_selectors, self.max_constants = num_selectors, max_constants
         self.generators, self.find, self.public_inputs, self.random_wire = generators, find, public_inputs, random_wire
@@ -736,7 +745,7 @@ class BuiltCircuit:
                                     num_query_rounds=cfg.num_query_rounds, arity_bits=cfg.arity_bits,
                                     final_poly_bits=cfg.final_poly_bits, num_selectors=num_selectors, field=cfg.field,
                                     gates=gate_table, num_public_inputs=len(public_inputs),
-                                    reduction_arity_bits=cfg.reduction_arity_bits(degree_bits))
+                                    reduction_arity_bits=cfg.reduction_arity_bits(degree_bits), programs=programs)
 
     def generate_witness(self, pw, rng=None):
         """generate_partial_witness + full_witness (iop/generator.rs:25-117, iop/witness.rs:359-371)

@@ -14,6 +14,22 @@ constexpr unsigned POSEIDON2_BB_WIRES_PER_OP = 33 + 8 + 16 * 7 + 13;           /
 constexpr unsigned MAX_INTERPOLATION_BITS = 4;   // CosetInterpolationGate subgroup_bits (= a FRI arity_bits, <= 4 here)
 constexpr unsigned MAX_RANDOM_ACCESS_BITS = 6;   // (2 + 2^bits) routed wires per copy
 
+// Constraint programs (GB_GATE_PROGRAM, include/goldibear_gpu.h): the limits checked at create and the decoded headers.  The
+// instruction words and the literals (device form) of all programs lie in two flat tables; a ProgramInfo points into them.
+constexpr unsigned MAX_PROGRAMS = 16, MAX_PROGRAM_INSTRS = 4096, MAX_PROGRAM_REGS = 32, MAX_PROGRAM_LITERALS = 256,
+                   MAX_PROGRAM_CONSTRAINTS = 1024;
+constexpr unsigned PROGRAM_HEADER_WORDS = 4;
+enum ProgramOp { PROG_ADD = 0, PROG_SUB = 1, PROG_MUL = 2, PROG_EMIT = 3 };
+enum ProgramSpace { PROG_REG = 0, PROG_WIRE = 1, PROG_CONST = 2, PROG_LIT = 3 };
+struct ProgramInfo {
+    unsigned num_wires, num_constants, num_constraints, degree, num_regs, num_literals, num_instrs;
+    unsigned lit_off, instr_off;   // first literal / first instruction word in the flat tables
+};
+struct ProgramSet {
+    unsigned num_programs, max_regs;
+    ProgramInfo p[MAX_PROGRAMS];
+};
+
 struct GateSet {
     unsigned num_gates, num_selectors;
     gb_gate g[MAX_GATES];

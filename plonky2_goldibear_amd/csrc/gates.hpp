@@ -99,6 +99,21 @@ GB_HD u32 num_constants(const gb_gate& g) {
     }
 }
 
+// the same three figures for any gate of a circuit: a program gate (param = index of its program) takes them from its header
+GB_HD bool is_program(const gb_gate& g) { return g.kind == GB_GATE_PROGRAM; }
+template <class F>
+GB_HD u32 num_constraints(const gb_gate& g, const ProgramSet& ps) {
+    return is_program(g) ? ps.p[g.param].num_constraints : num_constraints<F>(g);
+}
+template <class F>
+GB_HD u32 num_wires(const gb_gate& g, const ProgramSet& ps) {
+    return is_program(g) ? ps.p[g.param].num_wires : num_wires<F>(g);
+}
+template <class F>
+GB_HD u32 num_constants(const gb_gate& g, const ProgramSet& ps) {
+    return is_program(g) ? ps.p[g.param].num_constants : num_constants<F>(g);
+}
+
 // base-field algebra (device form) and extension-field algebra; constants handed to mulc / addc are base elements in device form
 template <class F>
 struct BaseAlg {
@@ -640,6 +655,55 @@ GB_HD void eval_poseidon2_internal_permutation(W&& wire, Emit&& emit) {
 #pragma unroll 1
     for (u32 i = 0; i < 15; i++)
         (X::load(wire, (17 + i) * D) - (full + X::load(wire, (i + 1) * D).scalar_c(F::mul(k, F::enc((u64)1 << SHIFTS[i]))))).emit_all(emit);
+}
+
+// GB_GATE_PROGRAM: a gate's eval_unfiltered as a straight-line program over the algebra A (include/goldibear_gpu.h describes the
+// words).  An instruction word: op in bits 0-1, destination register in bits 2-7, operand a in bits 8-31 and operand b in bits
+// 32-55, each operand its space in the low two bits and its index in the 22 above.  The programs are validated at create
+// (prover_host.inc check_programs): every index is in range and no register is read before it is written, so nothing is
+// checked here.  `ins` and `lits` are the same for every point: on the device they are read through the scalar unit.
+GB_HD u32 prog_op(u64 w) { return (u32)w & 3; }
+GB_HD u32 prog_dst(u64 w) { return ((u32)w >> 2) & 63; }
+GB_HD u32 prog_operand(u64 w, u32 which) { return (u32)(w >> (which ? 32 : 8)) & 0xFFFFFF; }
+GB_HD u32 prog_space(u32 operand) { return operand & 3; }
+GB_HD u32 prog_index(u32 operand) { return operand >> 2; }
+template <class V>
+struct ArrayRegs {  // the host's register file
+    V* r;
+    GB_HD V get(u32 i) const { return r[i]; }
+    GB_HD void set(u32 i, V v) const { r[i] = v; }
+};
+template <class T>
+struct LdsRegs {    // the device's: [num_regs][blockDim] words in LDS, a register's row lane-consecutive (conflict-free)
+    T* base;        // this lane's word of register 0
+    u32 stride;     // blockDim.x
+    GB_HD T get(u32 i) const { return base[i * stride]; }
+    GB_HD void set(u32 i, T v) const { base[i * stride] = v; }
+};
+template <class F, class A, class R, class W, class K, class Emit>
+GB_HD void run_program(const u64* __restrict__ ins, u32 num_instrs, const typename F::T* __restrict__ lits, R&& regs, W&& wire,
+                       K&& konst, Emit&& emit) {
+    typedef typename A::V V;
+    auto load = [&](u32 o) -> V {
+        const u32 i = prog_index(o);
+        switch (prog_space(o)) {
+            case PROG_REG: return regs.get(i);
+            case PROG_WIRE: return wire(i);
+            case PROG_CONST: return konst(i);
+            default: return A::cst(lits[i]);
+        }
+    };
+    for (u32 pc = 0; pc < num_instrs; pc++) {
+        const u64 w = ins[pc];
+        const V a = load(prog_operand(w, 0));
+        const u32 op = prog_op(w);
+        if (op == PROG_EMIT) {
+            emit(a);
+            continue;
+        }
+        const V b = load(prog_operand(w, 1));
+        regs.set(prog_dst(w), op == PROG_MUL ? A::mul(a, b) : op == PROG_ADD ? A::add(a, b) : A::sub(a, b));
+    }
 }
 
 // wire(col) / konst(i) give the opened (or LDE) value of a wire / of the i-th constant after the selectors

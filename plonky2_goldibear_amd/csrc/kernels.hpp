@@ -217,6 +217,13 @@ struct GateParams {
     gates::GateSet gs;
     u32 stride_bits;   // log2 of a column's length in cs / wires
 };
+// the constraint programs of a circuit's GB_GATE_PROGRAM gates for k_gate_programs: headers by value, tables on the device
+template <class F>
+struct ProgramParams {
+    gates::ProgramSet ps;
+    const u64* instrs;            // instruction words of all programs (ProgramInfo::instr_off)
+    const typename F::T* lits;    // literals of all programs, device form (ProgramInfo::lit_off)
+};
 template <class F>
 struct PolyGroups {
     const typename F::T* ptr[4];
@@ -241,7 +248,7 @@ bool quotient_shape_supported(u32 field, u32 chunk, u32 num_challenges);
 // qv <- the alpha-folded gate constraints of a general gate set (kernels_gates.hip), any num_challenges <= MAX_CHALLENGES (slices)
 template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st);
+                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs = nullptr);
 // l0[j] = Z_H(x_j) / (n (x_j - 1)), zh = device copy of the 2^rate_bits values of Z_H on the cosets
 template <class F>
 void l0_table(u32 log_n, u32 rate_bits, const PowTab<F>& w_N, const typename F::T* zh, typename F::T* l0, hipStream_t st);

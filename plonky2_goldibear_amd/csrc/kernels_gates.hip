@@ -4,7 +4,8 @@
 // gates, per challenge.  The result is the gate part of the alpha-folded vanishing polynomial; k_quotient (kernels_prover.hip,
 // ext_gates = 1) adds the permutation-argument terms to it and divides by Z_H.  Folding on the fly keeps the per-thread state
 // at C accumulators instead of num_gate_constraints (123 for PoseidonGate) values; the field is exact, so the order of the
-// additions does not change the result.  Two launches: the short gates, then the in-circuit hash gate (gates.hpp GateSubset).
+// additions does not change the result.  Two launches: the short gates, then the in-circuit hash gate (gates.hpp GateSubset); a
+// circuit with constraint programs (GB_GATE_PROGRAM) gets a third, the interpreter k_gate_programs.
 #include <algorithm>
 #include <utility>
 #include "gates.hpp"
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void k_gate_constraints(GateParams<F> p, const
     u32 idx0 = p.t0;
     for (u32 g = 0; g < p.gs.num_gates; g++) {
         const gb_gate& gd = p.gs.g[g];
-        if (gd.kind == GB_GATE_NOOP || gates::is_heavy(gd) != (SUBSET == gates::HEAVY_GATES)) continue;
+        if (gd.kind == GB_GATE_NOOP || gates::is_program(gd) || gates::is_heavy(gd) != (SUBSET == gates::HEAVY_GATES)) continue;
         const T f = gates::filter<F, A>(g, gd, cs[(size_t)gd.selector_index * N + j], p.gs.num_selectors > 1);
         FoldAcc<F> sum[C];
         u32 idx = idx0;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(64 * TILED_WAVES) void k_gate_constraints_tiled(Gat
     auto konst = [&](u32 i) { return shc[(p.gs.num_selectors + i) * 64 + lane]; };
     for (u32 g = 0; g < p.gs.num_gates; g++) {
         const gb_gate& gd = p.gs.g[g];
-        if (gd.kind == GB_GATE_NOOP || gates::is_heavy(gd) || plan.wave_of[g] != wave) continue;
+        if (gd.kind == GB_GATE_NOOP || gates::is_heavy(gd) || gates::is_program(gd) || plan.wave_of[g] != wave) continue;
         const T f = gates::filter<F, A>(g, gd, shc[gd.selector_index * 64 + lane], p.gs.num_selectors > 1);
         FoldAcc<F> sum[C];
         u32 idx = p.t0;
@@ -160,6 +161,52 @@ __global__ __launch_bounds__(64 * TILED_WAVES) void k_gate_constraints_tiled(Gat
             qv[(((size_t)k << r) + cidx) * n + il] = v;
         }
     }
+}
+
+// The program gates (GB_GATE_PROGRAM): gates::run_program at every point of the quotient domain, one thread per point with the
+// index math of k_gate_constraints, adding to qv like the HEAVY_GATES launch.  The register file of a program is indexed at run
+// time, so it lives in LDS and not in a per-lane array (which would go to scratch): [max_regs][blockDim] words, a register's row
+// lane-consecutive - a wave's access is one conflict-free row read.  At most 32 registers x 256 threads x 8 bytes = 64 KiB, two
+// workgroups per CU.  Instruction words and literals are the same for the whole wave and come through the scalar unit (const
+// __restrict__, uniform index); wire and constant operands are read from global memory where they are used, coalesced.
+static constexpr u32 PROGRAM_BLOCK = 256;
+template <class F, u32 C>
+__global__ __launch_bounds__(PROGRAM_BLOCK) void k_gate_programs(GateParams<F> p, ProgramParams<F> pp, const typename F::T* __restrict__ cs,
+                                                                  const typename F::T* __restrict__ wires,
+                                                                  const typename F::T* __restrict__ apow, typename F::T* __restrict__ qv) {
+    typedef typename F::T T;
+    typedef gates::BaseAlg<F> A;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_prog[];
+    const gates::LdsRegs<T> regs{reinterpret_cast<T*>(smem_prog) + threadIdx.x, PROGRAM_BLOCK};
+    const u32 lgn = p.log_n, r = p.rate_bits;
+    const size_t n = (size_t)1 << lgn, N = (size_t)1 << p.stride_bits;   // N: column stride of cs / wires (the FRI LDE)
+    const size_t j = (size_t)blockIdx.x * PROGRAM_BLOCK + threadIdx.x;
+    if (j >= (n << r)) return;   // (no barrier below: a lane only ever touches its own LDS words)
+    const u32 cidx = (u32)(j >> lgn), jl = (u32)(j & (n - 1));
+    const u32 il = brev32g(jl, lgn);
+    T acc[C];
+#pragma unroll
+    for (u32 k = 0; k < C; k++) acc[k] = qv[(((size_t)k << r) + cidx) * n + il];
+    auto wire = [&](u32 col) { return wires[(size_t)col * N + j]; };
+    auto konst = [&](u32 i) { return cs[(size_t)(p.gs.num_selectors + i) * N + j]; };
+    for (u32 g = 0; g < p.gs.num_gates; g++) {
+        const gb_gate& gd = p.gs.g[g];
+        if (!gates::is_program(gd)) continue;
+        const gates::ProgramInfo& pi = pp.ps.p[gd.param];
+        const T f = gates::filter<F, A>(g, gd, cs[(size_t)gd.selector_index * N + j], p.gs.num_selectors > 1);
+        FoldAcc<F> sum[C];
+        u32 idx = p.t0;
+        auto emit = [&](T c) {
+#pragma unroll
+            for (u32 k = 0; k < C; k++) sum[k].acc(c, apow[k * p.nterms + idx]);
+            idx++;
+        };
+        gates::run_program<F, A>(pp.instrs + pi.instr_off, pi.num_instrs, pp.lits + pi.lit_off, regs, wire, konst, emit);
+#pragma unroll
+        for (u32 k = 0; k < C; k++) acc[k] = F::add(acc[k], F::mul(f, sum[k].finish()));
+    }
+#pragma unroll
+    for (u32 k = 0; k < C; k++) qv[(((size_t)k << r) + cidx) * n + il] = acc[k];
 }
 
 // rough instruction count of one gate at one point: modular multiplications of the evaluator (29 instructions each), the
@@ -196,7 +243,7 @@ static bool make_tiled_plan(const GateParams<F>& p, TiledPlan* plan, size_t* sme
     for (u32 g = 0; g < p.gs.num_gates; g++) {
         const gb_gate& gd = p.gs.g[g];
         plan->wave_of[g] = 0;
-        if (gd.kind == GB_GATE_NOOP || gates::is_heavy(gd)) continue;
+        if (gd.kind == GB_GATE_NOOP || gates::is_heavy(gd) || gates::is_program(gd)) continue;
         nw = std::max(nw, gates::num_wires<F>(gd));
         nconst = std::max(nconst, gates::num_constants<F>(gd));
         cost[m++] = {gate_cost<F>(gd, p.num_challenges), g};
@@ -233,12 +280,16 @@ static bool has_heavy(const gates::GateSet& gs) {
             hipLaunchKernelGGL((k_gate_constraints<FF, CC, gates::LIGHT_GATES>), grid, block, 0, st, p, cs, wires, apow, pi_hash, qv); \
         if (has_heavy(p.gs))                                                                                                  \
             hipLaunchKernelGGL((k_gate_constraints<FF, CC, gates::HEAVY_GATES>), grid, block, 0, st, p, cs, wires, apow, pi_hash, qv); \
+        if (programs && programs->ps.num_programs)                                                                            \
+            hipLaunchKernelGGL((k_gate_programs<FF, CC>), grid, dim3(PROGRAM_BLOCK),                                          \
+                               (size_t)std::max(programs->ps.max_regs, 1u) * PROGRAM_BLOCK * sizeof(typename FF::T), st, p,   \
+                               *programs, cs, wires, apow, qv);                                                               \
     } while (0)
 // one launch per slice of challenges (challenge_slices, kernels.hpp): a slice [k0, k0 + w) is the same kernel on the alpha powers
 // and the qv block of challenge k0 - the gate kernels index both relative to their first challenge
 template <class F>
 static bool gate_slice(GateParams<F> p, u32 k0, u32 width, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st) {
+                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs) {
     const size_t N = (size_t)1 << (p.log_n + p.rate_bits);   // points of the quotient domain
     const dim3 grid((u32)((N + 255) / 256)), block(256);
     apow += (size_t)k0 * p.nterms;
@@ -267,16 +318,18 @@ static bool gate_slice(GateParams<F> p, u32 k0, u32 width, const typename F::T* 
 }
 template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st) {
+                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs) {
     u32 widths[MAX_CHALLENGES];
     const u32 ns = challenge_slices(F::TAG, 4, p.num_challenges, widths);
     if (!ns) return false;
     for (u32 i = 0, k0 = 0; i < ns; k0 += widths[i], i++)
-        if (!gate_slice<F>(p, k0, widths[i], cs, wires, apow, pi_hash, qv, st)) return false;
+        if (!gate_slice<F>(p, k0, widths[i], cs, wires, apow, pi_hash, qv, st, programs)) return false;
     return true;
 }
-template bool gate_constraints<GlF>(const GateParams<GlF>&, const u64*, const u64*, const u64*, const u64*, u64*, hipStream_t);
-template bool gate_constraints<BbF>(const GateParams<BbF>&, const u32*, const u32*, const u32*, const u32*, u32*, hipStream_t);
+template bool gate_constraints<GlF>(const GateParams<GlF>&, const u64*, const u64*, const u64*, const u64*, u64*, hipStream_t,
+                                    const ProgramParams<GlF>*);
+template bool gate_constraints<BbF>(const GateParams<BbF>&, const u32*, const u32*, const u32*, const u32*, u32*, hipStream_t,
+                                    const ProgramParams<BbF>*);
 #undef GB_G
 
 }  // namespace gbk

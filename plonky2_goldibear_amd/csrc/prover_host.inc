@@ -18,6 +18,10 @@ struct gb_circuit {
     bool general_gates = false;       // false: the dummy gate set, evaluated inside k_quotient
     bool verify_only = false;         // made by gb_verifier_create: no prover state
     uint32_t num_gate_constraints = 0;  // CommonCircuitData.num_gate_constraints (max over the gates)
+    // the constraint programs of the GB_GATE_PROGRAM gates (parse_programs): headers, instruction words, literals in device form
+    // (one per u64 for either field)
+    gbk::gates::ProgramSet programs{};
+    std::vector<u64> prog_instrs, prog_lits;
     std::vector<uint32_t> arity_bits;   // FriParams.reduction_arity_bits (ConstantArityBits' list unless set through the ABI)
     // cfg.arity_bits == 0, or a (cfg.arity_bits, cfg.final_poly_bits) on which ConstantArityBits would panic: the circuit's strategy
     // is Fixed / MinSize and its list comes through gb_circuit_set_fri_reduction_arity_bits - until then nothing that needs it runs
@@ -49,6 +53,128 @@ struct gb_circuit {
     virtual void release() = 0;
     virtual void verifier_data(void* cap_out, void* digest_out) = 0;
 };
+
+// ---------------------------------------------------------------------------------------------- constraint programs
+// The program table of gb_circuit_create_programs / gb_verifier_create_programs, decoded and checked (include/goldibear_gpu.h
+// gives the words and the list of what is refused).  Host only; this is the code that reads untrusted input: every length is
+// checked against the offsets before a word is read, and after it returns run_program needs no check of its own.
+struct ProgramTable {   // the three program arguments of the ABI
+    const uint64_t* words;
+    const uint32_t* offsets;
+    uint32_t num_programs;
+};
+struct ParsedPrograms {
+    gbk::gates::ProgramSet set{};
+    std::vector<u64> instrs, lits;
+    void move_to(gb_circuit* c) {   // the circuit is the tables' one owner from here on
+        c->programs = set;
+        c->prog_instrs = std::move(instrs);
+        c->prog_lits = std::move(lits);
+    }
+};
+template <class F>
+static gb_status parse_programs(gb_ctx* ctx, const gb_circuit_config* cfg, const uint64_t* words, const uint32_t* offsets,
+                                uint32_t num_programs, ParsedPrograms* out) {
+    namespace G = gbk::gates;
+    *out = ParsedPrograms{};
+    if (num_programs == 0) return GB_OK;
+    if (num_programs > G::MAX_PROGRAMS)
+        return fail(ctx, GB_ERR_INVALID, "more than " + std::to_string(G::MAX_PROGRAMS) + " constraint programs");
+    if (!words || !offsets) return fail(ctx, GB_ERR_INVALID, "null program table");
+    if (offsets[0] != 0) return fail(ctx, GB_ERR_INVALID, "program_offsets[0] is not 0");
+    constexpr u64 ORDER = F::ORDER_BITS == 64 ? 0xFFFFFFFF00000001ull : 2013265921ull;
+    // a program is at most a header, MAX_PROGRAM_LITERALS literals and MAX_PROGRAM_INSTRS instructions long
+    constexpr u32 MAX_WORDS = G::PROGRAM_HEADER_WORDS + G::MAX_PROGRAM_LITERALS + G::MAX_PROGRAM_INSTRS;
+    for (u32 pi = 0; pi < num_programs; pi++) {
+        const std::string name = "program " + std::to_string(pi);
+        if (offsets[pi + 1] < offsets[pi]) return fail(ctx, GB_ERR_INVALID, name + ": program_offsets are not ascending");
+        const u32 len = offsets[pi + 1] - offsets[pi];
+        if (len < G::PROGRAM_HEADER_WORDS || len > MAX_WORDS)
+            return fail(ctx, GB_ERR_INVALID, name + ": " + std::to_string(len) + " words is no program (header " +
+                        std::to_string(G::PROGRAM_HEADER_WORDS) + ", at most " + std::to_string(MAX_WORDS) + ")");
+        const uint64_t* w = words + offsets[pi];
+        G::ProgramInfo h{};
+        h.num_wires = (u32)w[0]; h.num_constants = (u32)(w[0] >> 32);
+        h.num_constraints = (u32)w[1]; h.degree = (u32)(w[1] >> 32);
+        h.num_regs = (u32)w[2]; h.num_literals = (u32)(w[2] >> 32);
+        h.num_instrs = (u32)w[3];
+        if ((w[3] >> 32) != 0) return fail(ctx, GB_ERR_INVALID, name + ": header word 3 has bits above num_instrs");
+        if (h.num_instrs > G::MAX_PROGRAM_INSTRS || h.num_regs > G::MAX_PROGRAM_REGS || h.num_literals > G::MAX_PROGRAM_LITERALS ||
+            h.num_constraints > G::MAX_PROGRAM_CONSTRAINTS)
+            return fail(ctx, GB_ERR_INVALID, name + ": header over the limits (" + std::to_string(h.num_instrs) + " instructions / " +
+                        std::to_string(h.num_regs) + " registers / " + std::to_string(h.num_literals) + " literals / " +
+                        std::to_string(h.num_constraints) + " constraints; at most 4096 / 32 / 256 / 1024)");
+        if (len != G::PROGRAM_HEADER_WORDS + h.num_literals + h.num_instrs)
+            return fail(ctx, GB_ERR_INVALID, name + ": the header describes " +
+                        std::to_string(G::PROGRAM_HEADER_WORDS + h.num_literals + h.num_instrs) + " words, the table holds " + std::to_string(len));
+        if (h.num_wires > cfg->num_wires || h.num_constants > cfg->num_constants)
+            return fail(ctx, GB_ERR_INVALID, name + " needs " + std::to_string(h.num_wires) + " wires / " + std::to_string(h.num_constants) +
+                        " constants, the config has " + std::to_string(cfg->num_wires) + " / " + std::to_string(cfg->num_constants));
+        h.lit_off = (u32)out->lits.size();
+        h.instr_off = (u32)out->instrs.size();
+        for (u32 i = 0; i < h.num_literals; i++) {
+            const u64 v = w[G::PROGRAM_HEADER_WORDS + i];
+            if (v >= ORDER) return fail(ctx, GB_ERR_INVALID, name + ": literal " + std::to_string(i) + " is not canonical");
+            out->lits.push_back((u64)F::enc((typename F::T)v));
+        }
+        // one pass: which registers are written, and the degree bound of what each holds
+        u32 reg_deg[G::MAX_PROGRAM_REGS];
+        bool written[G::MAX_PROGRAM_REGS] = {};
+        u32 emits = 0;
+        const uint64_t* ins = w + G::PROGRAM_HEADER_WORDS + h.num_literals;
+        for (u32 pc = 0; pc < h.num_instrs; pc++) {
+            const u64 iw = ins[pc];
+            const std::string at = name + " instruction " + std::to_string(pc);
+            if (iw >> 56) return fail(ctx, GB_ERR_INVALID, at + ": bits 56-63 are not zero");
+            const u32 op = G::prog_op(iw), dst = G::prog_dst(iw);
+            u32 deg[2] = {0, 0};
+            const u32 nops = op == G::PROG_EMIT ? 1 : 2;
+            for (u32 k = 0; k < nops; k++) {
+                const u32 o = G::prog_operand(iw, k), idx = G::prog_index(o);
+                switch (G::prog_space(o)) {
+                    case G::PROG_REG:
+                        if (idx >= h.num_regs) return fail(ctx, GB_ERR_INVALID, at + ": register " + std::to_string(idx) + " of " + std::to_string(h.num_regs));
+                        if (!written[idx]) return fail(ctx, GB_ERR_INVALID, at + ": register " + std::to_string(idx) + " is read before it is written");
+                        deg[k] = reg_deg[idx];
+                        break;
+                    case G::PROG_WIRE:
+                        if (idx >= h.num_wires) return fail(ctx, GB_ERR_INVALID, at + ": wire " + std::to_string(idx) + " of " + std::to_string(h.num_wires));
+                        deg[k] = 1;
+                        break;
+                    case G::PROG_CONST:
+                        if (idx >= h.num_constants) return fail(ctx, GB_ERR_INVALID, at + ": constant " + std::to_string(idx) + " of " + std::to_string(h.num_constants));
+                        deg[k] = 1;
+                        break;
+                    default:
+                        if (idx >= h.num_literals) return fail(ctx, GB_ERR_INVALID, at + ": literal " + std::to_string(idx) + " of " + std::to_string(h.num_literals));
+                        break;
+                }
+            }
+            if (op == G::PROG_EMIT) {
+                if (dst != 0 || G::prog_operand(iw, 1) != 0) return fail(ctx, GB_ERR_INVALID, at + ": EMIT with a destination or a second operand");
+                if (deg[0] > h.degree)
+                    return fail(ctx, GB_ERR_INVALID, at + ": constraint " + std::to_string(emits) + " has degree bound " + std::to_string(deg[0]) +
+                                ", the program declares " + std::to_string(h.degree));
+                emits++;
+                out->instrs.push_back(iw);
+                continue;
+            }
+            if (dst >= h.num_regs) return fail(ctx, GB_ERR_INVALID, at + ": register " + std::to_string(dst) + " of " + std::to_string(h.num_regs));
+            // (a bound past any quotient degree factor is clamped: 4096 products of it cannot wrap a u32)
+            const u32 d = op == G::PROG_MUL ? deg[0] + deg[1] : std::max(deg[0], deg[1]);
+            reg_deg[dst] = std::min(d, 1u << 16);
+            written[dst] = true;
+            out->instrs.push_back(iw);
+        }
+        if (emits != h.num_constraints)
+            return fail(ctx, GB_ERR_INVALID, name + ": " + std::to_string(emits) + " EMITs, the header declares " +
+                        std::to_string(h.num_constraints) + " constraints");
+        out->set.p[pi] = h;
+        out->set.max_regs = std::max(out->set.max_regs, h.num_regs);
+    }
+    out->set.num_programs = num_programs;
+    return GB_OK;
+}
 
 // A FriParams.reduction_arity_bits list for oracles of this shape: what gb_circuit_set_fri_reduction_arity_bits,
 // gb_fri_prove_openings and gb_fri_verify accept (the empty list included)
@@ -125,6 +251,8 @@ struct Circuit : gb_circuit {
     T* l0 = nullptr;               // [n 2^qb] L_0 on the quotient domain, leaf order (eval_l_0, zero_poly_coset.rs:58-61)
     std::vector<T> zh, zh_inv;     // ZeroPolyOnCoset (field/src/zero_poly_coset.rs:22-37), device form
     u32* perm_err = nullptr;       // set by the partial-products kernel on a zero denominator; zero otherwise
+    u64* prog_instrs_dev = nullptr;   // the constraint programs' instruction words and literals (device form), device copies
+    T* prog_lits_dev = nullptr;
     std::vector<void*> owned;
     void release() override {
         if (cs) gb_batch_free(cs);
@@ -247,7 +375,8 @@ gb_status read_cap(gb_batch* b, std::vector<typename F::T>& cap) {
 // ---------------------------------------------------------------------------------------------- build()
 template <class F>
 gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::gates::GateSet& gset, bool general,
-                         ColSrc constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out) {
+                         ColSrc constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out,
+                         ParsedPrograms* progs = nullptr) {
     typedef typename F::T T;
     typedef Host<F> HF;
     constexpr u32 H = F::H;
@@ -267,8 +396,9 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
     c->cfg = *cfg;
     c->gates = gset;
     c->general_gates = general;
+    if (progs) progs->move_to(c);
     for (u32 g = 0; g < gset.num_gates; g++)
-        c->num_gate_constraints = std::max(c->num_gate_constraints, gbk::gates::num_constraints<F>(gset.g[g]));
+        c->num_gate_constraints = std::max(c->num_gate_constraints, gbk::gates::num_constraints<F>(gset.g[g], c->programs));
     auto cleanup = [&](gb_status s) { gb_circuit_free(c); return s; };
     const size_t n = (size_t)1 << lg;
     const size_t ncs = cfg->num_selectors + cfg->num_constants + cfg->num_routed_wires;
@@ -301,6 +431,13 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
     for (T k : k_canon) c->k_is_dev_host.push_back(F::enc(k));
     if ((s = upload_owned(ctx, c->k_is_dev_host, &c->k_is, &c->owned))) return cleanup(s);
     if ((s = upload_owned(ctx, std::vector<u32>(1, 0u), &c->perm_err, &c->owned))) return cleanup(s);
+    if (c->programs.num_programs) {   // the tables k_gate_programs reads (an empty table still gets a valid one-word allocation)
+        std::vector<T> lits(c->prog_lits.begin(), c->prog_lits.end());
+        if (lits.empty()) lits.push_back(F::zero());
+        const std::vector<u64> no_instrs(1, 0);
+        if ((s = upload_owned(ctx, c->prog_instrs.empty() ? no_instrs : c->prog_instrs, &c->prog_instrs_dev, &c->owned))) return cleanup(s);
+        if ((s = upload_owned(ctx, lits, &c->prog_lits_dev, &c->owned))) return cleanup(s);
+    }
     // compute_quotient_polys works on every step-th point of the LDE, step = 2^(rate_bits - quotient_degree_bits)
     // (plonk/prover.rs:735-749): in leaf order those are the first 2^qb coset blocks of a column, so everything the quotient stage
     // needs - domain powers, Z_H on the cosets, L_0, the combine matrix of the coset_ifft - is the rate-qb table
@@ -479,7 +616,9 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
         gbk::GateParams<F> gp{lg, qb, nch, nterms, t0, c->gates, lg + r};
         const T* apow_dev = uni_dev + 2 * (size_t)nch + (size_t)nch * nr;
         const T* pi_dev = apow_dev + (size_t)nch * nterms + 2 * ((size_t)1 << qb);
-        if (!gbk::gate_constraints<F>(gp, (const T*)c->cs->lde, (const T*)wires->lde, apow_dev, pi_dev, qv, st))
+        const gbk::ProgramParams<F> pp{c->programs, c->prog_instrs_dev, c->prog_lits_dev};
+        if (!gbk::gate_constraints<F>(gp, (const T*)c->cs->lde, (const T*)wires->lde, apow_dev, pi_dev, qv, st,
+                                      c->programs.num_programs ? &pp : nullptr))
             return fail(ctx, GB_ERR_UNSUPPORTED, "no gate-constraint kernel for this num_challenges");
     }
     if (!gbk::quotient_values<F>(qp, (const T*)c->cs->lde, (const T*)wires->lde, (const T*)zs->lde, uni_dev, qv, st))
@@ -1405,7 +1544,7 @@ static gb_status abi_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, u
 // CommonCircuitData.gates + selectors_info -> GateSet, with the shape checks the reference's builder guarantees
 template <class F>
 static gb_status build_gate_set(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
-                                gbk::gates::GateSet* out) {
+                                gbk::gates::GateSet* out, const gbk::gates::ProgramSet* programs = nullptr) {
     typedef typename F::T T;
     namespace G = gbk::gates;
     if (!gates || num_gates == 0) return fail(ctx, GB_ERR_INVALID, "No gates?");
@@ -1463,13 +1602,28 @@ static gb_status build_gate_set(gb_ctx* ctx, const gb_circuit_config* cfg, const
                     return fail(ctx, GB_ERR_INVALID, name + ": CosetInterpolationGate degree is not the one with_max_degree() yields");
                 break;
             }
+            case GB_GATE_PROGRAM: {
+                if (!programs)
+                    return fail(ctx, GB_ERR_INVALID, name + ": a program gate needs the program table of gb_circuit_create_programs / gb_verifier_create_programs");
+                if (d.param >= programs->num_programs)
+                    return fail(ctx, GB_ERR_INVALID, name + ": program " + std::to_string(d.param) + " of " + std::to_string(programs->num_programs));
+                // the bound selectors.rs:125-209 keeps for every gate it groups: gate degree + filter degree <= max degree
+                const u32 filter_deg = d.group_end - d.group_start - 1 + (cfg->num_selectors > 1 ? 1 : 0);
+                if ((u64)programs->p[d.param].degree + filter_deg > (u64)cfg->max_quotient_degree_factor + 1)
+                    return fail(ctx, GB_ERR_INVALID, name + ": program " + std::to_string(d.param) + " of degree " +
+                                std::to_string(programs->p[d.param].degree) + " with a filter of degree " + std::to_string(filter_deg) +
+                                " exceeds max_quotient_degree_factor + 1 = " + std::to_string(cfg->max_quotient_degree_factor + 1));
+                break;
+            }
             default:
                 return fail(ctx, GB_ERR_UNSUPPORTED, name + ": kind " + std::to_string(d.kind) + " has no constraint evaluator (csrc/gates.hpp)");
         }
         if (needs_param && d.param == 0) return fail(ctx, GB_ERR_INVALID, name + ": param 0");
         if (d.kind == GB_GATE_BASE_SUM && G::base_sum_base(d) > cfg->max_quotient_degree_factor)
             return fail(ctx, GB_ERR_INVALID, name + ": BaseSumGate base exceeds the quotient degree factor");
-        const u32 wires = G::num_wires<F>(d), consts = G::num_constants<F>(d);
+        static const G::ProgramSet no_programs{};
+        const G::ProgramSet& ps = programs ? *programs : no_programs;
+        const u32 wires = G::num_wires<F>(d, ps), consts = G::num_constants<F>(d, ps);
         if (wires > cfg->num_wires || consts > cfg->num_constants)
             return fail(ctx, GB_ERR_INVALID, name + " needs " + std::to_string(wires) + " wires / " + std::to_string(consts) +
                         " constants, the config has " + std::to_string(cfg->num_wires) + " / " + std::to_string(cfg->num_constants));
@@ -1489,10 +1643,13 @@ static gb_status build_gate_set(gb_ctx* ctx, const gb_circuit_config* cfg, const
 // CommonCircuitData + VerifierOnlyCircuitData -> a circuit object that can only verify (no device state; ctx may be NULL)
 template <class F>
 static gb_status verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates, const void* k_is,
-                                 const void* cap, const void* digest, gb_circuit** out) {
+                                 const void* cap, const void* digest, gb_circuit** out, const ProgramTable* table = nullptr) {
     typedef typename F::T T;
     gbk::gates::GateSet gs{};
-    if (gb_status s = build_gate_set<F>(ctx, cfg, gates, num_gates, &gs)) return s;
+    ParsedPrograms progs;
+    if (table)
+        if (gb_status s = parse_programs<F>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs)) return s;
+    if (gb_status s = build_gate_set<F>(ctx, cfg, gates, num_gates, &gs, table ? &progs.set : nullptr)) return s;
     Circuit<F>* c = new (std::nothrow) Circuit<F>();
     if (!c) return fail(ctx, GB_ERR_OOM, "host allocation failed");
     c->field = F::TAG;
@@ -1501,8 +1658,9 @@ static gb_status verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, cons
     c->gates = gs;
     c->general_gates = true;
     c->verify_only = true;
+    progs.move_to(c);
     for (u32 g = 0; g < gs.num_gates; g++)
-        c->num_gate_constraints = std::max(c->num_gate_constraints, gbk::gates::num_constraints<F>(gs.g[g]));
+        c->num_gate_constraints = std::max(c->num_gate_constraints, gbk::gates::num_constraints<F>(gs.g[g], c->programs));
     const T* k = static_cast<const T*>(k_is);
     for (u32 j = 0; j < cfg->num_routed_wires; j++) c->k_is_dev_host.push_back(F::enc(k[j]));
     c->cap_host.assign(static_cast<const T*>(cap), static_cast<const T*>(cap) + ((size_t)F::H << cfg->cap_height));
@@ -1608,14 +1766,21 @@ gb_status gb_circuit_create_cols(gb_ctx* ctx, const gb_circuit_config* cfg, cons
 } GB_CATCH(ctx)
 
 static gb_status circuit_create_general(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
-                                        ColSrc constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out) {
+                                        ColSrc constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out,
+                                        const ProgramTable* table = nullptr) {
     if (gb_status s = check_circuit_cfg(ctx, cfg, constants_sigmas, k_is, flags, out)) return s;
     gbk::gates::GateSet gs{};
-    if (gb_status s = cfg->field == GB_GOLDILOCKS ? build_gate_set<GlF>(ctx, cfg, gates, num_gates, &gs)
-                                                 : build_gate_set<BbF>(ctx, cfg, gates, num_gates, &gs))
+    ParsedPrograms progs;
+    const bool gl = cfg->field == GB_GOLDILOCKS;
+    if (table)
+        if (gb_status s = gl ? parse_programs<GlF>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs)
+                             : parse_programs<BbF>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs))
+            return s;
+    const gbk::gates::ProgramSet* ps = table ? &progs.set : nullptr;
+    if (gb_status s = gl ? build_gate_set<GlF>(ctx, cfg, gates, num_gates, &gs, ps) : build_gate_set<BbF>(ctx, cfg, gates, num_gates, &gs, ps))
         return s;
-    return cfg->field == GB_GOLDILOCKS ? circuit_create<GlF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out)
-                                       : circuit_create<BbF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out);
+    return gl ? circuit_create<GlF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out, &progs)
+              : circuit_create<BbF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out, &progs);
 }
 
 gb_status gb_circuit_create_gates(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
@@ -1627,8 +1792,23 @@ gb_status gb_circuit_create_gates_cols(gb_ctx* ctx, const gb_circuit_config* cfg
     return circuit_create_general(ctx, cfg, gates, num_gates, ColSrc::columns(constants_sigmas_cols), k_is, flags, out);
 } GB_CATCH(ctx)
 
-gb_status gb_verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates, const void* k_is,
-                             const void* constants_sigmas_cap, const void* circuit_digest, gb_circuit** out) try {
+gb_status gb_circuit_create_programs(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                     const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                     const void* constants_sigmas, const void* k_is, uint32_t flags, gb_circuit** out) try {
+    const ProgramTable table{program_words, program_offsets, num_programs};
+    return circuit_create_general(ctx, cfg, gates, num_gates, constants_sigmas, k_is, flags, out, &table);
+} GB_CATCH(ctx)
+gb_status gb_circuit_create_programs_cols(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                          const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                          const void* const* constants_sigmas_cols, const void* k_is, uint32_t flags,
+                                          gb_circuit** out) try {
+    const ProgramTable table{program_words, program_offsets, num_programs};
+    return circuit_create_general(ctx, cfg, gates, num_gates, ColSrc::columns(constants_sigmas_cols), k_is, flags, out, &table);
+} GB_CATCH(ctx)
+
+static gb_status verifier_create_checked(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                         const void* k_is, const void* constants_sigmas_cap, const void* circuit_digest,
+                                         gb_circuit** out, const ProgramTable* table) {
     if (!cfg || !k_is || !constants_sigmas_cap || !circuit_digest || !out) return fail(ctx, GB_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->field != GB_GOLDILOCKS && cfg->field != GB_BABYBEAR) return fail(ctx, GB_ERR_INVALID, "unknown field tag");
@@ -1636,8 +1816,19 @@ gb_status gb_verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb
         cfg->max_quotient_degree_factor == 0 || cfg->arity_bits > 8 || cfg->cap_height > 24 ||
         cfg->degree_bits + cfg->rate_bits > (cfg->field == GB_GOLDILOCKS ? 32u : 27u) || cfg->num_wires > 4096)
         return fail(ctx, GB_ERR_INVALID, "bad circuit config");
-    return cfg->field == GB_GOLDILOCKS ? verifier_create<GlF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out)
-                                       : verifier_create<BbF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out);
+    return cfg->field == GB_GOLDILOCKS ? verifier_create<GlF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, table)
+                                       : verifier_create<BbF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, table);
+}
+gb_status gb_verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates, const void* k_is,
+                             const void* constants_sigmas_cap, const void* circuit_digest, gb_circuit** out) try {
+    return verifier_create_checked(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, nullptr);
+} GB_CATCH(ctx)
+gb_status gb_verifier_create_programs(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
+                                      const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                      const void* k_is, const void* constants_sigmas_cap, const void* circuit_digest,
+                                      gb_circuit** out) try {
+    const ProgramTable table{program_words, program_offsets, num_programs};
+    return verifier_create_checked(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, &table);
 } GB_CATCH(ctx)
 
 gb_status gb_circuit_free(gb_circuit* c) try {

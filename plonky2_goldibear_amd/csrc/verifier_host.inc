@@ -491,11 +491,19 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
             for (u32 i = 0; i < H; i++) pi_dev[i] = F::enc(pi_hash[i]);
             auto wire = [&](u32 col) { return o_w[col]; };
             auto konst = [&](u32 i) { return o_const[cfg.num_selectors + i]; };
+            const std::vector<T> prog_lits(c->prog_lits.begin(), c->prog_lits.end());   // device form, the field's word
+            std::vector<E> prog_regs(gbk::gates::MAX_PROGRAM_REGS, F::ezero());
             for (u32 g = 0; g < c->gates.num_gates; g++) {
                 const gb_gate& gd = c->gates.g[g];
                 const E f = gbk::gates::filter<F, A>(g, gd, o_const[gd.selector_index], c->gates.num_selectors > 1);
                 u32 idx = 0;
                 auto emit = [&](E v) { cons[idx] = F::eadd(cons[idx], F::emul(f, v)); idx++; };
+                if (gbk::gates::is_program(gd)) {   // the gate as data: the interpreter the quotient kernel runs, over the extension
+                    const gbk::gates::ProgramInfo& pi = c->programs.p[gd.param];
+                    gbk::gates::run_program<F, A>(c->prog_instrs.data() + pi.instr_off, pi.num_instrs, prog_lits.data() + pi.lit_off,
+                                                  gbk::gates::ArrayRegs<E>{prog_regs.data()}, wire, konst, emit);
+                    continue;
+                }
                 gbk::gates::eval_gate<F, A>(c->gates, gd, wire, konst, pi_dev, emit);
             }
             terms.insert(terms.end(), cons.begin(), cons.end());

@@ -67,6 +67,9 @@ SIGNATURES = {
     "gb_circuit_create_gates": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _pvp]),
     "gb_circuit_create_cols": (_i32, [_vp, _vp, _cols, _vp, _u32, _pvp]),
     "gb_circuit_create_gates_cols": (_i32, [_vp, _vp, _vp, _u32, _cols, _vp, _u32, _pvp]),
+    "gb_circuit_create_programs": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(_u32), _u32, _vp, _vp, _u32, _pvp]),
+    "gb_circuit_create_programs_cols": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(_u32), _u32, _cols, _vp, _u32, _pvp]),
+    "gb_verifier_create_programs": (_i32, [_vp, _vp, _vp, _u32, C.POINTER(_u64), C.POINTER(_u32), _u32, _vp, _vp, _vp, _pvp]),
     "gb_circuit_free": (_i32, [_vp]),
     "gb_circuit_verifier_data": (_i32, [_vp, _vp, _vp]),
     "gb_circuit_constants_sigmas_commitment": (_i32, [_vp, _pvp]),

@@ -35,6 +35,12 @@ class gb_gate(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("kind", "param", "selector_index", "group_start", "group_end", "param2", "param3")]
 
 
+def _program_table(programs):
+    """gate_program.pack_programs: the flat word and offset arrays of the *_programs entry points"""
+    from .gate_program import pack_programs
+    return pack_programs(programs)
+
+
 class _ProofBytesOps:
     """compress / decompress / verify_compressed over the C ABI (plonk/proof.rs:96-140, 183-265), shared by CircuitData and
     VerifierCircuitData; all three run on the host."""
@@ -88,11 +94,14 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
     def __init__(self, ctx, degree_bits, constants_sigmas, k_is, *, num_wires=135, num_routed_wires=80, num_constants=2,
                  num_challenges=2, max_quotient_degree_factor=8, rate_bits=3, cap_height=4, proof_of_work_bits=16,
                  num_query_rounds=28, arity_bits=4, final_poly_bits=5, num_selectors=1, gate_constant=1, gate_pi=2,
-                 field=N.GB_GOLDILOCKS, gates=None, zero_knowledge=False, num_public_inputs=0, reduction_arity_bits=None, p3_repr=False):
+                 field=N.GB_GOLDILOCKS, gates=None, zero_knowledge=False, num_public_inputs=0, reduction_arity_bits=None, p3_repr=False,
+                 programs=None):
         """`gates` = None: the dummy circuit's gate set, given by the selector values gate_constant / gate_pi
         (gb_circuit_create).  Otherwise CommonCircuitData.gates with selectors_info, one tuple
         (kind, param, selector_index, group_start, group_end) per gate in sorted order (gb_circuit_create_gates; what
-        circuit_builder.CircuitBuilder.build() passes); num_constants then counts the constant columns after the selectors."""
+        circuit_builder.CircuitBuilder.build() passes); num_constants then counts the constant columns after the selectors.
+        `programs`: the constraint programs of the GATE_PROGRAM entries (gate_program.GateProgram objects or their words), entry
+        `param` of a program gate indexing this list (gb_circuit_create_programs)."""
         self.ctx, self._lib = ctx, ctx._lib
         self.field, self._dt = field, _dtype(field)
         hout = 4 if field == N.GB_GOLDILOCKS else 8
@@ -120,10 +129,16 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         if gates is None:
             fn = self._lib.gb_circuit_create_cols if cs_cols else self._lib.gb_circuit_create
             N.check(fn(ctx.handle, C.byref(self.cfg), ptr, kptr, flags, C.byref(h)), ctx.handle)
-        else:
+        elif programs is None:
             arr = (gb_gate * len(gates))(*[gb_gate(*g) for g in gates])
             fn = self._lib.gb_circuit_create_gates_cols if cs_cols else self._lib.gb_circuit_create_gates
             N.check(fn(ctx.handle, C.byref(self.cfg), arr, len(gates), ptr, kptr, flags, C.byref(h)), ctx.handle)
+        else:
+            arr = (gb_gate * len(gates))(*[gb_gate(*g) for g in gates])
+            words, offsets = _program_table(programs)
+            fn = self._lib.gb_circuit_create_programs_cols if cs_cols else self._lib.gb_circuit_create_programs
+            N.check(fn(ctx.handle, C.byref(self.cfg), arr, len(gates), words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                       offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(programs), ptr, kptr, flags, C.byref(h)), ctx.handle)
         del keep, keep2
         self.handle = h
         cap = np.empty((1 << cap_height, hout), dtype=self._dt)
@@ -346,10 +361,11 @@ class VerifierCircuitData(_ProofBytesOps, _FriParamsOps):
     def __init__(self, degree_bits, gates, k_is, constants_sigmas_cap, circuit_digest, *, num_wires=135, num_routed_wires=80,
                  num_constants=2, num_challenges=2, max_quotient_degree_factor=8, rate_bits=3, cap_height=4,
                  proof_of_work_bits=16, num_query_rounds=28, arity_bits=4, final_poly_bits=5, num_selectors=1,
-                 zero_knowledge=False, field=N.GB_GOLDILOCKS, num_public_inputs=0, reduction_arity_bits=None):
+                 zero_knowledge=False, field=N.GB_GOLDILOCKS, num_public_inputs=0, reduction_arity_bits=None, programs=None):
         """`gates`: (kind, param, selector_index, group_start, group_end[, param2, param3]) per gate, sorted as in
         CommonCircuitData.gates; num_constants counts the constant columns after the selectors; reduction_arity_bits:
-        FriParams.reduction_arity_bits when the strategy is not ConstantArityBits(arity_bits, final_poly_bits)."""
+        FriParams.reduction_arity_bits when the strategy is not ConstantArityBits(arity_bits, final_poly_bits); programs: the
+        constraint programs of the GATE_PROGRAM entries, as for CircuitData (gb_verifier_create_programs)."""
         self._lib = N.load()
         self.field, self._dt = field, _dtype(field)
         hout = 4 if field == N.GB_GOLDILOCKS else 8
@@ -364,8 +380,15 @@ class VerifierCircuitData(_ProofBytesOps, _FriParamsOps):
             raise N.ShapeError(N.GB_ERR_INVALID, "k_is / constants_sigmas_cap / circuit_digest have the wrong shape")
         arr = (gb_gate * len(gates))(*[gb_gate(*g) for g in gates])
         h = C.c_void_p()
-        N.check(self._lib.gb_verifier_create(None, C.byref(self.cfg), arr, len(gates), k.ctypes.data, cap.ctypes.data,
-                                             dig.ctypes.data, C.byref(h)))
+        if programs is None:
+            N.check(self._lib.gb_verifier_create(None, C.byref(self.cfg), arr, len(gates), k.ctypes.data, cap.ctypes.data,
+                                                 dig.ctypes.data, C.byref(h)))
+        else:
+            words, offsets = _program_table(programs)
+            N.check(self._lib.gb_verifier_create_programs(None, C.byref(self.cfg), arr, len(gates),
+                                                          words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                          offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(programs),
+                                                          k.ctypes.data, cap.ctypes.data, dig.ctypes.data, C.byref(h)))
         self.handle = h
         if reduction_arity_bits is not None:
             self.set_reduction_arity_bits(reduction_arity_bits)
