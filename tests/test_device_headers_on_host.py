@@ -4,7 +4,10 @@ to be checked, and its failures would be data dependent."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
+
+import permutation_states as PS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,3 +64,26 @@ def test_host_transcript_permutation_matches_the_defining_form(tmp_path):
     out = subprocess.run([str(exe), "20000"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "mismatches=0" in out.stdout
+
+
+def test_poseidon2_bb_steps_keep_their_bounds_on_pulled_back_states(tmp_path):
+    """csrc/poseidon2_bb.hpp's permute_scaled one step at a time (tests/host_shim/poseidon2_bb_steps.cpp) on the BabyBear states of
+    tests/permutation_states.py and 50 000 random ones: the stated bounds after every step, the chosen word at its place (which
+    checks the scale sequence the Python model restates), equality with permute_scaled and with the host mirror at the end"""
+    exe = tmp_path / "poseidon2_bb_steps"
+    shim = os.path.join(ROOT, "tests", "host_shim")
+    cmd = ["g++", "-O2", "-std=c++17", "-include", os.path.join(shim, "shim.h"), "-I", shim,
+           "-I", os.path.join(ROOT, "plonky2_goldibear_amd", "csrc"), "-o", str(exe), os.path.join(shim, "poseidon2_bb_steps.cpp")]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    m = PS.model(PS.BB)
+    records = []
+    for t in PS.targets(PS.BB) + PS.zero_capacity_targets(PS.BB):
+        # one word per state: any word in the external rounds; inside the internal rounds words 1..15 carry per-round offsets
+        index = min(t.words) if m.is_full(t.round) else (0 if 0 in t.words else None)
+        records.append(list(t.input) + [2 * t.round + (t.where == PS.MDS_IN)] + ([index, t.words[index]] if index is not None else [0xFFFFFFFF, 0]))
+    probed = sum(1 for r in records if r[17] != 0xFFFFFFFF)
+    assert probed >= len(records) * 3 // 4
+    np.array(records, dtype=np.uint32).tofile(tmp_path / "states.bin")
+    out = subprocess.run([str(exe), str(tmp_path / "states.bin"), "50000"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "states=%d " % (len(records) + 50000) in out.stdout and "place_checks=%d " % probed in out.stdout and "mismatches=0" in out.stdout
