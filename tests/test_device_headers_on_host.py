@@ -87,3 +87,43 @@ def test_poseidon2_bb_steps_keep_their_bounds_on_pulled_back_states(tmp_path):
     out = subprocess.run([str(exe), str(tmp_path / "states.bin"), "50000"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "states=%d " % (len(records) + 50000) in out.stdout and "place_checks=%d " % probed in out.stdout and "mismatches=0" in out.stdout
+
+
+HOST_GATE_ROWS = 24   # past the longest list of edge words: every column has passed through all of them
+
+
+@pytest.fixture(scope="module")
+def gate_eval_exe(tmp_path_factory):
+    shim = os.path.join(ROOT, "tests", "host_shim")
+    clang = "/opt/rocm/lib/llvm/bin/clang++"   # gl_field.hpp's limb code uses clang's __builtin_addc
+    if not os.path.exists(clang):
+        pytest.skip("needs the ROCm clang++ as the host compiler")
+    exe = tmp_path_factory.mktemp("gate_eval_host") / "gate_eval"
+    cmd = [clang, "-O2", "-std=c++17", "-include", os.path.join(shim, "shim.h"), "-I", shim,
+           "-I", os.path.join(ROOT, "plonky2_goldibear_amd", "csrc"), "-o", str(exe), os.path.join(shim, "gate_eval.cpp")]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return str(exe)
+
+
+@pytest.mark.parametrize("algebra", ["base", "extension"])
+@pytest.mark.parametrize("field", [0, 1])
+def test_gate_evaluators_equal_the_oracle_over_both_algebras(gate_eval_exe, tmp_path, field, algebra):
+    """csrc/gates.hpp's eval_gate and filter over BaseAlg<F> (the quotient kernel's algebra, wires F.efrom(v)) and ExtAlg<F> (what
+    gb_verify runs at zeta: every wire, constant and selector a D-tuple of edge or random words, all D output coordinates compared)
+    == oracle/gates.py eval_unfiltered / compute_filter, for every gate of tests/gate_variants.py's grid - every parameter
+    gb_circuit_create_gates accepts, where tests/test_verifier_differential.py and the reference's fixture hold one
+    parameterisation per gate.  Also gates::num_wires / num_constraints / num_constants against recursion_gates.py's figures and
+    the oracle's num_constraints, for the whole grid."""
+    import gate_variants as GV
+    F = GV.FIELDS[field]
+    width = 1 if algebra == "base" else F.D
+    entries = GV.cases(field, width, HOST_GATE_ROWS)
+    assert len(entries) == GV.GRID_SIZE[field] == {0: 89, 1: 90}[field]   # no entry drops out silently
+    assert HOST_GATE_ROWS > len(GV.edge_values(F)) + 3
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    GV.pack(field, HOST_GATE_ROWS, width, entries).tofile(src)
+    out = subprocess.run([gate_eval_exe, str(src), str(dst)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, (out.returncode, out.stdout + out.stderr)
+    assert "gates=%d rows=%d width=%d" % (len(entries), HOST_GATE_ROWS, width) in out.stdout
+    bad = GV.compare(field, HOST_GATE_ROWS, width, entries, np.fromfile(dst, dtype=np.uint64))
+    assert not bad, "\n".join(bad[:10])

@@ -113,3 +113,21 @@ def test_unsupported_and_malformed_gates(ctx):
     with pytest.raises(N.GoldibearError):   # PoseidonMdsGate is Goldilocks only
         CircuitData.babybear(ctx, 3, np.zeros((1 + 2 + 41, 8), dtype=np.uint32), np.ones(41, dtype=np.uint32),
                              gates=[(0, 0, 0, 0, 2, 0, 0), (12, 0, 0, 0, 2, 0, 0)], num_selectors=1)
+
+
+@pytest.mark.parametrize("field", [N.GB_GOLDILOCKS, N.GB_BABYBEAR])
+def test_what_create_accepts_and_refuses(ctx, field):
+    """The table of tests/gate_variants.py acceptance_cases through gb_circuit_create_gates: CosetInterpolationGate at bits 1..5 x
+    degree 1..2^bits + 1 accepted exactly at bits <= 4 with a degree with_max_degree() yields (computed in Python), RandomAccessGate
+    at bits 0..6 accepted when the wires fit, bits 7 and no copies refused, BaseSumGate base 8 accepted and base 9 refused at
+    max_quotient_degree_factor 8, a gate with more wires than the config refused with "needs"."""
+    import gate_variants as GV
+    from plonky2_goldibear_amd.prover import CircuitData
+    if field == N.GB_GOLDILOCKS:
+        create = lambda gates: CircuitData(ctx, 3, np.zeros((1 + 2 + 80, 8), dtype=np.uint64), np.ones(80, dtype=np.uint64), gates=gates,
+                                           num_selectors=1)
+    else:
+        create = lambda gates: CircuitData.babybear(ctx, 3, np.zeros((1 + 2 + 41, 8), dtype=np.uint32), np.ones(41, dtype=np.uint32),
+                                                    gates=gates, num_selectors=1)
+    seen = GV.check_acceptance(field, create)
+    assert seen["ok"] >= 25 and seen["refused"] >= 50 and seen["needs"] >= 5, seen
