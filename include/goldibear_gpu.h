@@ -374,6 +374,47 @@ gb_status gb_prove_salted(gb_circuit* c, const void* witness, uint32_t flags, co
 gb_status gb_prove_salted_cols(gb_circuit* c, const void* const* wire_cols, uint32_t flags, const uint64_t* public_inputs,
                                size_t num_public_inputs, const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len);
 
+/* ---- prove() from the partition witness --------------------------------------------------------------------------------------
+ * prove_with_partition_witness (plonk/prover.rs:160-183) does not hold MatrixWitness.wire_values when it is called: it holds a
+ * PartitionWitness (iop/witness.rs:318-372) - one value per copy class in `values` - and ProverOnlyCircuitData.representative_map
+ * (plonk/circuit_data.rs:454), and its first timed step, "compute full witness", is partition_witness.full_witness()
+ * (iop/witness.rs:359-371): a single-threaded loop over degree x num_wires targets, each a dependent read through the map.  The
+ * functions below take those two objects as they are and build the matrix on the device, so that one value per CLASS crosses to
+ * the device, not one per wire.
+ *
+ * gb_circuit_set_partition, once after gb_circuit_create*: representative_map[num_targets] is the reference's Vec<usize>, indexed
+ * by Target::index (iop/target.rs:55-60): wire (row, column) -> row * num_wires + column, virtual target i -> degree * num_wires
+ * + i; public_input_targets holds the indices of prover_data.public_inputs.  GB_ERR_INVALID: num_targets < degree * num_wires, a
+ * map entry or a public-input target >= num_targets, num_public_inputs != cfg.num_public_inputs; GB_ERR_UNSUPPORTED:
+ * num_targets >= 2^32.  The library keeps the representatives that wire cells actually use ("slots", ranked in ascending target
+ * index) on the host and a 32-bit slot per wire cell on the device; a representative no wire cell uses - most virtual targets -
+ * gets no slot.  Calling it again replaces the map. */
+gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative_map, uint64_t num_targets,
+                                   const uint64_t* public_input_targets, size_t num_public_inputs);
+/* gb_prove / gb_prove_salted from the partition witness: values[num_targets], entry i = partition_witness.values[i]
+ * .unwrap_or(ZERO), canonical words or with GB_INPUT_P3_REPR the field types' in-memory words.  A HOST pointer:
+ * GB_INPUT_DEVICE is GB_ERR_INVALID.  salts: NULL unless the circuit is zero-knowledge, otherwise as for gb_prove_salted (host).
+ * The public inputs are read from `values` through the map (get_targets, prover.rs:177).  Result, errors and proof bytes are those
+ * of gb_prove / gb_prove_salted on the matrix full_witness() would build - GB_ERR_PERM_ARG_ZERO included; a value >= p in an
+ * entry that a wire cell or a public input reads is GB_ERR_INVALID ("non-canonical witness element"), entries nothing reads are
+ * not looked at.  Before gb_circuit_set_partition: GB_ERR_INVALID.  Timing scope: "compute full witness", the reference's name,
+ * around compaction, upload and expansion (its parts: "partition compaction", "partition upload", "partition expansion"). */
+gb_status gb_prove_partition(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out, size_t proof_cap,
+                             size_t* proof_len);
+/* The second or third attempt of prover.rs:186-226 after GB_ERR_PERM_ARG_ZERO: the caller has re-drawn
+ * values[representative_map[row * num_wires + wire]] - prover_data.random_wire - and changed nothing else.  Same bytes and errors
+ * as gb_prove_partition(values).  Where the failed attempt left its state behind (see gb_prove_retry) and that cell is alone in
+ * its class, as the random wire is, the value goes into the device matrix the failed attempt kept, that one column is transformed
+ * again and the last absorption of the leaf sponges and the tree are re-hashed; anything else is the full computation.
+ * A witness that violates a copy constraint - the gb_prove tests' "broken copy class" - cannot be expressed here: every cell of a
+ * class reads the same entry of `values`. */
+gb_status gb_prove_partition_retry(gb_circuit* c, const void* values, uint32_t flags, uint32_t wire, uint64_t row, void* proof_out,
+                                   size_t proof_cap, size_t* proof_len);
+/* full_witness() on its own, for a host that keeps the prover loop: writes the canonical [num_wires][n] matrix to witness_dev_out,
+ * a DEVICE buffer of the caller (16-byte aligned), on the context's stream - ready as the GB_INPUT_DEVICE input of
+ * gb_commit_values and gb_zs_partial_products on the same context.  `values` is the caller's again on return. */
+gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags, void* witness_dev_out);
+
 /* verify() of a proof produced for this circuit (plonk/verifier.rs:17-128, fri/verifier.rs:67-250,
  * plonk/get_challenges.rs:26-101), restated for the dummy gate set and run on the HOST like the reference's verifier: the
  * Fiat-Shamir replay, vanishing(zeta) == Z_H(zeta) * quotient(zeta), the proof of work, every Merkle path and the FRI

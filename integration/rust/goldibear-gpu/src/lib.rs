@@ -118,6 +118,13 @@ extern "C" {
                             proof_len: *mut usize) -> i32;
     fn gb_zs_partial_products_cols(c: *mut gb_circuit, wire_cols: *const *const c_void, flags: u32, betas: *const c_void,
                                    gammas: *const c_void, values_out: *mut c_void) -> i32;
+    fn gb_circuit_set_partition(c: *mut gb_circuit, representative_map: *const u64, num_targets: u64,
+                                public_input_targets: *const u64, num_public_inputs: usize) -> i32;
+    fn gb_prove_partition(c: *mut gb_circuit, values: *const c_void, flags: u32, salts: *const c_void, proof_out: *mut c_void,
+                          proof_cap: usize, proof_len: *mut usize) -> i32;
+    fn gb_prove_partition_retry(c: *mut gb_circuit, values: *const c_void, flags: u32, wire: u32, row: u64, proof_out: *mut c_void,
+                                proof_cap: usize, proof_len: *mut usize) -> i32;
+    fn gb_expand_partition(c: *mut gb_circuit, values: *const c_void, flags: u32, witness_dev_out: *mut c_void) -> i32;
     fn gb_commit_values(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
                         cap_height: u32, salts: *const c_void, flags: u32, out: *mut *mut gb_batch) -> i32;
     fn gb_commit_coeffs(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
@@ -891,6 +898,42 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         }
         check(self.ctx.0, st)?;
         Ok(Some(out))
+    }
+    /// `ProverOnlyCircuitData.representative_map` (plonk/circuit_data.rs:454, a `Vec<usize>` indexed by `Target::index`) and the
+    /// target indices of `prover_data.public_inputs`, once after the circuit is created: what `prove_partition` expands through.
+    pub fn set_partition(&self, representative_map: &[usize], public_input_targets: &[usize]) -> Result<(), GpuError> {
+        let map: Vec<u64> = representative_map.iter().map(|&t| t as u64).collect();
+        let pis: Vec<u64> = public_input_targets.iter().map(|&t| t as u64).collect();
+        check(self.ctx.0, unsafe { gb_circuit_set_partition(self.handle, map.as_ptr(), map.len() as u64, pis.as_ptr(), pis.len()) })
+    }
+    /// `prove_with_partition_witness` from the `PartitionWitness` itself (plonk/prover.rs:160-183): `values[i]` =
+    /// `partition_witness.values[i].unwrap_or(F::ZERO)`; `full_witness()` runs on the device.  `salts`: zero-knowledge circuits only.
+    pub fn prove_partition(&self, values: &[W], salts: Option<&[W]>, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        let mut buf = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let st = unsafe {
+            gb_prove_partition(self.handle, values.as_ptr() as *const c_void, repr.flags(),
+                               salts.map_or(std::ptr::null(), |s| s.as_ptr() as *const c_void), buf.as_mut_ptr() as *mut c_void, buf.len(),
+                               &mut len)
+        };
+        self.finish_proof(st, buf, len)
+    }
+    /// The retry (prover.rs:186-226): `values[representative_map[row * num_wires + wire]]` - the random wire - re-drawn, nothing else.
+    pub fn prove_partition_retry(&self, values: &[W], wire: usize, row: usize, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        let mut buf = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let st = unsafe {
+            gb_prove_partition_retry(self.handle, values.as_ptr() as *const c_void, repr.flags(), wire as u32, row as u64,
+                                     buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
+        };
+        self.finish_proof(st, buf, len)
+    }
+    /// `full_witness()` alone into a device buffer of the caller ([num_wires][n] canonical words), on the context's stream.
+    ///
+    /// # Safety
+    /// `witness_dev_out` must be a device allocation of num_wires * n elements on this context's device.
+    pub unsafe fn expand_partition(&self, values: &[W], repr: Repr, witness_dev_out: *mut c_void) -> Result<(), GpuError> {
+        check(self.ctx.0, gb_expand_partition(self.handle, values.as_ptr() as *const c_void, repr.flags(), witness_dev_out))
     }
     /// Give up after `PermArgZero` (`ProverError::TooManyPermArgFailures`, prover.rs:221-225): releases what the failed attempt
     /// left on the device for `prove_retry` (~12 GB at 2^20 Goldilocks rows).  No-op when nothing is held.

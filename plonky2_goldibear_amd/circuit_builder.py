@@ -658,7 +658,9 @@ class CircuitBuilder:
                        getattr(g, "param2", 0), getattr(g, "param3", 0)) for i, g in enumerate(gates)]
         return BuiltCircuit(ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, len(groups), max_constants, gens, find,
                             list(self.public_inputs), self.random_wire, [g.id for g in gates],
-                            sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None)
+                            sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None,
+                            copy_targets=sorted({t for ab in self.copy_constraints for t in ab}),
+                            num_virtual_targets=self.virtual_target_index)
 
     def _forest(self):
         """Disjoint sets over the targets that appear in copy constraints (plonk/permutation_argument.rs:13-101)."""
@@ -729,12 +731,16 @@ class BuiltCircuit:
     """CircuitData (plonk/circuit_data.rs:153-300) for a built circuit: prove(PartialWitness) / verify(proof)."""
 
     def __init__(self, ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, num_selectors, max_constants, generators, find,
-                 public_inputs, random_wire, gate_ids, copy_wires, programs=None):
+                 public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0):
         self.config, self.F, self.degree_bits, self.programs = cfg, F, degree_bits, programs
         self.constants_sigmas, self.k_is, self.gate_table, self.gate_ids = constants_sigmas, k_is, gate_table, gate_ids
         self.num_selectors, self.max_constants = num_selectors, max_constants
         self.generators, self.find, self.public_inputs, self.random_wire = generators, find, public_inputs, random_wire
         self.copy_wires = copy_wires
+        # every target a copy constraint names (wires and virtual targets) and the count of virtual targets: what
+        # representative_map is built from
+        self.copy_targets, self.num_virtual_targets = copy_targets, num_virtual_targets
+        self._representative_map, self._partition_set = None, False
         self.data = None
         if ctx is not None:
             from .prover import CircuitData
@@ -747,9 +753,8 @@ class BuiltCircuit:
                                     gates=gate_table, num_public_inputs=len(public_inputs),
                                     reduction_arity_bits=cfg.reduction_arity_bits(degree_bits), programs=programs)
 
-    def generate_witness(self, pw, rng=None):
-        """generate_partial_witness + full_witness (iop/generator.rs:25-117, iop/witness.rs:359-371)
-        -> (wire_values [num_wires][n], public input values)"""
+    def _run_generators(self, pw, rng=None):
+        """generate_partial_witness (iop/generator.rs:25-117) -> the partition witness: one value per copy class"""
         p = self.F.p
         w = _PartitionWitness(self.find, p, rng or np.random.default_rng(0))
         for t, v in pw.values.items():
@@ -765,6 +770,12 @@ class BuiltCircuit:
             if len(rest) == len(pending):
                 break   # the remaining generators wait on targets nobody sets; their wires stay zero like unset wires
             pending = rest
+        return w
+
+    def generate_witness(self, pw, rng=None):
+        """generate_partial_witness + full_witness (iop/generator.rs:25-117, iop/witness.rs:359-371)
+        -> (wire_values [num_wires][n], public input values)"""
+        w = self._run_generators(pw, rng)
         # full_witness: every wire carries the value of its copy class; unset wires are zero
         wires = np.zeros((self.config.num_wires, 1 << self.degree_bits), dtype=self.F.dtype)
         for rep, v in w.v.items():
@@ -776,10 +787,53 @@ class BuiltCircuit:
                 wires[t[2], t[1]] = w.v[r]
         return wires, [w.get(t) for t in self.public_inputs]
 
+    # ---- the partition witness as the reference holds it (iop/witness.rs:318-372, plonk/circuit_data.rs:454)
+    def target_index(self, t):
+        """Target::index (iop/target.rs:55-60): wire (row, column) -> row * num_wires + column, virtual i -> n * num_wires + i"""
+        if t[0] == "w":
+            return t[1] * self.config.num_wires + t[2]
+        return (self.config.num_wires << self.degree_bits) + t[1]
+
+    @property
+    def num_targets(self):
+        return (self.config.num_wires << self.degree_bits) + self.num_virtual_targets
+
+    @property
+    def representative_map(self):
+        """ProverOnlyCircuitData.representative_map: target index -> the index of its copy class's representative"""
+        if self._representative_map is None:
+            m = np.arange(self.num_targets, dtype=np.uint64)
+            for t in self.copy_targets:
+                m[self.target_index(t)] = self.target_index(self.find(t))
+            self._representative_map = m
+        return self._representative_map
+
+    @property
+    def public_input_targets(self):
+        return np.array([self.target_index(t) for t in self.public_inputs], dtype=np.uint64)
+
+    def generate_partition_witness(self, pw, rng=None):
+        """generate_partial_witness (iop/generator.rs:25-117) -> PartitionWitness.values as a dense array, one entry per target:
+        the class's value at its representative, zero everywhere else (unwrap_or(ZERO)).  No expansion: full_witness() is
+        gb_prove_partition's first step."""
+        w = self._run_generators(pw, rng)
+        values = np.zeros(self.num_targets, dtype=self.F.dtype)
+        for rep, v in w.v.items():
+            values[self.target_index(rep)] = v
+        return values
+
     def prove(self, pw, rng=None):
-        wires, pis = self.generate_witness(pw, rng)
-        col_row = (self.random_wire[1], self.random_wire[0]) if self.random_wire else None
-        return self.data.prove(wires, pis, random_wire=col_row, rng=rng)
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        if not self._partition_set:
+            self.data.set_partition(self.representative_map, self.public_input_targets)
+            self._partition_set = True
+        values = self.generate_partition_witness(pw, rng)
+        col_row = rep = None
+        if self.random_wire:
+            col_row = (self.random_wire[1], self.random_wire[0])
+            rep = self.representative_map[self.target_index(wire(*self.random_wire))]
+        return self.data.prove_partition(values, representative=rep, random_wire=col_row, rng=rng)
 
     def verify(self, proof):
         return self.data.verify(proof)

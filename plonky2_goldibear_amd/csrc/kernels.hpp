@@ -115,6 +115,10 @@ void bitrev_copy(const typename F::T* src, typename F::T* dst, u32 bits, size_t 
 // any word -> the residue below p, in place (GB_INPUT_P3_REPR: the words of the reference's field types from a host)
 template <class F>
 void reduce_words(typename F::T* p, size_t count, hipStream_t stream);
+// PartitionWitness::full_witness (kernels_partition.hip, partition_expand.hpp): out[col][row] = staged[slots[row][col]] - slots
+// [2^log_n][num_wires] row-major, out [num_wires][2^log_n]; words are copied as they are
+template <class F>
+void expand_partition(const u32* slots, const typename F::T* staged, typename F::T* out, u32 log_n, u32 num_wires, hipStream_t stream);
 
 // ---------------------------------------------------------------- stand-alone transforms and trees (kernels_poly.hip)
 // The transform passes move canonical words and convert nothing (the transforms are linear and multiply by table values only:

@@ -9,6 +9,7 @@
 #include <array>
 
 #include "gates.hpp"
+#include "partition_map.hpp"
 
 struct gb_circuit {
     uint32_t field = 0;
@@ -37,11 +38,37 @@ struct gb_circuit {
         size_t wit_mont_cols = 0;   // BabyBear: columns below this are in Montgomery form in wit_vals, the rest canonical (commit())
         SegKeep seg;
     } retry;
+    // gb_circuit_set_partition: ProverOnlyCircuitData.representative_map as the slot map of partition_map.hpp - the ascending
+    // representatives and the public inputs' on the host, a u32 slot per wire cell on the device - and what gb_prove_partition
+    // works with: page-locked staging for the compacted values, and the expanded canonical matrix of an attempt that ended in
+    // InvZeroPermArg (the "device witness" gb_prove_partition_retry re-draws one cell of; released with the retry state).
+    struct Partition {
+        bool set = false;
+        std::vector<uint32_t> reps, pi_reps;
+        std::vector<uint64_t> shared;
+        uint64_t num_targets = 0;
+        uint32_t* slots_dev = nullptr;
+        void* staged_host = nullptr;
+        size_t staged_host_bytes = 0;
+        hipEvent_t staged_read = nullptr;   // recorded behind the upload out of staged_host
+        void* matrix = nullptr;
+        size_t matrix_bytes = 0;
+        bool is_shared_slot(uint32_t k) const { return (shared[k >> 6] >> (k & 63)) & 1; }
+    } part;
     void drop_retry() {
         if (retry.wires) gb_batch_free(retry.wires);
         if (ctx && retry.wit_vals) pool_free(ctx, retry.wit_vals, retry.wit_bytes);
         if (ctx && retry.seg.state) pool_free(ctx, retry.seg.state, retry.seg.bytes);
         retry = RetryKeep{};
+        if (ctx && part.matrix) pool_free(ctx, part.matrix, part.matrix_bytes);
+        part.matrix = nullptr;
+        part.matrix_bytes = 0;
+    }
+    void drop_partition() {   // (the caller has waited for the stream)
+        if (part.slots_dev) (void)hipFree(part.slots_dev);
+        if (part.staged_host) (void)hipHostFree(part.staged_host);
+        if (part.staged_read) (void)hipEventDestroy(part.staged_read);
+        part = Partition{};
     }
     void attach(gb_ctx* cx) {
         ctx = cx;
@@ -1670,6 +1697,171 @@ static gb_status verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, cons
     return GB_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the partition witness
+// prove_with_partition_witness's first timed step, "compute full witness" = partition_witness.full_witness() (plonk/prover.rs:
+// 160-183, iop/witness.rs:359-371), from the reference's own object: `values` holds PartitionWitness.values (None as zero), one
+// entry per target.  Compaction staged[k] = values[reps[k]] (reps ascending: one streaming pass, canonicalised and range-checked as
+// it goes, by the context's copy threads into page-locked memory), upload of the K staged elements, k_expand_partition.  The
+// upload is not overlapped with the transforms the way the chunks of a host matrix are (DESIGN.md section 8).
+template <class F>
+static bool partition_value(const void* values, uint64_t target, bool p3, typename F::T* out) {
+    typedef typename F::T T;
+    T v = static_cast<const T*>(values)[target];
+    if (p3) v = (T)Host<F>::p3_to_canonical(F::reduce_word(v));
+    *out = v;
+    return (u64)v < F::ORDER;
+}
+
+template <class F>
+static gb_status partition_public_inputs(Circuit<F>* c, const void* values, bool p3, std::vector<uint64_t>* pis) {
+    pis->resize(c->part.pi_reps.size());
+    for (size_t i = 0; i < pis->size(); i++) {
+        typename F::T v;
+        if (!partition_value<F>(values, c->part.pi_reps[i], p3, &v)) return fail(c->ctx, GB_ERR_INVALID, "non-canonical witness element");
+        (*pis)[i] = (uint64_t)v;
+    }
+    return GB_OK;
+}
+
+// values -> matrix_dev [num_wires][n], canonical words, on the context's stream
+template <class F>
+static gb_status expand_partition_stage(Circuit<F>* c, TmpAlloc& tmp, const void* values, uint32_t flags, typename F::T* matrix_dev) {
+    typedef typename F::T T;
+    gb_ctx* ctx = c->ctx;
+    gb_circuit::Partition& part = c->part;
+    hipStream_t st = ctx->stream;
+    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
+    const size_t K = part.reps.size(), bytes = K * sizeof(T);
+    Scope sc(ctx, "compute full witness");
+    if (part.staged_host_bytes < bytes) {
+        if (part.staged_host) {
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            (void)hipHostFree(part.staged_host);
+            part.staged_host = nullptr;
+            part.staged_host_bytes = 0;
+        }
+        HIP_TRY(ctx, hipHostMalloc(&part.staged_host, bytes, hipHostMallocDefault));
+        part.staged_host_bytes = bytes;
+    }
+    if (!part.staged_read) HIP_TRY(ctx, hipEventCreateWithFlags(&part.staged_read, hipEventDisableTiming));
+    else HIP_TRY(ctx, hipEventSynchronize(part.staged_read));   // the upload of the call before has left the staging block
+    {
+        Scope s1(ctx, "partition compaction");
+        T* staged = static_cast<T*>(part.staged_host);
+        const uint32_t* reps = part.reps.data();
+        std::atomic<bool> bad{false};
+        auto run = [&](size_t k0, size_t k1) {
+            bool ok = true;
+            for (size_t k = k0; k < k1; k++) ok &= partition_value<F>(values, reps[k], p3, staged + k);
+            if (!ok) bad.store(true, std::memory_order_relaxed);
+        };
+        const size_t nthreads = K >= ((size_t)1 << 18) && ctx->copy_threads > 1 ? (size_t)ctx->copy_threads : 1;
+        if (nthreads == 1) {
+            run(0, K);
+        } else {
+            std::vector<std::thread> workers;
+            const size_t per = (K + nthreads - 1) / nthreads;
+            try {   // a thread the system refuses: the calling thread takes its share
+                for (size_t i = 1; i < nthreads; i++) workers.emplace_back(run, std::min(K, i * per), std::min(K, (i + 1) * per));
+            } catch (...) {
+            }
+            const size_t started = workers.size() + 1;
+            run(0, std::min(K, per));
+            if (started < nthreads) run(std::min(K, started * per), K);
+            for (auto& w : workers) w.join();
+        }
+        if (bad.load()) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
+    }
+    T* staged_dev = tmp.get<T>(K);
+    if (!staged_dev) return fail(ctx, GB_ERR_OOM, "partition staging");
+    {
+        Scope s2(ctx, "partition upload");
+        HIP_TRY(ctx, hipMemcpyAsync(staged_dev, part.staged_host, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipEventRecord(part.staged_read, st));
+    }
+    {
+        Scope s3(ctx, "partition expansion");
+        gbk::expand_partition<F>(part.slots_dev, staged_dev, matrix_dev, c->cfg.degree_bits, c->cfg.num_wires, st);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
+    return GB_OK;
+}
+
+template <class F>
+static gb_status prove_partition(Circuit<F>* c, const void* values, uint32_t flags, const void* salts, void* proof_out, size_t proof_cap,
+                                 size_t* proof_len, const RetryHint* hint) {
+    typedef typename F::T T;
+    gb_ctx* ctx = c->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const gb_circuit_config& cfg = c->cfg;
+    const size_t n = (size_t)1 << cfg.degree_bits, N = n << cfg.rate_bits;
+    const u32 nw = cfg.num_wires;
+    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
+    hipStream_t st = ctx->stream;
+    gb_status s;
+    std::vector<uint64_t> pis;
+    if ((s = partition_public_inputs<F>(c, values, p3, &pis))) return s;
+    struct MatrixGuard {   // the expanded matrix: a pool block, handed to c->part when the attempt leaves retry state behind
+        gb_ctx* ctx; void* p; size_t bytes;
+        ~MatrixGuard() { if (p) pool_free(ctx, p, bytes); }
+    } matrix{ctx, nullptr, (size_t)nw * n * sizeof(T)};
+    TmpAlloc tmp(ctx);
+    // the retry (prover.rs:186-226): the caller re-drew values[representative_map[row * num_wires + wire]] - one cell of the matrix
+    // the failed attempt kept, provided that cell is alone in its class (prover_data.random_wire is)
+    bool incremental = hint && !salts && c->retry.wires && c->retry.seg.state && c->part.matrix && hint->wire < nw && hint->row < n;
+    if (incremental) {
+        uint32_t slot = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&slot, c->part.slots_dev + hint->row * nw + hint->wire, sizeof slot, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        T v;
+        if (slot >= c->part.reps.size() || c->part.is_shared_slot(slot)) {
+            incremental = false;
+        } else {
+            // (every other used entry is the failed attempt's, which was checked then)
+            if (!partition_value<F>(values, c->part.reps[slot], p3, &v)) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
+            matrix.p = c->part.matrix;
+            c->part.matrix = nullptr;
+            c->part.matrix_bytes = 0;
+            Scope sc(ctx, "compute full witness");
+            u32* cell = reinterpret_cast<u32*>(static_cast<T*>(matrix.p) + (size_t)hint->wire * n + hint->row);
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)v, 1, st));
+            if (sizeof(T) == 8) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(cell + 1), (int)(u32)((u64)v >> 32), 1, st));
+        }
+    }
+    if (!incremental) {
+        hint = nullptr;
+        c->drop_retry();   // (with the matrix of an earlier attempt) before the new one is allocated
+        if (pool_alloc(ctx, matrix.bytes, &matrix.p) != hipSuccess) { matrix.p = nullptr; return fail(ctx, GB_ERR_OOM, "partition witness matrix"); }
+        if ((s = expand_partition_stage<F>(c, tmp, values, flags, static_cast<T*>(matrix.p)))) return s;
+    }
+    // the proof proper: the device-witness path of prove().  Host salts go to the device with the witness.
+    const T* salts_dev = nullptr;
+    if (salts) {
+        const size_t count = (size_t)3 * GB_SALT_SIZE * N;
+        T* sd = tmp.get<T>(count);
+        if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
+        HIP_TRY(ctx, hipMemcpyAsync(sd, salts, count * sizeof(T), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));   // the salts are the caller's again
+        if (p3) p3_to_canonical_dev<F>(sd, count, st);
+        salts_dev = sd;
+    }
+    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE, pis.data(), pis.size(), salts_dev, proof_out, proof_cap, proof_len, hint);
+    if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
+        c->part.matrix = matrix.p;
+        c->part.matrix_bytes = matrix.bytes;
+        matrix.p = nullptr;
+    }
+    return s;
+}
+
+template <class F>
+static gb_status abi_expand_partition(Circuit<F>* c, const void* values, uint32_t flags, void* witness_dev_out) {
+    gb_ctx* ctx = c->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TmpAlloc tmp(ctx);
+    return expand_partition_stage<F>(c, tmp, values, flags, static_cast<typename F::T*>(witness_dev_out));
+}
+
 extern "C" {
 
 gb_status gb_pow_grind(gb_ctx* ctx, uint32_t field, const void* sponge_state, uint32_t witness_pos, uint32_t min_leading_zeros,
@@ -1838,6 +2030,7 @@ gb_status gb_circuit_free(gb_circuit* c) try {
         (void)hipStreamSynchronize(c->ctx->stream);
     }
     c->drop_retry();
+    c->drop_partition();
     c->release();
     delete c;
     return GB_OK;
@@ -1976,6 +2169,74 @@ gb_status gb_zs_partial_products(gb_circuit* c, const void* witness, uint32_t fl
 gb_status gb_zs_partial_products_cols(gb_circuit* c, const void* const* wire_cols, uint32_t flags, const void* betas, const void* gammas,
                                       void* values_out) try {
     return zs_entry(c, ColSrc::columns(wire_cols), flags, betas, gammas, values_out);
+} GB_CATCH_CIRCUIT(c)
+
+// ---- the partition witness (templates above: prove_partition, expand_partition_stage)
+gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative_map, uint64_t num_targets,
+                                   const uint64_t* public_input_targets, size_t num_public_inputs) try {
+    if (gb_status s = stage_guard(c)) return s;
+    gb_ctx* ctx = c->ctx;
+    const uint64_t cells = (uint64_t)c->cfg.num_wires << c->cfg.degree_bits;
+    gbk::partition::SlotMap m;
+    const char* msg = "";
+    if (const int ms = gbk::partition::build_slot_map(representative_map, num_targets, cells, public_input_targets, num_public_inputs,
+                                                      c->cfg.num_public_inputs, &m, &msg))
+        return fail(ctx, (gb_status)ms, std::string("gb_circuit_set_partition: ") + msg);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    c->drop_retry();
+    c->drop_partition();
+    void* p = nullptr;
+    HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(4, m.slots.size() * sizeof(uint32_t))));
+    c->part.slots_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, hipMemcpy(p, m.slots.data(), m.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->part.reps = std::move(m.reps);
+    c->part.pi_reps = std::move(m.pi_reps);
+    c->part.shared = std::move(m.shared);
+    c->part.num_targets = num_targets;
+    c->part.set = true;
+    return GB_OK;
+} GB_CATCH_CIRCUIT(c)
+
+static gb_status partition_guard(gb_circuit* c, const void* values, uint32_t flags) {
+    if (gb_status s = stage_guard(c)) return s;
+    if (!values) return fail(c->ctx, GB_ERR_INVALID, "null argument");
+    if (flags & ~GB_PUBLIC_INPUT_FLAGS) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the partition witness is a host object: GB_INPUT_DEVICE does not apply");
+    if (!c->part.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_partition has not been called on this circuit");
+    return GB_OK;
+}
+
+static gb_status prove_partition_entry(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out,
+                                       size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
+    if (gb_status s = partition_guard(c, values, flags)) return s;
+    gb_ctx* ctx = c->ctx;
+    if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if (c->cfg.zero_knowledge && !salts)
+        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
+    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
+    if (gb_status s = need_arity_list(c)) return s;
+    return c->field == GB_GOLDILOCKS
+               ? prove_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, salts, proof_out, proof_cap, proof_len, hint)
+               : prove_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, salts, proof_out, proof_cap, proof_len, hint);
+}
+
+gb_status gb_prove_partition(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out, size_t proof_cap,
+                             size_t* proof_len) try {
+    return prove_partition_entry(c, values, flags, salts, proof_out, proof_cap, proof_len);
+} GB_CATCH_CIRCUIT(c)
+
+gb_status gb_prove_partition_retry(gb_circuit* c, const void* values, uint32_t flags, uint32_t wire, uint64_t row, void* proof_out,
+                                   size_t proof_cap, size_t* proof_len) try {
+    const RetryHint hint{wire, row};
+    return prove_partition_entry(c, values, flags, nullptr, proof_out, proof_cap, proof_len, &hint);
+} GB_CATCH_CIRCUIT(c)
+
+gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags, void* witness_dev_out) try {
+    if (gb_status s = partition_guard(c, values, flags)) return s;
+    if (!witness_dev_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
+    return c->field == GB_GOLDILOCKS ? abi_expand_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, witness_dev_out)
+                                     : abi_expand_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, witness_dev_out);
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_quotient_polys(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial_products, const void* public_inputs_hash,

@@ -90,6 +90,10 @@ SIGNATURES = {
     "gb_prove_retry_cols": (_i32, [_vp, _cols, _u32, _u32, _u64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_salted_cols": (_i32, [_vp, _cols, _u32, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
     "gb_zs_partial_products_cols": (_i32, [_vp, _cols, _u32, _vp, _vp, _vp]),
+    "gb_circuit_set_partition": (_i32, [_vp, C.POINTER(_u64), _u64, C.POINTER(_u64), _sz]),
+    "gb_prove_partition": (_i32, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "gb_prove_partition_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, C.POINTER(_sz)]),
+    "gb_expand_partition": (_i32, [_vp, _vp, _u32, _vp]),
     "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
     "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
     "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),

@@ -244,6 +244,83 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         del keep
         return self._proof_buf[: n.value].tobytes()
 
+    # ---- prove() from the partition witness (include/goldibear_gpu.h: gb_circuit_set_partition, gb_prove_partition*)
+    def set_partition(self, representative_map, public_input_targets=()):
+        """ProverOnlyCircuitData.representative_map (plonk/circuit_data.rs:454), indexed by Target::index - wire (row, column) ->
+        row * num_wires + column, virtual target i -> n * num_wires + i - and the target indices of prover_data.public_inputs"""
+        m = np.ascontiguousarray(representative_map, dtype=np.uint64)
+        t = np.ascontiguousarray(public_input_targets, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        N.check(self._lib.gb_circuit_set_partition(self.handle, m.ctypes.data_as(u64p), m.size,
+                                                   t.ctypes.data_as(u64p) if t.size else None, t.size), self.ctx.handle)
+        self.num_targets = int(m.size)
+
+    def _partition_values(self, values, p3_repr):
+        v = np.ascontiguousarray(values, dtype=self._dt)
+        if v.shape != (getattr(self, "num_targets", -1),):
+            raise N.ShapeError(N.GB_ERR_INVALID, "values must have one entry per target of the map given to set_partition")
+        return v, (N.GB_INPUT_P3_REPR if p3_repr else N.GB_INPUT_HOST)
+
+    def prove_partition_once(self, values, salts=None, retry_wire=None, p3_repr=False):
+        """internal_prove_with_partition_witness from PartitionWitness.values (None as zero): full_witness() runs on the device"""
+        v, flags = self._partition_values(values, p3_repr)
+        if self._proof_buf is None:
+            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
+        n = C.c_size_t()
+        out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
+        if salts is None and retry_wire is not None:
+            st = self._lib.gb_prove_partition_retry(self.handle, v.ctypes.data, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap,
+                                                    C.byref(n))
+        else:
+            sa = None
+            if salts is not None:
+                sa = np.ascontiguousarray(salts, dtype=self._dt).reshape(3 * N.GB_SALT_SIZE, -1)
+                if sa.shape[1] != 1 << (self.cfg.degree_bits + self.cfg.rate_bits):
+                    raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N]")
+            st = self._lib.gb_prove_partition(self.handle, v.ctypes.data, flags, sa.ctypes.data if sa is not None else None, out, cap,
+                                              C.byref(n))
+        N.check(st, self.ctx.handle)
+        return self._proof_buf[: n.value].tobytes()
+
+    def prove_partition(self, values, representative=None, random_wire=None, rng=None, salts=None, p3_repr=False):
+        """prove_with_partition_witness (plonk/prover.rs:160-226) on the reference's own witness object: the retry loop of prove()
+        over gb_prove_partition / gb_prove_partition_retry.  random_wire = (column, row) as for prove(); `representative` is the
+        entry of `values` that holds it (representative_map[row * num_wires + column]), re-drawn in place after InvZeroPermArg."""
+        self.perm_arg_retries = 0
+        for attempt in range(self.MAX_PERM_ARG_RETRIES):
+            if attempt > 0:
+                if random_wire is None or representative is None:
+                    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "Permutation argument division by zero but no "
+                                                        "random wire was given to randomize the witness")
+                rng = rng or np.random.default_rng()
+                p = 0xFFFFFFFF00000001 if self.field == N.GB_GOLDILOCKS else 2013265921
+                val = int(rng.integers(0, p, dtype=np.uint64))
+                if p3_repr and self.field == N.GB_BABYBEAR:
+                    val = (val << 32) % p
+                values[int(representative)] = val
+                self.perm_arg_retries = attempt
+            try:
+                retry = random_wire if attempt > 0 and salts is None else None
+                return self.prove_partition_once(values, salts, retry_wire=retry, p3_repr=p3_repr)
+            except N.PermArgZeroError:
+                if random_wire is None:
+                    self.drop_retry()
+                continue
+        self.drop_retry()
+        raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+
+    def expand_partition(self, values, p3_repr=False):
+        """partition_witness.full_witness() (iop/witness.rs:359-371) alone: -> a torch device tensor [num_wires][n] of canonical
+        words (as int64 / int32 bit patterns), usable as the device input of commits and of zs_partial_products"""
+        import torch
+        v, flags = self._partition_values(values, p3_repr)
+        out = torch.empty((self.cfg.num_wires, 1 << self.cfg.degree_bits), dtype=torch.int64 if self._dt == np.uint64 else torch.int32,
+                          device="cuda:%d" % self.ctx.device)
+        torch.cuda.current_stream(out.device).synchronize()
+        N.check(self._lib.gb_expand_partition(self.handle, v.ctypes.data, flags, out.data_ptr()), self.ctx.handle)
+        N.check(self._lib.gb_ctx_synchronize(self.ctx.handle), self.ctx.handle)
+        return out
+
     @property
     def constants_sigmas_commitment(self):
         """ProverOnlyCircuitData.constants_sigmas_commitment (plonk/circuit_data.rs:532-534): a PolynomialBatch view that the
