@@ -415,6 +415,91 @@ gb_status gb_prove_partition_retry(gb_circuit* c, const void* values, uint32_t f
  * gb_commit_values and gb_zs_partial_products on the same context.  `values` is the caller's again on return. */
 gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags, void* witness_dev_out);
 
+/* ---- prove() from the inputs alone: the witness generators on the device ------------------------------------------------------
+ * prove() is two calls (plonk/prover.rs:136-158): generate_partial_witness, timed as "run N generators" (iop/generator.rs:25-106),
+ * and prove_with_partition_witness.  gb_prove_partition starts at the second and needs a host that has run every generator and
+ * hands over one word per target.  The functions below start at the first: the host hands over the generators ONCE per circuit,
+ * as records, and per proof only the values it alone knows - the PartialWitness and the random values (host inputs under the
+ * determinism contract) - and the generated values never leave the device.
+ *
+ * A record names one generator of prover_only.generators:
+ *   gate generators (GB_GEN_ARITHMETIC .. GB_GEN_POSEIDON2_INTERNAL, one kind per SimpleGenerator of the built-in gates): `gate`
+ *     is the index in the gate table given to gb_circuit_create_gates, `a` the row, `b` the operation (ArithmeticGate,
+ *     ArithmeticExtensionGate, MulExtensionGate, AddManyGate, ApplyMat4Gate, Poseidon2BabyBearGate), the copy (RandomAccessGate)
+ *     or the constant index (GB_GEN_CONSTANT: ConstantGenerator of a ConstantGate wire or of a RandomAccessGate extra constant),
+ *     0 for the gates with one generator per row;
+ *   GB_GEN_COPY (CopyGenerator, iop/generator.rs): `a` is the source target, `b` the destination target, `gate` is not read.
+ * The host lists the generators explicitly: CircuitBuilder::build drops those of the unused operations of partly filled gates
+ * (circuit_builder.rs:1252-1270), so they cannot be derived from the gate table.  Not built, GB_ERR_UNSUPPORTED: any other kind -
+ * generators of program gates, the lookup pair, and the gadget generators beyond Copy (Equality, NonzeroTest, Split, WireSplit,
+ * LowHigh, BaseSum, QuotientExtension, DummyProof); a circuit that has them stays on gb_prove_partition. */
+#define GB_GEN_ARITHMETIC 0
+#define GB_GEN_ARITHMETIC_EXTENSION 1
+#define GB_GEN_MUL_EXTENSION 2
+#define GB_GEN_CONSTANT 3
+#define GB_GEN_BASE_SPLIT 4
+#define GB_GEN_REDUCING 5
+#define GB_GEN_REDUCING_EXTENSION 6
+#define GB_GEN_RANDOM_ACCESS 7
+#define GB_GEN_POSEIDON_MDS 8
+#define GB_GEN_COSET_INTERPOLATION 9
+#define GB_GEN_EXPONENTIATION 10
+#define GB_GEN_POSEIDON 11
+#define GB_GEN_POSEIDON2_BABYBEAR 12
+#define GB_GEN_ADD_MANY 13
+#define GB_GEN_APPLY_MAT4 14
+#define GB_GEN_POSEIDON2_INTERNAL 15
+#define GB_GEN_COPY 16
+typedef struct gb_generator {
+    uint32_t kind;            /* GB_GEN_* */
+    uint32_t gate;
+    uint64_t a;
+    uint64_t b;
+} gb_generator;
+/* After gb_circuit_set_partition (before it: GB_ERR_INVALID): generators = gb_generator[num_generators]; input_targets
+ * [num_inputs] = the target indices (Target::index, as in the representative map) whose values the host supplies per proof - every
+ * target of the PartialWitness and of a RandomValueGenerator; constants = the circuit's constants columns again (no read-back from
+ * the device): [cfg.num_constants][degree] canonical 64-bit words for either field; flags = 0.  The library schedules the
+ * generators once: a dense index over the copy classes that a wire cell, an input, a public input or a generator touches (the
+ * slots of gb_circuit_set_partition first, in their order, then the classes only virtual targets use, ascending); levels
+ * (inputs are level 0, a generator runs one level after the last of its dependencies is stored); for every class ONE storing
+ * writer - the first in (level, record) order - while every later writer and every writer of an input class compares instead
+ * (witness.rs:340-350 "set twice with different values"); a run of levels that each fit one workgroup is one kernel launch.
+ * A generator with a dependency that nothing ever sets cannot run: it is left out and counted (the reference panics with
+ * "{n} generators weren't run"), its outputs stay zero.  GB_ERR_INVALID: a target >= num_targets, a gate index out of range or
+ * of another kind than the record's, a row, operation or constant index outside the gate's parameters, an input target listed
+ * twice, unknown flags.  Calling it again replaces the schedule; gb_circuit_set_partition drops it. */
+gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
+                                    uint64_t num_inputs, const uint64_t* constants, uint32_t flags);
+/* what the schedule looks like; any out pointer may be NULL */
+gb_status gb_circuit_generators_info(gb_circuit* c, uint32_t* num_levels, uint32_t* num_launches, uint32_t* num_unrunnable,
+                                     uint32_t* num_checks, uint32_t* num_classes);
+/* class_targets_out[num_classes]: the representative target of each class of the schedule, for a host that reads
+ * gb_generate_partition's values */
+gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_out, uint64_t capacity);
+/* The stage alone, for a host that keeps the prover loop: input_values[num_inputs] in the order of input_targets (host pointer;
+ * canonical words of the field's width, or with GB_INPUT_P3_REPR the field types' in-memory words), values_dev_out a DEVICE
+ * buffer of num_classes elements: one canonical word per class, the front part in slot order (what k_expand_partition reads),
+ * classes nothing sets zero.  Returns after the generated values' error word has been read back.  GB_ERR_INVALID: an input
+ * >= p ("non-canonical witness element"); two inputs, or an input and a generator, or two generators that set one class to
+ * different values ("Partition containing .. was set twice with different values"); a PoseidonGate / Poseidon2BabyBearGate row
+ * whose swap wire is not 0 or 1; a RandomAccessGate access index >= 2^bits; a BaseSumGate value that does not fit its limbs -
+ * the reference's assert!s, with the record index in gb_last_error.  Nothing faults and the circuit stays usable. */
+gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_t flags, void* values_dev_out);
+/* prove(): upload the inputs, run the generators (timing scope "run generators"), k_expand_partition straight from the generated
+ * values ("compute full witness" is now the expansion alone), then the device-witness path of gb_prove unchanged.  The public
+ * inputs are read from the generated values, in the same read-back as the error word.  salts as for gb_prove_partition.  The
+ * proof bytes are those of gb_prove_partition on the same values; errors are gb_generate_partition's and gb_prove's. */
+gb_status gb_prove_inputs(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
+                          size_t proof_cap, size_t* proof_len);
+/* After GB_ERR_PERM_ARG_ZERO: the caller has re-drawn the input whose target is wire `wire` of row `row` -
+ * prover_data.random_wire - and changed nothing else.  Same bytes and errors as gb_prove_inputs(input_values).  Where that input's
+ * class has no generator that reads or writes it and the cell is alone in its class, as holds for random_wire, and the failed
+ * attempt left its state behind, the value goes into the kept matrix as in gb_prove_partition_retry; anything else is the full
+ * computation. */
+gb_status gb_prove_inputs_retry(gb_circuit* c, const void* input_values, uint32_t flags, uint32_t wire, uint64_t row,
+                                void* proof_out, size_t proof_cap, size_t* proof_len);
+
 /* verify() of a proof produced for this circuit (plonk/verifier.rs:17-128, fri/verifier.rs:67-250,
  * plonk/get_challenges.rs:26-101), restated for the dummy gate set and run on the HOST like the reference's verifier: the
  * Fiat-Shamir replay, vanishing(zeta) == Z_H(zeta) * quotient(zeta), the proof of work, every Merkle path and the FRI

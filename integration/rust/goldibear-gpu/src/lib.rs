@@ -27,6 +27,23 @@ pub const GB_BABYBEAR: u32 = 1;
 pub const GB_INPUT_HOST: u32 = 0;
 pub const GB_INPUT_P3_REPR: u32 = 2;
 pub const GB_MAX_FRI_LAYERS: usize = 32;
+pub const GB_GEN_ARITHMETIC: u32 = 0;
+pub const GB_GEN_ARITHMETIC_EXTENSION: u32 = 1;
+pub const GB_GEN_MUL_EXTENSION: u32 = 2;
+pub const GB_GEN_CONSTANT: u32 = 3;
+pub const GB_GEN_BASE_SPLIT: u32 = 4;
+pub const GB_GEN_REDUCING: u32 = 5;
+pub const GB_GEN_REDUCING_EXTENSION: u32 = 6;
+pub const GB_GEN_RANDOM_ACCESS: u32 = 7;
+pub const GB_GEN_POSEIDON_MDS: u32 = 8;
+pub const GB_GEN_COSET_INTERPOLATION: u32 = 9;
+pub const GB_GEN_EXPONENTIATION: u32 = 10;
+pub const GB_GEN_POSEIDON: u32 = 11;
+pub const GB_GEN_POSEIDON2_BABYBEAR: u32 = 12;
+pub const GB_GEN_ADD_MANY: u32 = 13;
+pub const GB_GEN_APPLY_MAT4: u32 = 14;
+pub const GB_GEN_POSEIDON2_INTERNAL: u32 = 15;
+pub const GB_GEN_COPY: u32 = 16;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -51,6 +68,27 @@ pub struct gb_circuit_config {
     pub zero_knowledge: u32,
     /// CommonCircuitData.num_public_inputs: proofs carrying any other count are rejected (plonk/validate_shape.rs:22-25)
     pub num_public_inputs: u32,
+}
+
+/// One generator of prover_only.generators as a record (include/goldibear_gpu.h: gb_generator, GB_GEN_*): a gate generator by
+/// (gate index, row, operation / copy / constant index), a CopyGenerator by (source target, destination target).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct gb_generator {
+    pub kind: u32,
+    pub gate: u32,
+    pub a: u64,
+    pub b: u64,
+}
+
+/// `gb_circuit_generators_info`
+#[derive(Clone, Copy, Debug, Default)]
+pub struct GeneratorsInfo {
+    pub num_levels: u32,
+    pub num_launches: u32,
+    pub num_unrunnable: u32,
+    pub num_checks: u32,
+    pub num_classes: u32,
 }
 
 /// One entry of CommonCircuitData.gates with selectors_info flattened in (include/goldibear_gpu.h: gb_gate, GB_GATE_*).
@@ -125,6 +163,16 @@ extern "C" {
     fn gb_prove_partition_retry(c: *mut gb_circuit, values: *const c_void, flags: u32, wire: u32, row: u64, proof_out: *mut c_void,
                                 proof_cap: usize, proof_len: *mut usize) -> i32;
     fn gb_expand_partition(c: *mut gb_circuit, values: *const c_void, flags: u32, witness_dev_out: *mut c_void) -> i32;
+    fn gb_circuit_set_generators(c: *mut gb_circuit, generators: *const c_void, num_generators: u64, input_targets: *const u64,
+                                 num_inputs: u64, constants: *const u64, flags: u32) -> i32;
+    fn gb_circuit_generators_info(c: *mut gb_circuit, num_levels: *mut u32, num_launches: *mut u32, num_unrunnable: *mut u32,
+                                  num_checks: *mut u32, num_classes: *mut u32) -> i32;
+    fn gb_circuit_generator_classes(c: *mut gb_circuit, class_targets_out: *mut u64, capacity: u64) -> i32;
+    fn gb_generate_partition(c: *mut gb_circuit, input_values: *const c_void, flags: u32, values_dev_out: *mut c_void) -> i32;
+    fn gb_prove_inputs(c: *mut gb_circuit, input_values: *const c_void, flags: u32, salts: *const c_void, proof_out: *mut c_void,
+                       proof_cap: usize, proof_len: *mut usize) -> i32;
+    fn gb_prove_inputs_retry(c: *mut gb_circuit, input_values: *const c_void, flags: u32, wire: u32, row: u64, proof_out: *mut c_void,
+                             proof_cap: usize, proof_len: *mut usize) -> i32;
     fn gb_commit_values(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
                         cap_height: u32, salts: *const c_void, flags: u32, out: *mut *mut gb_batch) -> i32;
     fn gb_commit_coeffs(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
@@ -645,6 +693,9 @@ pub struct GpuCircuit<'c, W> {
     ctx: &'c GpuContext,
     handle: *mut gb_circuit,
     pub config: gb_circuit_config,
+    /// lengths the C side reads without being told: targets of `set_partition`'s map, inputs of `set_generators`
+    num_targets: std::cell::Cell<Option<usize>>,
+    num_inputs: std::cell::Cell<Option<usize>>,
     _w: std::marker::PhantomData<W>,
 }
 
@@ -668,7 +719,8 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         check(ctx.0, unsafe {
             gb_circuit_create(ctx.0, &config, constants_sigmas.as_ptr() as *const c_void, k_is.as_ptr() as *const c_void, GB_INPUT_HOST, &mut h)
         })?;
-        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+        Ok(Self { ctx, handle: h, config, num_targets: std::cell::Cell::new(None), num_inputs: std::cell::Cell::new(None),
+                  _w: std::marker::PhantomData })
     }
     /// The same for any gate set the library evaluates (`gates` = CommonCircuitData.gates with selectors_info, sorted as build()
     /// leaves them); GB_ERR_UNSUPPORTED (status 4) tells the caller to keep the CPU prover for this circuit.
@@ -680,7 +732,8 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
             gb_circuit_create_gates(ctx.0, &config, gates.as_ptr(), gates.len() as u32, constants_sigmas.as_ptr() as *const c_void,
                                     k_is.as_ptr() as *const c_void, GB_INPUT_HOST, &mut h)
         })?;
-        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+        Ok(Self { ctx, handle: h, config, num_targets: std::cell::Cell::new(None), num_inputs: std::cell::Cell::new(None),
+                  _w: std::marker::PhantomData })
     }
     /// `with_gates` for a gate set with gates of the host's own (`kind` = GB_GATE_PROGRAM, `param` = index of the gate's program):
     /// the programs lie end to end in `program_words`, program i at program_offsets[i] .. program_offsets[i + 1]; a program is the
@@ -696,7 +749,8 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
                                        num_programs, constants_sigmas.as_ptr() as *const c_void, k_is.as_ptr() as *const c_void,
                                        GB_INPUT_HOST, &mut h)
         })?;
-        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+        Ok(Self { ctx, handle: h, config, num_targets: std::cell::Cell::new(None), num_inputs: std::cell::Cell::new(None),
+                  _w: std::marker::PhantomData })
     }
     /// `with_programs` over one column per `Vec` (`gb_circuit_create_programs_cols`)
     pub fn with_programs_columns<C: AsRef<[W]>>(ctx: &'c GpuContext, mut config: gb_circuit_config, gates: &[gb_gate],
@@ -711,7 +765,8 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
             gb_circuit_create_programs_cols(ctx.0, &config, gates.as_ptr(), gates.len() as u32, program_words.as_ptr(), program_offsets.as_ptr(),
                                             num_programs, table.as_ptr(), k_is.as_ptr() as *const c_void, GB_INPUT_HOST, &mut h)
         })?;
-        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+        Ok(Self { ctx, handle: h, config, num_targets: std::cell::Cell::new(None), num_inputs: std::cell::Cell::new(None),
+                  _w: std::marker::PhantomData })
     }
     /// `with_gates` over `constants_sigmas_vecs` as `build()` holds them (circuit_builder.rs:1198-1229): one column per `Vec`, canonical
     /// words, handed over as a pointer table (`gb_circuit_create_gates_cols`)
@@ -726,7 +781,8 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
             gb_circuit_create_gates_cols(ctx.0, &config, gates.as_ptr(), gates.len() as u32, table.as_ptr(), k_is.as_ptr() as *const c_void,
                                          GB_INPUT_HOST, &mut h)
         })?;
-        Ok(Self { ctx, handle: h, config, _w: std::marker::PhantomData })
+        Ok(Self { ctx, handle: h, config, num_targets: std::cell::Cell::new(None), num_inputs: std::cell::Cell::new(None),
+                  _w: std::marker::PhantomData })
     }
     /// Zero-knowledge circuits: `salts` = [3][4][N] canonical words, the F::rand_vec columns of the wires / Zs / quotient
     /// commitments (fri/oracle.rs:144-148)
@@ -904,11 +960,24 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
     pub fn set_partition(&self, representative_map: &[usize], public_input_targets: &[usize]) -> Result<(), GpuError> {
         let map: Vec<u64> = representative_map.iter().map(|&t| t as u64).collect();
         let pis: Vec<u64> = public_input_targets.iter().map(|&t| t as u64).collect();
-        check(self.ctx.0, unsafe { gb_circuit_set_partition(self.handle, map.as_ptr(), map.len() as u64, pis.as_ptr(), pis.len()) })
+        check(self.ctx.0, unsafe { gb_circuit_set_partition(self.handle, map.as_ptr(), map.len() as u64, pis.as_ptr(), pis.len()) })?;
+        self.num_targets.set(Some(map.len()));
+        self.num_inputs.set(None);   // the library drops the generator schedule with the old map
+        Ok(())
+    }
+    fn need_len(what: &str, have: usize, want: Option<usize>, setter: &str) -> Result<(), GpuError> {
+        match want {
+            Some(w) => need(what, have, w),
+            None => Err(GpuError { status: GB_ERR_INVALID, message: format!("{setter} has not been called on this circuit") }),
+        }
     }
     /// `prove_with_partition_witness` from the `PartitionWitness` itself (plonk/prover.rs:160-183): `values[i]` =
     /// `partition_witness.values[i].unwrap_or(F::ZERO)`; `full_witness()` runs on the device.  `salts`: zero-knowledge circuits only.
     pub fn prove_partition(&self, values: &[W], salts: Option<&[W]>, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        Self::need_len("values", values.len(), self.num_targets.get(), "set_partition")?;
+        if let Some(s) = salts {
+            need("salts", s.len(), 12 * (1usize << (self.config.degree_bits + self.config.rate_bits)))?;
+        }
         let mut buf = vec![0u8; 8 << 20];
         let mut len = 0usize;
         let st = unsafe {
@@ -920,6 +989,7 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
     }
     /// The retry (prover.rs:186-226): `values[representative_map[row * num_wires + wire]]` - the random wire - re-drawn, nothing else.
     pub fn prove_partition_retry(&self, values: &[W], wire: usize, row: usize, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        Self::need_len("values", values.len(), self.num_targets.get(), "set_partition")?;
         let mut buf = vec![0u8; 8 << 20];
         let mut len = 0usize;
         let st = unsafe {
@@ -933,7 +1003,70 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
     /// # Safety
     /// `witness_dev_out` must be a device allocation of num_wires * n elements on this context's device.
     pub unsafe fn expand_partition(&self, values: &[W], repr: Repr, witness_dev_out: *mut c_void) -> Result<(), GpuError> {
+        Self::need_len("values", values.len(), self.num_targets.get(), "set_partition")?;
         check(self.ctx.0, gb_expand_partition(self.handle, values.as_ptr() as *const c_void, repr.flags(), witness_dev_out))
+    }
+    /// `prover_only.generators` as records (see INTEGRATION.md "Generators as records"), the targets whose values the host supplies
+    /// per proof - the `PartialWitness` and every `RandomValueGenerator` target - and the constants columns
+    /// `[num_constants][degree]` as canonical words; once, after `set_partition`.
+    pub fn set_generators(&self, generators: &[gb_generator], input_targets: &[usize], constants: &[u64]) -> Result<(), GpuError> {
+        need("constants", constants.len(), (self.config.num_constants as usize) << self.config.degree_bits)?;
+        let inputs: Vec<u64> = input_targets.iter().map(|&t| t as u64).collect();
+        check(self.ctx.0, unsafe {
+            gb_circuit_set_generators(self.handle, generators.as_ptr() as *const c_void, generators.len() as u64, inputs.as_ptr(),
+                                      inputs.len() as u64, constants.as_ptr(), 0)
+        })?;
+        self.num_inputs.set(Some(inputs.len()));
+        Ok(())
+    }
+    /// What the schedule looks like; `num_unrunnable` is the `n` of the reference's "{n} generators weren't run".
+    pub fn generators_info(&self) -> Result<GeneratorsInfo, GpuError> {
+        let mut i = GeneratorsInfo::default();
+        check(self.ctx.0, unsafe {
+            gb_circuit_generators_info(self.handle, &mut i.num_levels, &mut i.num_launches, &mut i.num_unrunnable, &mut i.num_checks,
+                                       &mut i.num_classes)
+        })?;
+        Ok(i)
+    }
+    /// The representative target of every class of the schedule, in the order of `generate_partition`'s values.
+    pub fn generator_classes(&self) -> Result<Vec<u64>, GpuError> {
+        let mut out = vec![0u64; self.generators_info()?.num_classes as usize];
+        check(self.ctx.0, unsafe { gb_circuit_generator_classes(self.handle, out.as_mut_ptr(), out.len() as u64) })?;
+        Ok(out)
+    }
+    /// `generate_partial_witness` (iop/generator.rs:25-106) alone, into a device buffer of the caller.
+    ///
+    /// # Safety
+    /// `values_dev_out` must be a device allocation of `num_classes` elements on this context's device.
+    pub unsafe fn generate_partition(&self, input_values: &[W], repr: Repr, values_dev_out: *mut c_void) -> Result<(), GpuError> {
+        Self::need_len("input_values", input_values.len(), self.num_inputs.get(), "set_generators")?;
+        check(self.ctx.0, gb_generate_partition(self.handle, input_values.as_ptr() as *const c_void, repr.flags(), values_dev_out))
+    }
+    /// `prove()` (plonk/prover.rs:136-158) from the inputs alone: `input_values` in the order of `set_generators`' targets; the
+    /// generators, `full_witness()` and the proof run on the device.  `salts`: zero-knowledge circuits only.
+    pub fn prove_inputs(&self, input_values: &[W], salts: Option<&[W]>, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        Self::need_len("input_values", input_values.len(), self.num_inputs.get(), "set_generators")?;
+        if let Some(s) = salts {
+            need("salts", s.len(), 12 * (1usize << (self.config.degree_bits + self.config.rate_bits)))?;
+        }
+        let mut buf = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let st = unsafe {
+            gb_prove_inputs(self.handle, input_values.as_ptr() as *const c_void, repr.flags(),
+                            salts.map_or(std::ptr::null(), |s| s.as_ptr() as *const c_void), buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
+        };
+        self.finish_proof(st, buf, len)
+    }
+    /// The retry (prover.rs:186-226): the input of the random wire (`wire`, `row`) re-drawn, nothing else.
+    pub fn prove_inputs_retry(&self, input_values: &[W], wire: usize, row: usize, repr: Repr) -> Result<ProveOutcome, GpuError> {
+        Self::need_len("input_values", input_values.len(), self.num_inputs.get(), "set_generators")?;
+        let mut buf = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let st = unsafe {
+            gb_prove_inputs_retry(self.handle, input_values.as_ptr() as *const c_void, repr.flags(), wire as u32, row as u64,
+                                  buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
+        };
+        self.finish_proof(st, buf, len)
     }
     /// Give up after `PermArgZero` (`ProverError::TooManyPermArgFailures`, prover.rs:221-225): releases what the failed attempt
     /// left on the device for `prove_retry` (~12 GB at 2^20 Goldilocks rows).  No-op when nothing is held.

@@ -8,7 +8,8 @@ Python so that circuits other than the dummy one - the reference's `factorial` e
     x = builder.add_virtual_target(); y = builder.mul(x, builder.constant(3)); builder.register_public_input(y)
     data = builder.build(ctx)                   # CircuitData: constants||sigmas committed on the GPU
     pw = PartialWitness(); pw.set_target(x, 5)
-    proof = data.prove(pw)                      # witness generation on the host, prove() on the GPU
+    proof = data.prove_inputs(pw)               # witness generation, full_witness() and prove() on the GPU
+    proof = data.prove(pw)                      # the same bytes: witness generation on the host (gb_prove_partition)
     data.verify(proof)
 
 Gates: NoopGate, ConstantGate, PublicInputGate, ArithmeticGate (gates/arithmetic_base.rs) and the in-circuit hash of the
@@ -185,6 +186,9 @@ class _ArithmeticGenerator:
         self.row, self.c0, self.c1, self.i = row, c0, c1, i
         self.deps = [wire(row, 4 * i), wire(row, 4 * i + 1), wire(row, 4 * i + 2)]
 
+    def record(self, built):
+        return (N.GB_GEN_ARITHMETIC, built.row_gates[self.row], self.row, self.i)
+
     def run(self, w, p):
         m0, m1, a = (w.get(t) for t in self.deps)
         w.set(wire(self.row, 4 * self.i + 3), (m0 * m1 * self.c0 + a * self.c1) % p)
@@ -197,6 +201,9 @@ class _ConstantGenerator:
     def __init__(self, row, constant_index, wire_index):
         self.row, self.constant_index, self.wire_index, self.constant = row, constant_index, wire_index, 0
 
+    def record(self, built):
+        return (N.GB_GEN_CONSTANT, built.row_gates[self.row], self.row, self.constant_index)
+
     def run(self, w, p):
         w.set(wire(self.row, self.wire_index), self.constant)
 
@@ -207,8 +214,24 @@ class _RandomValueGenerator:
     def __init__(self, target):
         self.target = target
 
+    def record(self, built):
+        return None   # its target is an input: random values are the host's (determinism contract)
+
     def run(self, w, p):
         w.set(self.target, w.random())
+
+
+class _CopyGenerator:
+    """iop/generator.rs CopyGenerator: dst = src"""
+
+    def __init__(self, src, dst):
+        self.src, self.dst, self.deps = src, dst, [src]
+
+    def record(self, built):
+        return (N.GB_GEN_COPY, 0, built.target_index(self.src), built.target_index(self.dst))
+
+    def run(self, w, p):
+        w.set(self.dst, w.get(self.src))
 
 
 class _PoseidonGenerator:
@@ -217,6 +240,9 @@ class _PoseidonGenerator:
     def __init__(self, row):
         self.row = row
         self.deps = [wire(row, c) for c in range(12)] + [wire(row, PoseidonGate.WIRE_SWAP)]
+
+    def record(self, built):
+        return (N.GB_GEN_POSEIDON, built.row_gates[self.row], self.row, 0)
 
     def run(self, w, p):
         G, row = PoseidonGate, self.row
@@ -238,6 +264,9 @@ class _Poseidon2Generator:
     def __init__(self, row, num_ops, op):
         self.row, self.num_ops, self.op = row, num_ops, op
         self.deps = [wire(row, 33 * op + c) for c in range(16)] + [wire(row, 33 * op + 32)]
+
+    def record(self, built):
+        return (N.GB_GEN_POSEIDON2_BABYBEAR, built.row_gates[self.row], self.row, self.op)
 
     def run(self, w, p):
         row, op = self.row, self.op
@@ -428,6 +457,10 @@ class CircuitBuilder:
 
     def is_routable(self, t):
         return t[0] == "v" or t[2] < self.config.num_routed_wires
+
+    def generate_copy(self, src, dst):
+        """gadgets/arithmetic.rs generate_copy: a CopyGenerator, no copy constraint"""
+        self.generators.append(_CopyGenerator(src, dst))
 
     def connect(self, x, y):
         if not (self.is_routable(x) and self.is_routable(y)):
@@ -660,7 +693,8 @@ class CircuitBuilder:
                             list(self.public_inputs), self.random_wire, [g.id for g in gates],
                             sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None,
                             copy_targets=sorted({t for ab in self.copy_constraints for t in ab}),
-                            num_virtual_targets=self.virtual_target_index)
+                            num_virtual_targets=self.virtual_target_index,
+                            row_gates=[gates.index(g) for g, _ in self.gate_instances])
 
     def _forest(self):
         """Disjoint sets over the targets that appear in copy constraints (plonk/permutation_argument.rs:13-101)."""
@@ -731,7 +765,7 @@ class BuiltCircuit:
     """CircuitData (plonk/circuit_data.rs:153-300) for a built circuit: prove(PartialWitness) / verify(proof)."""
 
     def __init__(self, ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, num_selectors, max_constants, generators, find,
-                 public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0):
+                 public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0, row_gates=()):
         self.config, self.F, self.degree_bits, self.programs = cfg, F, degree_bits, programs
         self.constants_sigmas, self.k_is, self.gate_table, self.gate_ids = constants_sigmas, k_is, gate_table, gate_ids
         self.num_selectors, self.max_constants = num_selectors, max_constants
@@ -741,6 +775,9 @@ class BuiltCircuit:
         # representative_map is built from
         self.copy_targets, self.num_virtual_targets = copy_targets, num_virtual_targets
         self._representative_map, self._partition_set = None, False
+        self.row_gates = row_gates          # per row: the index of its gate in gate_table (what a gb_generator record names)
+        self._inputs = None                 # set_generators: the targets whose values the host supplies per proof
+        self._input_set = frozenset()
         self.data = None
         if ctx is not None:
             from .prover import CircuitData
@@ -834,6 +871,100 @@ class BuiltCircuit:
             col_row = (self.random_wire[1], self.random_wire[0])
             rep = self.representative_map[self.target_index(wire(*self.random_wire))]
         return self.data.prove_partition(values, representative=rep, random_wire=col_row, rng=rng)
+
+    # ---- prove() from the inputs alone: the generators run on the device (include/goldibear_gpu.h gb_circuit_set_generators)
+    @property
+    def random_targets(self):
+        """the targets of the RandomValueGenerators, in the order the mirror draws them"""
+        return [g.target for g in self.generators if isinstance(g, _RandomValueGenerator)]
+
+    def generator_records(self):
+        """prover_only.generators as gb_generator tuples (kind, gate, a, b); a RandomValueGenerator has none"""
+        return [r for r in (g.record(self) for g in self.generators) if r is not None]
+
+    @property
+    def constants_columns(self):
+        return self.constants_sigmas[self.num_selectors:self.num_selectors + self.max_constants]
+
+    def set_generators(self, input_targets=None, pw=None):
+        """hand the generators over once.  input_targets: the targets whose values the host supplies per proof; the default is
+        the targets of `pw` plus the random-value targets"""
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        if input_targets is None:
+            if pw is None:
+                raise ValueError("set_generators needs input_targets, or a PartialWitness to take them from")
+            input_targets = list(pw.values) + [t for t in self.random_targets if t not in pw.values]
+        if not self._partition_set:
+            self.data.set_partition(self.representative_map, self.public_input_targets)
+            self._partition_set = True
+        self.data.set_generators(self.generator_records(), [self.target_index(t) for t in input_targets], self.constants_columns)
+        self._input_targets = list(input_targets)
+
+    def input_values(self, pw, rng=None):
+        """the per-proof inputs in the order of set_generators' input_targets: the partial witness, and for the random-value
+        targets the values the mirror's RandomValueGenerators would draw from `rng`"""
+        rng = rng or np.random.default_rng(0)
+        extra = [t for t in pw.values if t not in self._input_set]
+        if extra:
+            raise ValueError("the partial witness sets %d targets that are no inputs of the schedule (first: %r): call "
+                             "set_generators again with these targets" % (len(extra), extra[0]))
+        drawn = {t: int(rng.integers(0, self.F.p, dtype=np.uint64)) for t in self.random_targets}
+        out = np.zeros(len(self._input_targets), dtype=self.F.dtype)
+        for i, t in enumerate(self._input_targets):
+            if t in pw.values:
+                out[i] = pw.values[t] % self.F.p
+            elif t in drawn:
+                out[i] = drawn[t]
+            else:
+                raise ValueError("the partial witness has no value for input target %r of the schedule" % (t,))
+        return out
+
+    def generate_partition_device(self, pw, rng=None):
+        """generate_partition_witness on the device -> PartitionWitness.values as a dense array, one entry per target"""
+        if self._input_targets is None:
+            self.set_generators(pw=pw)
+        got = self.data.generate_partition(self.input_values(pw, rng))
+        values = np.zeros(self.num_targets, dtype=self.F.dtype)
+        values[self.data.generator_classes().astype(np.int64)] = got
+        return values
+
+    def prove_inputs(self, pw, rng=None):
+        """prove() (plonk/prover.rs:136-226): the generators, full_witness() and the proof on the device, with the reference's
+        retry loop - after InvZeroPermArg the random wire's input is drawn again"""
+        if self._input_targets is None:
+            self.set_generators(pw=pw)
+        values = self.input_values(pw, rng)
+        data = self.data
+        data.perm_arg_retries = 0
+        for attempt in range(data.MAX_PERM_ARG_RETRIES):
+            retry = None
+            if attempt > 0:
+                t = wire(*self.random_wire) if self.random_wire else None
+                if t not in self._input_targets:
+                    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "Permutation argument division by zero but the "
+                                                        "random wire is no input to randomize")
+                rng = rng or np.random.default_rng()
+                values[self._input_targets.index(t)] = int(rng.integers(0, self.F.p, dtype=np.uint64))
+                data.perm_arg_retries = attempt
+                retry = (self.random_wire[1], self.random_wire[0])
+            try:
+                return data.prove_inputs_once(values, retry_wire=retry)
+            except N.PermArgZeroError:
+                if not self.random_wire:
+                    data.drop_retry()
+                continue
+        data.drop_retry()
+        raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+
+    @property
+    def _input_targets(self):
+        return self._inputs
+
+    @_input_targets.setter
+    def _input_targets(self, targets):
+        self._inputs = None if targets is None else list(targets)
+        self._input_set = frozenset(self._inputs or ())
 
     def verify(self, proof):
         return self.data.verify(proof)

@@ -216,24 +216,15 @@ GB_HD void mds_layer(typename A::V (&s)[12]) {  // mds_layer_field (:584-592)
     for (u32 r = 0; r < 12; r++) s[r] = out[r];
 }
 
-// PoseidonGate::eval_unfiltered (Goldilocks: device form == canonical, so the tables are used as they are)
-template <class A, class W, class Emit>
-GB_HD void eval_poseidon(W&& wire, Emit&& emit) {
+// The rounds of PoseidonGate as the gate lays them out (Goldilocks: device form == canonical, so the tables are used as they are):
+// `step(column, computed)` is handed the value computed for an s-box-input wire (every round but the first) or an output wire
+// and returns the value to go on with.  eval_poseidon below goes on with the wire and emits the difference; the witness generator
+// (generators.hpp) stores the computed value and goes on with it.  `s` is the state after the swap.
+template <class A, class Step>
+GB_HD void poseidon_gate_rounds(typename A::V (&s)[12], Step&& step) {
     typedef typename A::V V;
     const PoseidonTab& t = poseidon_tab();
-    constexpr u32 WIRE_SWAP = 24, START_DELTA = 25, START_FULL_0 = 29, START_PARTIAL = START_FULL_0 + 36, START_FULL_1 = START_PARTIAL + 22;
-    const V swap = wire(WIRE_SWAP);
-    emit(A::mul(swap, A::sub(swap, A::cst(1))));
-    V s[12];
-#pragma unroll
-    for (u32 i = 0; i < 4; i++) {
-        const V lhs = wire(i), rhs = wire(i + 4), delta = wire(START_DELTA + i);
-        emit(A::sub(A::mul(swap, A::sub(rhs, lhs)), delta));
-        s[i] = A::add(lhs, delta);
-        s[i + 4] = A::sub(rhs, delta);
-    }
-#pragma unroll
-    for (u32 i = 8; i < 12; i++) s[i] = wire(i);
+    constexpr u32 START_FULL_0 = 29, START_PARTIAL = START_FULL_0 + 36, START_FULL_1 = START_PARTIAL + 22;
     u32 ctr = 0;
 #pragma unroll 1
     for (u32 r = 0; r < 4; r++, ctr++) {
@@ -241,11 +232,7 @@ GB_HD void eval_poseidon(W&& wire, Emit&& emit) {
         for (u32 i = 0; i < 12; i++) s[i] = A::addc(s[i], t.rc[12 * ctr + i]);
         if (r != 0) {
 #pragma unroll
-            for (u32 i = 0; i < 12; i++) {
-                const V in = wire(START_FULL_0 + 12 * (r - 1) + i);
-                emit(A::sub(s[i], in));
-                s[i] = in;
-            }
+            for (u32 i = 0; i < 12; i++) s[i] = step(START_FULL_0 + 12 * (r - 1) + i, s[i]);
         }
 #pragma unroll
         for (u32 i = 0; i < 12; i++) s[i] = sbox7<A>(s[i]);
@@ -269,9 +256,7 @@ GB_HD void eval_poseidon(W&& wire, Emit&& emit) {
     }
 #pragma unroll 1
     for (u32 r = 0; r < 22; r++) {
-        const V in = wire(START_PARTIAL + r);
-        emit(A::sub(s[0], in));
-        s[0] = sbox7<A>(in);
+        s[0] = sbox7<A>(step(START_PARTIAL + r, s[0]));
         if (r != 21) s[0] = A::addc(s[0], t.fastc[r]);
         // mds_partial_layer_fast_field (:747-767)
         V d = A::mulc(s[0], t.circ[0] + t.diag[0]);
@@ -285,15 +270,35 @@ GB_HD void eval_poseidon(W&& wire, Emit&& emit) {
 #pragma unroll 1
     for (u32 r = 0; r < 4; r++, ctr++) {
 #pragma unroll
-        for (u32 i = 0; i < 12; i++) {
-            const V in = wire(START_FULL_1 + 12 * r + i);
-            emit(A::sub(A::addc(s[i], t.rc[12 * ctr + i]), in));
-            s[i] = sbox7<A>(in);
-        }
+        for (u32 i = 0; i < 12; i++) s[i] = sbox7<A>(step(START_FULL_1 + 12 * r + i, A::addc(s[i], t.rc[12 * ctr + i])));
         mds_layer<A>(s);
     }
 #pragma unroll
-    for (u32 i = 0; i < 12; i++) emit(A::sub(s[i], wire(12 + i)));
+    for (u32 i = 0; i < 12; i++) step(12 + i, s[i]);
+}
+
+// PoseidonGate::eval_unfiltered
+template <class A, class W, class Emit>
+GB_HD void eval_poseidon(W&& wire, Emit&& emit) {
+    typedef typename A::V V;
+    constexpr u32 WIRE_SWAP = 24, START_DELTA = 25;
+    const V swap = wire(WIRE_SWAP);
+    emit(A::mul(swap, A::sub(swap, A::cst(1))));
+    V s[12];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) {
+        const V lhs = wire(i), rhs = wire(i + 4), delta = wire(START_DELTA + i);
+        emit(A::sub(A::mul(swap, A::sub(rhs, lhs)), delta));
+        s[i] = A::add(lhs, delta);
+        s[i + 4] = A::sub(rhs, delta);
+    }
+#pragma unroll
+    for (u32 i = 8; i < 12; i++) s[i] = wire(i);
+    poseidon_gate_rounds<A>(s, [&](u32 col, V computed) -> V {
+        const V in = wire(col);
+        emit(A::sub(computed, in));
+        return in;
+    });
 }
 
 // Poseidon2BabyBearGate::eval_unfiltered.  Wire layout (:56-147): per op 33 routed wires (16 in, 16 out, swap) first for all
@@ -339,14 +344,45 @@ GB_HD void p2_internal(typename A::V (&s)[16]) {  // permute_internal_mut (:787-
 #pragma unroll
     for (u32 i = 0; i < 15; i++) s[i + 1] = A::add(full, A::mulc(s[i + 1], F::enc((u64)1 << SHIFTS[i])));
 }
+// The rounds of one Poseidon2BabyBearGate operation, with `step` as in poseidon_gate_rounds: the s-box inputs lie from column
+// start_full_0 on (full rounds 1..3, the 13 internal rounds, full rounds 4..7), the outputs from out0.  `s` is the state after the swap.
+template <class F, class A, class Step>
+GB_HD void poseidon2_gate_rounds(typename A::V (&s)[16], u32 start_full_0, u32 out0, Step&& step) {
+    const Poseidon2Tab& t = poseidon2_tab();
+    const u32 start_partial = start_full_0 + 48, start_full_1 = start_partial + 13;
+    p2_external<A>(s);
+#pragma unroll 1
+    for (u32 r = 0; r < 4; r++) {
+#pragma unroll
+        for (u32 i = 0; i < 16; i++) s[i] = A::addc(s[i], F::enc(t.ext[16 * r + i]));
+        if (r > 0) {
+#pragma unroll
+            for (u32 i = 0; i < 16; i++) s[i] = step(start_full_0 + 16 * (r - 1) + i, s[i]);
+        }
+#pragma unroll
+        for (u32 i = 0; i < 16; i++) s[i] = sbox7<A>(s[i]);
+        p2_external<A>(s);
+    }
+#pragma unroll 1
+    for (u32 r = 0; r < 13; r++) {
+        s[0] = sbox7<A>(step(start_partial + r, A::addc(s[0], F::enc(t.internal[r]))));
+        p2_internal<F, A>(s);
+    }
+#pragma unroll 1
+    for (u32 r = 4; r < 8; r++) {
+#pragma unroll
+        for (u32 i = 0; i < 16; i++) s[i] = sbox7<A>(step(start_full_1 + 16 * (r - 4) + i, A::addc(s[i], F::enc(t.ext[16 * r + i]))));
+        p2_external<A>(s);
+    }
+#pragma unroll
+    for (u32 i = 0; i < 16; i++) step(out0 + i, s[i]);
+}
 template <class F, class A, class W, class Emit>
 GB_HD void eval_poseidon2_bb(u32 num_ops, W&& wire, Emit&& emit) {
     typedef typename A::V V;
-    const Poseidon2Tab& t = poseidon2_tab();
     constexpr u32 ROUTED = 33, NON_ROUTED = 8 + 16 * 7 + 13;
     for (u32 op = 0; op < num_ops; op++) {
         const u32 in0 = ROUTED * op, out0 = in0 + 16, start_delta = num_ops * ROUTED + op * NON_ROUTED;
-        const u32 start_full_0 = start_delta + 8, start_partial = start_full_0 + 48, start_full_1 = start_partial + 13;
         const V swap = wire(in0 + 32);
         emit(A::mul(swap, A::sub(swap, A::cst(F::one()))));
         V s[16];
@@ -357,42 +393,11 @@ GB_HD void eval_poseidon2_bb(u32 num_ops, W&& wire, Emit&& emit) {
             s[i] = A::add(lhs, delta);
             s[i + 8] = A::sub(rhs, delta);
         }
-        p2_external<A>(s);
-#pragma unroll 1
-        for (u32 r = 0; r < 4; r++) {
-#pragma unroll
-            for (u32 i = 0; i < 16; i++) s[i] = A::addc(s[i], F::enc(t.ext[16 * r + i]));
-            if (r > 0) {
-#pragma unroll
-                for (u32 i = 0; i < 16; i++) {
-                    const V in = wire(start_full_0 + 16 * (r - 1) + i);
-                    emit(A::sub(s[i], in));
-                    s[i] = in;
-                }
-            }
-#pragma unroll
-            for (u32 i = 0; i < 16; i++) s[i] = sbox7<A>(s[i]);
-            p2_external<A>(s);
-        }
-#pragma unroll 1
-        for (u32 r = 0; r < 13; r++) {
-            const V in = wire(start_partial + r);
-            emit(A::sub(A::addc(s[0], F::enc(t.internal[r])), in));
-            s[0] = sbox7<A>(in);
-            p2_internal<F, A>(s);
-        }
-#pragma unroll 1
-        for (u32 r = 4; r < 8; r++) {
-#pragma unroll
-            for (u32 i = 0; i < 16; i++) {
-                const V in = wire(start_full_1 + 16 * (r - 4) + i);
-                emit(A::sub(A::addc(s[i], F::enc(t.ext[16 * r + i])), in));
-                s[i] = sbox7<A>(in);
-            }
-            p2_external<A>(s);
-        }
-#pragma unroll
-        for (u32 i = 0; i < 16; i++) emit(A::sub(s[i], wire(out0 + i)));
+        poseidon2_gate_rounds<F, A>(s, start_delta + 8, out0, [&](u32 col, V computed) -> V {
+            const V in = wire(col);
+            emit(A::sub(computed, in));
+            return in;
+        });
     }
 }
 

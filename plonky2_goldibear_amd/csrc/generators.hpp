@@ -1,0 +1,352 @@
+// Witness generators on the device: generate_partial_witness (iop/generator.rs:25-106) as waves over the schedule of
+// generator_schedule.hpp.  One evaluator per generator kind, each the counterpart of its gate's eval_* in gates.hpp and written
+// with the same extension algebra (Tup<>), MDS tables and round structure (poseidon_gate_rounds / poseidon2_gate_rounds):
+//   ArithmeticBaseGenerator        gates/arithmetic_base.rs:192-240      ArithmeticExtensionGenerator  gates/arithmetic_extension.rs:186-233
+//   MulExtensionGenerator          gates/multiplication_extension.rs:160-200   ConstantGenerator / CopyGenerator  iop/generator.rs
+//   BaseSplitGenerator             gates/base_sum.rs:178-225             ReducingGenerator             gates/reducing.rs:205-250
+//   ReducingExtensionGenerator     gates/reducing_extension.rs:203-245   RandomAccessGenerator         gates/random_access.rs:383-440
+//   PoseidonMdsGenerator           gates/poseidon_goldilocks_mds.rs:255-300    InterpolationGenerator  gates/coset_interpolation.rs:451-560
+//   ExponentiationGenerator        gates/exponentiation.rs:248-300       PoseidonGenerator             gates/poseidon_goldilocks.rs:436-531
+//   Poseidon2BabyBearGenerator     gates/poseidon2_babybear.rs:536-676   AddManyGenerator              gates/add_many.rs:167-215
+//   ApplyMat4Generator             gates/apply_mat4.rs:216-270           Poseidon2InternalPermutationGenerator  gates/poseidon2_internal_permutation.rs:225-290
+// The values array holds one CANONICAL word per copy class; an evaluator converts to the device form and back (a no-op for
+// Goldilocks).  Every class index comes from the schedule, which range-checked it; values that index something - the access index
+// of RandomAccessGenerator - are compared with their bound before use.  The reference's assert!s end in the device error word,
+// not in a fault.
+//
+// Depends on the field headers and gates.hpp only (and the plain words of generator_ops.hpp): tests/device/generators.hip and
+// tests/host_shim/generators.cpp include it on their own.
+#pragma once
+#include "gates.hpp"
+#include "generator_ops.hpp"
+
+namespace gbk {
+namespace gen {
+
+GB_HD void report(u32* err, u32 code, u32 record, u32 cls) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (atomicCAS(err, 0u, code) == 0u) {   // the first report stays
+        err[1] = record;
+        err[2] = cls;
+    }
+#else
+    if (!err[0]) {
+        err[0] = code;
+        err[1] = record;
+        err[2] = cls;
+    }
+#endif
+}
+
+// an Op's view of the values array.  `values` is written and read again inside one launch of the chain kernel: a plain pointer,
+// never const __restrict__ (the scalar-cache path is not coherent with vector stores).
+template <class F>
+struct Io {
+    typedef typename F::T T;
+    const Op& op;
+    const u32* args;
+    T* values;
+    u32* err;
+    GB_HD T raw(u32 i) const { return values[args[op.in_off + i]]; }   // canonical
+    GB_HD T in(u32 i) const { return F::enc(raw(i)); }                  // device form
+    GB_HD T operator()(u32 i) const { return in(i); }                   // as a `wire` accessor of Tup<>::load
+    GB_HD void put(u32 i, T canonical) const {
+        const u32 w = args[op.out_off + i];
+        if (w == OUT_SKIP) return;
+        const u32 cl = w & ~OUT_CHECK;
+        if (w & OUT_CHECK) {
+            if (values[cl] != canonical) report(err, ERR_SET_TWICE, op.record, cl);
+        } else {
+            values[cl] = canonical;
+        }
+    }
+    GB_HD void out(u32 i, T device_form) const { put(i, (T)F::dec(device_form)); }
+    template <class X>
+    GB_HD void out_ext(u32 i, const X& x) const {
+#pragma unroll
+        for (u32 k = 0; k < F::D; k++) out(i + k, x.c[k]);
+    }
+};
+
+template <class F>
+GB_HD void gen_arithmetic_extension(const Io<F>& io, bool with_addend) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    constexpr u32 D = F::D;
+    X r = (X::load(io, 0) * X::load(io, D)).scalar_c(F::enc(io.op.k[0]));
+    if (with_addend) r = r + X::load(io, 2 * D).scalar_c(F::enc(io.op.k[1]));
+    io.out_ext(0, r);
+}
+
+template <class F>
+GB_HD void gen_base_split(const Io<F>& io) {
+    const u32 limbs = io.op.p0, base = io.op.p1 < 2 ? 2 : io.op.p1;
+    u64 v = (u64)io.raw(0);
+    for (u32 i = 0; i < limbs; i++) {
+        io.put(i, (typename F::T)(v % base));
+        v /= base;
+    }
+    if (v) report(io.err, ERR_SPLIT_TOO_LARGE, io.op.record, io.args[io.op.in_off]);
+}
+
+template <class F>
+GB_HD void gen_reducing(const Io<F>& io, bool extension_coeffs) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    constexpr u32 D = F::D;
+    const X alpha = X::load(io, 0);
+    X acc = X::load(io, D);
+    for (u32 i = 0; i < io.op.p0; i++) {
+        const X coeff = extension_coeffs ? X::load(io, 2 * D + i * D) : X::from_base(io.in(2 * D + i));
+        acc = acc * alpha + coeff;
+        io.out_ext(i * D, acc);
+    }
+}
+
+template <class F>
+GB_HD void gen_random_access(const Io<F>& io) {
+    const u32 bits = io.op.p0;
+    const u64 index = (u64)io.raw(0);
+    if (index >> bits) {   // assert!(access_index < vec_size)
+        report(io.err, ERR_ACCESS_INDEX, io.op.record, io.args[io.op.in_off]);
+        return;
+    }
+    for (u32 i = 0; i < bits; i++) io.put(i, (typename F::T)((index >> i) & 1));
+}
+
+template <class F>
+GB_HD void gen_poseidon_mds(const Io<F>& io) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    constexpr u32 D = F::D;
+    const gates::PoseidonTab& t = gates::poseidon_tab();
+#pragma unroll 1
+    for (u32 r = 0; r < 12; r++) {
+        X res = X::load(io, r * D).scalar_c(F::enc(t.circ[0] + t.diag[r]));
+#pragma unroll 1
+        for (u32 i = 1; i < 12; i++) {
+            const u32 j = r + i >= 12 ? r + i - 12 : r + i;
+            res = res + X::load(io, j * D).scalar_c(F::enc(t.circ[i]));
+        }
+        io.out_ext(r * D, res);
+    }
+}
+
+template <class F>
+GB_HD void gen_coset_interpolation(const Io<F>& io) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    typedef typename F::T T;
+    constexpr u32 D = F::D;
+    const u32 bits = io.op.p0, degree = io.op.p1, npts = 1u << bits;
+    const u32 nint = degree > 1 ? (npts - 2) / (degree - 1) : 0;
+    const T g = F::two_adic_generator(bits), inv_m = F::inv(F::enc(npts));
+    const X shifted = X::load(io, 1 + npts * D).scalar_c(F::inv(io.in(0)));
+    io.out_ext(0, shifted);
+    X ev = X::zero(), prod = X::from_base(F::one());
+    T x_i = F::one();
+    u32 next = 0;
+    auto partial = [&](u32 hi) {   // partial_interpolate (:637-664); the points are visited once, in order
+        for (; next < hi; next++) {
+            const X val = X::load(io, 1 + next * D).scalar_c(F::mul(x_i, inv_m));   // barycentric weight x_i / 2^bits
+            X term = shifted;
+            term.c[0] = F::sub(term.c[0], x_i);
+            ev = ev * term + val * prod;
+            prod = prod * term;
+            x_i = F::mul(x_i, g);
+        }
+    };
+    partial(degree < npts ? degree : npts);
+    for (u32 i = 0; i < nint; i++) {
+        io.out_ext(D + 2 * D * i, ev);
+        io.out_ext(2 * D + 2 * D * i, prod);
+        const u32 lo = 1 + (degree - 1) * (i + 1), hi = lo + degree - 1 < npts ? lo + degree - 1 : npts;
+        partial(hi);
+    }
+    io.out_ext(D + 2 * D * nint, ev);
+}
+
+template <class F>
+GB_HD void gen_exponentiation(const Io<F>& io) {
+    typedef typename F::T T;
+    const u32 n = io.op.p0;
+    const T base = io.in(0);
+    T cur = F::one();
+    for (u32 i = 0; i < n; i++) {
+        if (i) cur = F::mul(cur, cur);
+        if (io.raw(1 + (n - 1 - i)) != 0) cur = F::mul(cur, base);   // power bits are little-endian, the chain runs big-endian
+        io.out(i, cur);
+    }
+    io.out(n, cur);
+}
+
+GB_HD void gen_poseidon(const Io<GlF>& io) {
+    typedef gates::BaseAlg<GlF> A;
+    const u64 swap = io.raw(12);
+    if (swap > 1) {   // assert!(swap_value == F::ZERO || swap_value == F::ONE)
+        report(io.err, ERR_SWAP_NOT_BOOLEAN, io.op.record, io.args[io.op.in_off + 12]);
+        return;
+    }
+    u64 s[12];
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) {
+        const u64 lhs = io.raw(i), rhs = io.raw(i + 4), delta = swap ? gl::sub(rhs, lhs) : 0;
+        io.put(i, delta);
+        s[i] = gl::add(lhs, delta);
+        s[i + 4] = gl::sub(rhs, delta);
+    }
+#pragma unroll
+    for (u32 i = 8; i < 12; i++) s[i] = io.raw(i);
+    // outputs: wires 25..134 (the deltas and the s-box inputs), then wires 12..23
+    gates::poseidon_gate_rounds<A>(s, [&](u32 col, u64 computed) -> u64 {
+        io.put(col >= 25 ? col - 25 : 110 + (col - 12), computed);
+        return computed;
+    });
+}
+
+GB_HD void gen_poseidon2_bb(const Io<BbF>& io) {
+    typedef gates::BaseAlg<BbF> A;
+    const u32 swap = io.raw(16);
+    if (swap > 1) {
+        report(io.err, ERR_SWAP_NOT_BOOLEAN, io.op.record, io.args[io.op.in_off + 16]);
+        return;
+    }
+    u32 s[16];
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) {
+        const u32 lhs = io.in(i), rhs = io.in(i + 8), delta = swap ? bb::sub(rhs, lhs) : 0;
+        io.out(i, delta);
+        s[i] = bb::add(lhs, delta);
+        s[i + 8] = bb::sub(rhs, delta);
+    }
+    // outputs: the operation's 133 non-routed wires (8 deltas, then the s-box inputs), then its 16 output wires
+    gates::poseidon2_gate_rounds<BbF, A>(s, 8, 133, [&](u32 col, u32 computed) -> u32 {
+        io.out(col, computed);
+        return computed;
+    });
+}
+
+template <class F>
+GB_HD void gen_apply_mat4(const Io<F>& io) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    constexpr u32 D = F::D;
+    const X x0 = X::load(io, 0), x1 = X::load(io, D), x2 = X::load(io, 2 * D), x3 = X::load(io, 3 * D);
+    const X t01 = x0 + x1, t23 = x2 + x3, t0123 = t01 + t23, t01123 = t0123 + x1, t01233 = t0123 + x3;
+    io.out_ext(0, t01123 + t01);
+    io.out_ext(D, t01123 + (x2 + x2));
+    io.out_ext(2 * D, t01233 + t23);
+    io.out_ext(3 * D, t01233 + (x0 + x0));
+}
+
+template <class F>
+GB_HD void gen_poseidon2_internal(const Io<F>& io) {
+    typedef gates::Tup<F, gates::BaseAlg<F>> X;
+    constexpr u32 D = F::D;
+    constexpr u32 SHIFTS[15] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15};
+    const typename F::T k = F::enc(943718400u);
+    X part = X::zero();
+#pragma unroll 1
+    for (u32 i = 1; i < 16; i++) part = part + X::load(io, i * D).scalar_c(k);
+    const X s0 = X::load(io, 0).scalar_c(k), full = part + s0;
+    io.out_ext(0, part - s0);
+#pragma unroll 1
+    for (u32 i = 0; i < 15; i++) io.out_ext((1 + i) * D, full + X::load(io, (i + 1) * D).scalar_c(F::mul(k, F::enc((u64)1 << SHIFTS[i]))));
+}
+
+template <class F>
+GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err) {
+    typedef typename F::T T;
+    const Io<F> io{op, args, values, err};
+    switch (op.kind) {
+        case GEN_ARITHMETIC:
+            io.out(0, F::add(F::mul(F::mul(io.in(0), io.in(1)), F::enc(op.k[0])), F::mul(io.in(2), F::enc(op.k[1]))));
+            break;
+        case GEN_ARITHMETIC_EXTENSION: gen_arithmetic_extension<F>(io, true); break;
+        case GEN_MUL_EXTENSION: gen_arithmetic_extension<F>(io, false); break;
+        case GEN_CONSTANT: io.put(0, (T)op.k[0]); break;
+        case GEN_COPY: io.put(0, io.raw(0)); break;
+        case GEN_BASE_SPLIT: gen_base_split<F>(io); break;
+        case GEN_REDUCING: gen_reducing<F>(io, false); break;
+        case GEN_REDUCING_EXTENSION: gen_reducing<F>(io, true); break;
+        case GEN_RANDOM_ACCESS: gen_random_access<F>(io); break;
+        case GEN_POSEIDON_MDS:
+            if constexpr (F::TAG == 0) gen_poseidon_mds<F>(io);
+            break;
+        case GEN_COSET_INTERPOLATION: gen_coset_interpolation<F>(io); break;
+        case GEN_EXPONENTIATION: gen_exponentiation<F>(io); break;
+        case GEN_POSEIDON:
+            if constexpr (F::TAG == 0) gen_poseidon(io);
+            break;
+        case GEN_POSEIDON2_BABYBEAR:
+            if constexpr (F::TAG == 1) gen_poseidon2_bb(io);
+            break;
+        case GEN_ADD_MANY: {
+            T sum = F::zero();
+            for (u32 j = 0; j < op.p0; j++) sum = F::add(sum, io.in(j));
+            io.out(0, sum);
+            break;
+        }
+        case GEN_APPLY_MAT4: gen_apply_mat4<F>(io); break;
+        case GEN_POSEIDON2_INTERNAL:
+            if constexpr (F::TAG == 1) gen_poseidon2_internal<F>(io);
+            break;
+        default: break;
+    }
+}
+
+#if defined(__HIPCC__)
+// one thread per generator of a level
+template <class F>
+__global__ __launch_bounds__(GROUP) void k_generate_level(const Op* __restrict__ ops, const u32* __restrict__ args, u32 first, u32 count,
+                                                          typename F::T* values, u32* err) {
+    const u32 i = blockIdx.x * GROUP + threadIdx.x;
+    if (i < count) run_op<F>(ops[first + i], args, values, err);
+}
+
+// ONE workgroup walks levels first_level .. first_level + num_levels of level_off, each at most GROUP wide, with a barrier
+// between levels: __syncthreads() is a workgroup-scope release, the barrier and a workgroup-scope acquire, which is all a
+// hand-off inside one workgroup - one CU, one vector L1 - needs.  Nothing is handed to another workgroup.
+template <class F>
+__global__ __launch_bounds__(GROUP) void k_generate_chain(const Op* __restrict__ ops, const u32* __restrict__ args,
+                                                          const u32* __restrict__ level_off, u32 first_level, u32 num_levels,
+                                                          typename F::T* values, u32* err) {
+    for (u32 l = 0; l < num_levels; l++) {
+        const u32 lo = level_off[first_level + l], hi = level_off[first_level + l + 1];
+        for (u32 i = lo + threadIdx.x; i < hi; i += GROUP) run_op<F>(ops[i], args, values, err);
+        __syncthreads();
+    }
+}
+
+// values[cls[i]] = in[i] for the inputs that are the first of their class (the host has compared the others)
+template <class F>
+__global__ __launch_bounds__(GROUP) void k_scatter_inputs(const u32* __restrict__ cls, const typename F::T* __restrict__ in, u32 count,
+                                                          typename F::T* values) {
+    const u32 i = blockIdx.x * GROUP + threadIdx.x;
+    if (i < count && cls[i] != OUT_SKIP) values[cls[i]] = in[i];
+}
+
+// what the host needs before the first challenge, in one block: the public inputs' values, then the error word
+template <class F>
+__global__ __launch_bounds__(GROUP) void k_gather_public(const u32* __restrict__ pi_cls, u32 count, const typename F::T* values,
+                                                         const u32* err, u64* out) {
+    const u32 i = blockIdx.x * GROUP + threadIdx.x;
+    if (i < count) out[i] = (u64)values[pi_cls[i]];
+    if (i < ERROR_WORDS) out[count + i] = err[i];
+}
+
+// the launches of one generation pass on `stream`; `values` holds the inputs, everything else zero; err is zero
+template <class F>
+inline void launch_generators(const DeviceSchedule& d, const Launch* launches, size_t num_launches, const u32* level_off_host,
+                              typename F::T* values, u32* err, hipStream_t stream) {
+    for (size_t k = 0; k < num_launches; k++) {
+        const Launch& L = launches[k];
+        if (L.chain) {
+            hipLaunchKernelGGL(k_generate_chain<F>, dim3(1), dim3(GROUP), 0, stream, d.ops, d.args, d.level_off, L.first_level, L.num_levels,
+                               values, err);
+        } else {
+            const u32 first = level_off_host[L.first_level], count = level_off_host[L.first_level + 1] - first;
+            hipLaunchKernelGGL(k_generate_level<F>, dim3((count + GROUP - 1) / GROUP), dim3(GROUP), 0, stream, d.ops, d.args, first, count,
+                               values, err);
+        }
+    }
+}
+#endif
+
+}  // namespace gen
+}  // namespace gbk

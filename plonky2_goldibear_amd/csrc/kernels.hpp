@@ -9,6 +9,7 @@
 
 #include "field_traits.hpp"
 #include "gate_set.hpp"
+#include "generator_ops.hpp"
 #include "challenge_slices.hpp"
 
 namespace gbk {
@@ -119,6 +120,17 @@ void reduce_words(typename F::T* p, size_t count, hipStream_t stream);
 // [2^log_n][num_wires] row-major, out [num_wires][2^log_n]; words are copied as they are
 template <class F>
 void expand_partition(const u32* slots, const typename F::T* staged, typename F::T* out, u32 log_n, u32 num_wires, hipStream_t stream);
+// generate_partial_witness on the device (kernels_generators.hip, generators.hpp): the launches of a schedule
+// (generator_schedule.hpp) over `values`, one canonical word per copy class - the inputs scattered, everything else zero
+template <class F>
+void run_generators(const gen::DeviceSchedule& d, const gen::Launch* launches, size_t num_launches, const u32* level_off_host,
+                    typename F::T* values, u32* err, hipStream_t stream);
+// values[cls[i]] = in[i] (cls[i] = gen::OUT_SKIP: left out)
+template <class F>
+void scatter_inputs(const u32* cls, const typename F::T* in, u32 count, typename F::T* values, hipStream_t stream);
+// out[0 .. count) = values[pi_cls[i]], out[count .. count + gen::ERROR_WORDS) = the error word
+template <class F>
+void gather_public(const u32* pi_cls, u32 count, const typename F::T* values, const u32* err, u64* out, hipStream_t stream);
 
 // ---------------------------------------------------------------- stand-alone transforms and trees (kernels_poly.hip)
 // The transform passes move canonical words and convert nothing (the transforms are linear and multiply by table values only:

@@ -9,6 +9,7 @@
 #include <array>
 
 #include "gates.hpp"
+#include "generator_schedule.hpp"
 #include "partition_map.hpp"
 
 struct gb_circuit {
@@ -45,6 +46,7 @@ struct gb_circuit {
     struct Partition {
         bool set = false;
         std::vector<uint32_t> reps, pi_reps;
+        std::vector<uint32_t> rep_map;      // the map itself (targets are below 2^32): gb_circuit_set_generators resolves targets with it
         std::vector<uint64_t> shared;
         uint64_t num_targets = 0;
         uint32_t* slots_dev = nullptr;
@@ -55,6 +57,24 @@ struct gb_circuit {
         size_t matrix_bytes = 0;
         bool is_shared_slot(uint32_t k) const { return (shared[k >> 6] >> (k & 63)) & 1; }
     } part;
+    // gb_circuit_set_generators: the schedule of generator_schedule.hpp - its launches, levels and input classes on the host, the
+    // ops, operands and level offsets on the device - and the device error word of the generator kernels.
+    struct Generators {
+        bool set = false;
+        gbk::gen::Schedule sched;
+        gbk::gen::Op* ops_dev = nullptr;
+        uint32_t *args_dev = nullptr, *level_off_dev = nullptr, *input_cls_dev = nullptr, *pi_cls_dev = nullptr, *err_dev = nullptr;
+        std::vector<std::pair<uint64_t, uint32_t>> input_index;   // (target, index into input_targets), ascending
+        std::vector<uint8_t> input_fast;    // the input may be re-drawn inside a kept matrix (gb_prove_inputs_retry)
+        std::vector<uint64_t> kept_pis;     // the public inputs of the attempt that left part.matrix == kept_for behind
+        const void* kept_for = nullptr;
+    } gens;
+    void drop_generators() {   // (the caller has waited for the stream)
+        for (void* p : {(void*)gens.ops_dev, (void*)gens.args_dev, (void*)gens.level_off_dev, (void*)gens.input_cls_dev, (void*)gens.pi_cls_dev,
+                        (void*)gens.err_dev})
+            if (p) (void)hipFree(p);
+        gens = Generators{};
+    }
     void drop_retry() {
         if (retry.wires) gb_batch_free(retry.wires);
         if (ctx && retry.wit_vals) pool_free(ctx, retry.wit_vals, retry.wit_bytes);
@@ -63,8 +83,10 @@ struct gb_circuit {
         if (ctx && part.matrix) pool_free(ctx, part.matrix, part.matrix_bytes);
         part.matrix = nullptr;
         part.matrix_bytes = 0;
+        gens.kept_for = nullptr;
     }
     void drop_partition() {   // (the caller has waited for the stream)
+        drop_generators();
         if (part.slots_dev) (void)hipFree(part.slots_dev);
         if (part.staged_host) (void)hipHostFree(part.staged_host);
         if (part.staged_read) (void)hipEventDestroy(part.staged_read);
@@ -1862,6 +1884,176 @@ static gb_status abi_expand_partition(Circuit<F>* c, const void* values, uint32_
     return expand_partition_stage<F>(c, tmp, values, flags, static_cast<typename F::T*>(witness_dev_out));
 }
 
+
+// ---------------------------------------------------------------------------------------------- the witness generators
+// prove()'s first call, generate_partial_witness (plonk/prover.rs:136-158; "run N generators", iop/generator.rs:25-106), on the
+// device: the inputs are uploaded and scattered to their classes, the schedule's launches (generators.hpp) fill the values array -
+// one canonical word per class, the slots of the partition map first - and one block comes back: the public inputs' values and
+// the error word.  k_expand_partition then reads the front of that array where gb_prove_partition reads its staged upload.
+template <class F>
+static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_values, uint32_t flags, typename F::T* values_dev,
+                                std::vector<uint64_t>* pis) {
+    typedef typename F::T T;
+    namespace GN = gbk::gen;
+    gb_ctx* ctx = c->ctx;
+    gb_circuit::Generators& g = c->gens;
+    const GN::Schedule& sc = g.sched;
+    hipStream_t st = ctx->stream;
+    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
+    const size_t ni = sc.input_cls.size(), npi = sc.pi_cls.size();
+    Scope scope(ctx, "run generators");
+    // the inputs: canonical, below p, and equal where two of them name one class (witness.rs:340-350).  They go up in slices of
+    // the context's page-locked arena (stage_up), each filled and handed to one asynchronous copy; only a context that has no
+    // arena copies from pageable memory, and waits for that copy before the buffer goes
+    auto canonical = [&](size_t i) {
+        T v = static_cast<const T*>(input_values)[i];
+        return p3 ? (T)Host<F>::p3_to_canonical(F::reduce_word(v)) : v;
+    };
+    HIP_TRY(ctx, hipMemsetAsync(values_dev, 0, (size_t)sc.num_classes * sizeof(T), st));
+    HIP_TRY(ctx, hipMemsetAsync(g.err_dev, 0, GN::ERROR_WORDS * sizeof(uint32_t), st));
+    if (ni) {
+        T* in_dev = tmp.get<T>(ni);
+        if (!in_dev) return fail(ctx, GB_ERR_OOM, "generator inputs");
+        const size_t slice = XFER_UP_BYTES / 4 / sizeof(T);
+        std::vector<T> pageable;
+        for (size_t i0 = 0; i0 < ni; i0 += slice) {
+            const size_t count = std::min(slice, ni - i0);
+            T* host = static_cast<T*>(stage_up(ctx, count * sizeof(T)));
+            const bool staged = host != nullptr;
+            if (!staged) {
+                pageable.resize(count);
+                host = pageable.data();
+            }
+            for (size_t i = i0; i < i0 + count; i++) {
+                const T v = canonical(i);
+                if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element (input " + std::to_string(i) + ")");
+                host[i - i0] = v;
+                if (sc.input_first[i] != i && canonical(sc.input_first[i]) != v)
+                    return fail(ctx, GB_ERR_INVALID, "Partition containing target " + std::to_string(sc.class_reps[sc.input_cls[i]]) +
+                                " was set twice with different values (inputs " + std::to_string(sc.input_first[i]) + " and " + std::to_string(i) + ")");
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(in_dev + i0, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+            if (!staged) HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
+        gbk::scatter_inputs<F>(g.input_cls_dev, in_dev, (u32)ni, values_dev, st);
+    }
+    const GN::DeviceSchedule ds{g.ops_dev, g.args_dev, g.level_off_dev};
+    gbk::run_generators<F>(ds, sc.launches.data(), sc.launches.size(), sc.level_off.data(), values_dev, g.err_dev, st);
+    u64* back_dev = tmp.get<u64>(npi + GN::ERROR_WORDS);
+    if (!back_dev) return fail(ctx, GB_ERR_OOM, "generator read-back");
+    gbk::gather_public<F>(g.pi_cls_dev, (u32)npi, values_dev, g.err_dev, back_dev, st);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
+    std::vector<u64> back(npi + GN::ERROR_WORDS);
+    {
+        ReadBack rb(ctx);
+        if (gb_status rs = rb.add(back.data(), back_dev, back.size() * sizeof(u64))) return rs;
+        if (gb_status rs = rb.finish()) return rs;
+    }
+    const u32 code = (u32)back[npi], record = (u32)back[npi + 1], cls = (u32)back[npi + 2];
+    if (code != GN::ERR_NONE) {
+        const std::string rec = "generator record " + std::to_string(record) + ": ";
+        const std::string target = cls < sc.class_reps.size() ? std::to_string(sc.class_reps[cls]) : std::string("?");
+        switch (code) {
+            case GN::ERR_SET_TWICE:
+                return fail(ctx, GB_ERR_INVALID, rec + "Partition containing target " + target + " was set twice with different values");
+            case GN::ERR_SWAP_NOT_BOOLEAN:
+                return fail(ctx, GB_ERR_INVALID, rec + "the swap wire (target " + target + ") is neither 0 nor 1");
+            case GN::ERR_ACCESS_INDEX:
+                return fail(ctx, GB_ERR_INVALID, rec + "Access index (target " + target + ") is larger than the vector size");
+            case GN::ERR_SPLIT_TOO_LARGE:
+                return fail(ctx, GB_ERR_INVALID, rec + "Integer too large to fit in given number of limbs");
+            default:
+                return fail(ctx, GB_ERR_HIP, rec + "unknown generator error word");
+        }
+    }
+    if (pis) pis->assign(back.begin(), back.begin() + npi);
+    return GB_OK;
+}
+
+template <class F>
+static gb_status prove_inputs(Circuit<F>* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
+                              size_t proof_cap, size_t* proof_len, const RetryHint* hint) {
+    typedef typename F::T T;
+    gb_ctx* ctx = c->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const gb_circuit_config& cfg = c->cfg;
+    const size_t n = (size_t)1 << cfg.degree_bits, N = n << cfg.rate_bits;
+    const u32 nw = cfg.num_wires;
+    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
+    hipStream_t st = ctx->stream;
+    gb_circuit::Generators& g = c->gens;
+    gb_status s;
+    std::vector<uint64_t> pis;
+    struct MatrixGuard {
+        gb_ctx* ctx; void* p; size_t bytes;
+        ~MatrixGuard() { if (p) pool_free(ctx, p, bytes); }
+    } matrix{ctx, nullptr, (size_t)nw * n * sizeof(T)};
+    TmpAlloc tmp(ctx);
+    // the retry (prover.rs:186-226): the caller re-drew ONE input.  Where no generator reads, writes or checks its class, no public
+    // input is in it and one wire cell alone carries it - prover_data.random_wire - the matrix and the public inputs the failed
+    // attempt kept are right but for that cell (prove_partition's incremental path from here on)
+    bool incremental = hint && !salts && c->retry.wires && c->retry.seg.state && c->part.matrix && g.kept_for == c->part.matrix &&
+                       hint->wire < nw && hint->row < n;
+    if (incremental) {
+        const uint64_t target = hint->row * nw + hint->wire;
+        auto it = std::lower_bound(g.input_index.begin(), g.input_index.end(), std::make_pair(target, (uint32_t)0));
+        if (it == g.input_index.end() || it->first != target || !g.input_fast[it->second]) {
+            incremental = false;
+        } else {
+            T v = static_cast<const T*>(input_values)[it->second];
+            if (p3) v = (T)Host<F>::p3_to_canonical(F::reduce_word(v));
+            if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
+            pis = g.kept_pis;
+            matrix.p = c->part.matrix;
+            c->part.matrix = nullptr;
+            c->part.matrix_bytes = 0;
+            Scope sc(ctx, "compute full witness");
+            u32* cell = reinterpret_cast<u32*>(static_cast<T*>(matrix.p) + (size_t)hint->wire * n + hint->row);
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)v, 1, st));
+            if (sizeof(T) == 8) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(cell + 1), (int)(u32)((u64)v >> 32), 1, st));
+        }
+    }
+    g.kept_for = nullptr;
+    if (!incremental) {
+        hint = nullptr;
+        c->drop_retry();
+        if (pool_alloc(ctx, matrix.bytes, &matrix.p) != hipSuccess) { matrix.p = nullptr; return fail(ctx, GB_ERR_OOM, "witness matrix"); }
+        T* values_dev = tmp.get<T>(g.sched.num_classes);
+        if (!values_dev) return fail(ctx, GB_ERR_OOM, "generated values");
+        if ((s = generate_stage<F>(c, tmp, input_values, flags, values_dev, &pis))) return s;
+        Scope sc(ctx, "compute full witness");   // full_witness(): the expansion alone, straight from the generated values
+        gbk::expand_partition<F>(c->part.slots_dev, values_dev, static_cast<T*>(matrix.p), cfg.degree_bits, nw, st);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
+    }
+    const T* salts_dev = nullptr;
+    if (salts) {
+        const size_t count = (size_t)3 * GB_SALT_SIZE * N;
+        T* sd = tmp.get<T>(count);
+        if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
+        HIP_TRY(ctx, hipMemcpyAsync(sd, salts, count * sizeof(T), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));   // the salts are the caller's again
+        if (p3) p3_to_canonical_dev<F>(sd, count, st);
+        salts_dev = sd;
+    }
+    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE, pis.data(), pis.size(), salts_dev, proof_out, proof_cap, proof_len, hint);
+    if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
+        c->part.matrix = matrix.p;
+        c->part.matrix_bytes = matrix.bytes;
+        g.kept_for = matrix.p;
+        g.kept_pis = pis;
+        matrix.p = nullptr;
+    }
+    return s;
+}
+
+template <class F>
+static gb_status abi_generate_partition(Circuit<F>* c, const void* input_values, uint32_t flags, void* values_dev_out) {
+    gb_ctx* ctx = c->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TmpAlloc tmp(ctx);
+    return generate_stage<F>(c, tmp, input_values, flags, static_cast<typename F::T*>(values_dev_out), nullptr);
+}
+
 extern "C" {
 
 gb_status gb_pow_grind(gb_ctx* ctx, uint32_t field, const void* sponge_state, uint32_t witness_pos, uint32_t min_leading_zeros,
@@ -2190,6 +2382,8 @@ gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative
     HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(4, m.slots.size() * sizeof(uint32_t))));
     c->part.slots_dev = static_cast<uint32_t*>(p);
     HIP_TRY(ctx, hipMemcpy(p, m.slots.data(), m.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    c->part.rep_map.resize(num_targets);
+    for (uint64_t t = 0; t < num_targets; t++) c->part.rep_map[t] = (uint32_t)representative_map[t];
     c->part.reps = std::move(m.reps);
     c->part.pi_reps = std::move(m.pi_reps);
     c->part.shared = std::move(m.shared);
@@ -2237,6 +2431,161 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
     if (!witness_dev_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
     return c->field == GB_GOLDILOCKS ? abi_expand_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, witness_dev_out)
                                      : abi_expand_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, witness_dev_out);
+} GB_CATCH_CIRCUIT(c)
+
+// ---- the witness generators (templates above: generate_stage, prove_inputs)
+// replaces the host's generate_partial_witness (plonk/prover.rs:136-158, iop/generator.rs:25-106): the generators as data, scheduled once
+gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
+                                    uint64_t num_inputs, const uint64_t* constants, uint32_t flags) try {
+    namespace GN = gbk::gen;
+    if (gb_status s = stage_guard(c)) return s;
+    gb_ctx* ctx = c->ctx;
+    if (flags) return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generators: unknown bits in flags");
+    if (!c->part.set) return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generators: gb_circuit_set_partition has not been called on this circuit");
+    static_assert(sizeof(gb_generator) == sizeof(GN::Record) && offsetof(gb_generator, a) == offsetof(GN::Record, a) &&
+                  offsetof(gb_generator, b) == offsetof(GN::Record, b) && offsetof(gb_generator, gate) == offsetof(GN::Record, gate), "gb_generator");
+    std::vector<GN::GateDesc> gates(c->gates.num_gates);
+    for (u32 i = 0; i < c->gates.num_gates; i++) {
+        const gb_gate& gg = c->gates.g[i];
+        gates[i] = GN::GateDesc{gg.kind, gg.param, gg.param2, gg.param3};
+    }
+    GN::CircuitDesc d;
+    d.representative_map = c->part.rep_map.data();
+    d.num_targets = c->part.num_targets;
+    d.num_wires = c->cfg.num_wires;
+    d.degree_bits = c->cfg.degree_bits;
+    d.num_constants = c->cfg.num_constants;
+    d.ext_degree = c->field == GB_GOLDILOCKS ? GlF::D : BbF::D;
+    d.order = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::ORDER : (uint64_t)BbF::ORDER;
+    d.slot_reps = c->part.reps.data();
+    d.num_slots = c->part.reps.size();
+    d.pi_reps = c->part.pi_reps.data();
+    d.num_public_inputs = c->part.pi_reps.size();
+    d.gates = gates.data();
+    d.num_gates = (uint32_t)gates.size();
+    d.constants = constants;
+    GN::Schedule sched;
+    std::string msg;
+    if (const int ss = GN::build_schedule(d, static_cast<const GN::Record*>(generators), num_generators, input_targets, num_inputs, GN::GROUP, &sched,
+                                          &msg))
+        return fail(ctx, (gb_status)ss, "gb_circuit_set_generators: " + msg);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    c->drop_retry();
+    c->drop_generators();
+    gb_circuit::Generators& g = c->gens;
+    // the inputs that are not the first of their class are compared on the host and left out of the scatter
+    std::vector<uint32_t> scatter(sched.input_cls);
+    std::vector<uint32_t> per_class(sched.num_classes, 0);
+    for (size_t i = 0; i < scatter.size(); i++) {
+        per_class[sched.input_cls[i]]++;
+        if (sched.input_first[i] != i) scatter[i] = GN::OUT_SKIP;
+    }
+    g.input_fast.assign(scatter.size(), 0);
+    g.input_index.resize(scatter.size());
+    for (size_t i = 0; i < scatter.size(); i++) {
+        const uint32_t cl = sched.input_cls[i];
+        g.input_index[i] = std::make_pair(input_targets[i], (uint32_t)i);
+        bool fast = sched.input_free[i] && per_class[cl] == 1 && cl < sched.num_slots && !c->part.is_shared_slot(cl);
+        for (uint32_t pc : sched.pi_cls) fast = fast && pc != cl;
+        g.input_fast[i] = fast;
+    }
+    std::sort(g.input_index.begin(), g.input_index.end());
+    auto upload = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    void* p = nullptr;
+    HIP_TRY(ctx, upload(sched.ops.data(), sched.ops.size() * sizeof(GN::Op), &p));
+    g.ops_dev = static_cast<GN::Op*>(p);
+    HIP_TRY(ctx, upload(sched.args.data(), sched.args.size() * sizeof(uint32_t), &p));
+    g.args_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, upload(sched.level_off.data(), sched.level_off.size() * sizeof(uint32_t), &p));
+    g.level_off_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, upload(scatter.data(), scatter.size() * sizeof(uint32_t), &p));
+    g.input_cls_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, upload(sched.pi_cls.data(), sched.pi_cls.size() * sizeof(uint32_t), &p));
+    g.pi_cls_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, upload(nullptr, 0, &p));
+    g.err_dev = static_cast<uint32_t*>(p);
+    // the kernels read ops and args from the device; the host keeps what it launches and reports with
+    std::vector<GN::Op>().swap(sched.ops);
+    std::vector<uint32_t>().swap(sched.args);
+    g.sched = std::move(sched);
+    g.set = true;
+    return GB_OK;
+} GB_CATCH_CIRCUIT(c)
+
+static gb_status schedule_guard(gb_circuit* c) {   // a schedule is set
+    if (gb_status s = stage_guard(c)) return s;
+    if (!c->part.set || !c->gens.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_generators has not been called on this circuit");
+    return GB_OK;
+}
+static gb_status generators_guard(gb_circuit* c, const void* input_values, uint32_t flags) {   // and these are inputs for it
+    if (gb_status s = stage_guard(c)) return s;
+    if (flags & ~GB_PUBLIC_INPUT_FLAGS) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the inputs are a host object: GB_INPUT_DEVICE does not apply");
+    if (gb_status s = schedule_guard(c)) return s;
+    if (!input_values && !c->gens.sched.input_cls.empty()) return fail(c->ctx, GB_ERR_INVALID, "null argument");
+    return GB_OK;
+}
+
+// what a host that polls "run N generators" would log (iop/generator.rs:25-30)
+gb_status gb_circuit_generators_info(gb_circuit* c, uint32_t* num_levels, uint32_t* num_launches, uint32_t* num_unrunnable,
+                                     uint32_t* num_checks, uint32_t* num_classes) try {
+    if (gb_status s = schedule_guard(c)) return s;
+    const gbk::gen::Schedule& sc = c->gens.sched;
+    if (num_levels) *num_levels = sc.num_levels;
+    if (num_launches) *num_launches = (uint32_t)sc.launches.size();
+    if (num_unrunnable) *num_unrunnable = sc.num_unrunnable;
+    if (num_checks) *num_checks = sc.num_checks;
+    if (num_classes) *num_classes = sc.num_classes;
+    return GB_OK;
+} GB_CATCH_CIRCUIT(c)
+
+// the keys of PartitionWitness.values (iop/witness.rs:318-330) that the generated array holds, in its order
+gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_out, uint64_t capacity) try {
+    if (gb_status s = schedule_guard(c)) return s;
+    const gbk::gen::Schedule& sc = c->gens.sched;
+    if (!class_targets_out || capacity < sc.class_reps.size()) return fail(c->ctx, GB_ERR_INVALID, "class_targets_out holds fewer than num_classes entries");
+    for (size_t k = 0; k < sc.class_reps.size(); k++) class_targets_out[k] = sc.class_reps[k];
+    return GB_OK;
+} GB_CATCH_CIRCUIT(c)
+
+// generate_partial_witness (iop/generator.rs:25-106) alone
+gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_t flags, void* values_dev_out) try {
+    if (gb_status s = generators_guard(c, input_values, flags)) return s;
+    if (!values_dev_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
+    return c->field == GB_GOLDILOCKS ? abi_generate_partition<GlF>(static_cast<Circuit<GlF>*>(c), input_values, flags, values_dev_out)
+                                     : abi_generate_partition<BbF>(static_cast<Circuit<BbF>*>(c), input_values, flags, values_dev_out);
+} GB_CATCH_CIRCUIT(c)
+
+static gb_status prove_inputs_entry(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
+                                    size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
+    if (gb_status s = generators_guard(c, input_values, flags)) return s;
+    gb_ctx* ctx = c->ctx;
+    if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if (c->cfg.zero_knowledge && !salts)
+        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
+    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
+    if (gb_status s = need_arity_list(c)) return s;
+    return c->field == GB_GOLDILOCKS
+               ? prove_inputs<GlF>(static_cast<Circuit<GlF>*>(c), input_values, flags, salts, proof_out, proof_cap, proof_len, hint)
+               : prove_inputs<BbF>(static_cast<Circuit<BbF>*>(c), input_values, flags, salts, proof_out, proof_cap, proof_len, hint);
+}
+
+// prove() (plonk/prover.rs:136-158): generate_partial_witness, then prove_with_partition_witness
+gb_status gb_prove_inputs(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
+                          size_t proof_cap, size_t* proof_len) try {
+    return prove_inputs_entry(c, input_values, flags, salts, proof_out, proof_cap, proof_len);
+} GB_CATCH_CIRCUIT(c)
+
+// the second or third attempt of prove_with_partition_witness's loop (plonk/prover.rs:186-226)
+gb_status gb_prove_inputs_retry(gb_circuit* c, const void* input_values, uint32_t flags, uint32_t wire, uint64_t row,
+                                void* proof_out, size_t proof_cap, size_t* proof_len) try {
+    const RetryHint hint{wire, row};
+    return prove_inputs_entry(c, input_values, flags, nullptr, proof_out, proof_cap, proof_len, &hint);
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_quotient_polys(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial_products, const void* public_inputs_hash,

@@ -94,6 +94,12 @@ SIGNATURES = {
     "gb_prove_partition": (_i32, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_partition_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, C.POINTER(_sz)]),
     "gb_expand_partition": (_i32, [_vp, _vp, _u32, _vp]),
+    "gb_circuit_set_generators": (_i32, [_vp, _vp, _u64, C.POINTER(_u64), _u64, C.POINTER(_u64), _u32]),
+    "gb_circuit_generators_info": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gb_circuit_generator_classes": (_i32, [_vp, C.POINTER(_u64), _u64]),
+    "gb_generate_partition": (_i32, [_vp, _vp, _u32, _vp]),
+    "gb_prove_inputs": (_i32, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "gb_prove_inputs_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, C.POINTER(_sz)]),
     "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
     "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
     "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
@@ -104,6 +110,10 @@ SIGNATURES = {
     "gb_merkle_tree_leaf": (_i32, [_vp, _u64, _vp, _vp, C.POINTER(_u32)]),
     "gb_merkle_tree_digests": (_i32, [_vp, _vp]),
 }
+# gb_generator.kind (include/goldibear_gpu.h GB_GEN_*)
+(GB_GEN_ARITHMETIC, GB_GEN_ARITHMETIC_EXTENSION, GB_GEN_MUL_EXTENSION, GB_GEN_CONSTANT, GB_GEN_BASE_SPLIT, GB_GEN_REDUCING,
+ GB_GEN_REDUCING_EXTENSION, GB_GEN_RANDOM_ACCESS, GB_GEN_POSEIDON_MDS, GB_GEN_COSET_INTERPOLATION, GB_GEN_EXPONENTIATION, GB_GEN_POSEIDON,
+ GB_GEN_POSEIDON2_BABYBEAR, GB_GEN_ADD_MANY, GB_GEN_APPLY_MAT4, GB_GEN_POSEIDON2_INTERNAL, GB_GEN_COPY) = range(17)
 # include/goldibear_gpu_test_hooks.h: exports for the test suite, outside the product ABI
 TEST_HOOK_SIGNATURES = {
     "gb_test_arm_perm_arg_failure": (_i32, [_vp]),

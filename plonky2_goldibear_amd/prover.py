@@ -321,6 +321,77 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         N.check(self._lib.gb_ctx_synchronize(self.ctx.handle), self.ctx.handle)
         return out
 
+    # ---- prove() from the inputs alone (include/goldibear_gpu.h: gb_circuit_set_generators, gb_generate_partition, gb_prove_inputs*)
+    GENERATOR_DTYPE = np.dtype([("kind", "<u4"), ("gate", "<u4"), ("a", "<u8"), ("b", "<u8")])   # gb_generator
+
+    def set_generators(self, records, input_targets, constants):
+        """prover_only.generators as gb_generator records [(kind, gate, a, b)], the target indices whose values the host supplies
+        per proof, and the circuit's constants columns [num_constants][n]; after set_partition"""
+        words = np.array(records, dtype=np.uint64).reshape(-1, 4)
+        rec = np.zeros(len(words), dtype=self.GENERATOR_DTYPE)
+        for k, name in enumerate(("kind", "gate", "a", "b")):
+            rec[name] = words[:, k]
+        t = np.ascontiguousarray(input_targets, dtype=np.uint64)
+        k = np.ascontiguousarray(constants, dtype=np.uint64)
+        if k.size != self.cfg.num_constants << self.cfg.degree_bits:
+            raise N.ShapeError(N.GB_ERR_INVALID, "constants must be [num_constants][n]")
+        u64p = C.POINTER(C.c_uint64)
+        N.check(self._lib.gb_circuit_set_generators(self.handle, rec.ctypes.data if rec.size else None, rec.size,
+                                                    t.ctypes.data_as(u64p) if t.size else None, t.size,
+                                                    k.ctypes.data_as(u64p) if k.size else None, 0), self.ctx.handle)
+        self.num_inputs = int(t.size)
+
+    def generators_info(self):
+        """-> dict(num_levels, num_launches, num_unrunnable, num_checks, num_classes) of the schedule"""
+        names = ("num_levels", "num_launches", "num_unrunnable", "num_checks", "num_classes")
+        out = [C.c_uint32() for _ in names]
+        N.check(self._lib.gb_circuit_generators_info(self.handle, *[C.byref(x) for x in out]), self.ctx.handle)
+        return {k: int(v.value) for k, v in zip(names, out)}
+
+    def generator_classes(self):
+        """the representative target of every class of the schedule, in the order of generate_partition's values"""
+        out = np.zeros(self.generators_info()["num_classes"], dtype=np.uint64)
+        N.check(self._lib.gb_circuit_generator_classes(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), out.size), self.ctx.handle)
+        return out
+
+    def _input_values(self, input_values, p3_repr):
+        v = np.ascontiguousarray(input_values, dtype=self._dt)
+        if v.shape != (getattr(self, "num_inputs", -1),):
+            raise N.ShapeError(N.GB_ERR_INVALID, "input_values must have one entry per input target given to set_generators")
+        return v, (N.GB_INPUT_P3_REPR if p3_repr else N.GB_INPUT_HOST)
+
+    def generate_partition(self, input_values, p3_repr=False):
+        """generate_partial_witness (iop/generator.rs:25-106) on the device -> a host array, one canonical value per class of
+        generator_classes()"""
+        import torch
+        v, flags = self._input_values(input_values, p3_repr)
+        out = torch.empty(max(1, self.generators_info()["num_classes"]), dtype=torch.int64 if self._dt == np.uint64 else torch.int32,
+                          device="cuda:%d" % self.ctx.device)
+        torch.cuda.current_stream(out.device).synchronize()
+        N.check(self._lib.gb_generate_partition(self.handle, v.ctypes.data if v.size else None, flags, out.data_ptr()), self.ctx.handle)
+        N.check(self._lib.gb_ctx_synchronize(self.ctx.handle), self.ctx.handle)
+        return out.cpu().numpy().view(self._dt)[:self.generators_info()["num_classes"]]
+
+    def prove_inputs_once(self, input_values, salts=None, retry_wire=None, p3_repr=False):
+        """prove() (plonk/prover.rs:136-158) from the inputs: the generators, full_witness() and the proof on the device"""
+        v, flags = self._input_values(input_values, p3_repr)
+        if self._proof_buf is None:
+            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
+        n = C.c_size_t()
+        out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
+        vp = v.ctypes.data if v.size else None
+        if salts is None and retry_wire is not None:
+            st = self._lib.gb_prove_inputs_retry(self.handle, vp, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap, C.byref(n))
+        else:
+            sa = None
+            if salts is not None:
+                sa = np.ascontiguousarray(salts, dtype=self._dt).reshape(3 * N.GB_SALT_SIZE, -1)
+                if sa.shape[1] != 1 << (self.cfg.degree_bits + self.cfg.rate_bits):
+                    raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N]")
+            st = self._lib.gb_prove_inputs(self.handle, vp, flags, sa.ctypes.data if sa is not None else None, out, cap, C.byref(n))
+        N.check(st, self.ctx.handle)
+        return self._proof_buf[: n.value].tobytes()
+
     @property
     def constants_sigmas_commitment(self):
         """ProverOnlyCircuitData.constants_sigmas_commitment (plonk/circuit_data.rs:532-534): a PolynomialBatch view that the

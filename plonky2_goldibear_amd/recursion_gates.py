@@ -120,6 +120,10 @@ class _ArithmeticExtensionGenerator:
         D, k = gate.E.D, gate.OPERANDS
         self.deps = [t for j in range(k - 1) for t in _ext_wires(row, k * D * i + j * D, D)]
 
+    def record(self, built):
+        kind = N.GB_GEN_ARITHMETIC_EXTENSION if self.g.OPERANDS == 4 else N.GB_GEN_MUL_EXTENSION
+        return (kind, built.row_gates[self.row], self.row, self.i)
+
     def run(self, w, p):
         E, k, D = self.g.E, self.g.OPERANDS, self.g.E.D
         base = k * D * self.i
@@ -150,6 +154,9 @@ class _BaseSplitGenerator:
 
     def __init__(self, gate, row):
         self.g, self.row, self.deps = gate, row, [wire(row, 0)]
+
+    def record(self, built):
+        return (N.GB_GEN_BASE_SPLIT, built.row_gates[self.row], self.row, 0)
 
     def run(self, w, p):
         v = w.get(wire(self.row, 0))
@@ -199,6 +206,10 @@ class _ReducingGenerator:
         self.g, self.row = gate, row
         D = gate.E.D
         self.deps = _ext_wires(row, D, 2 * D) + [wire(row, gate.start_coeffs + k) for k in range(gate.num_coeffs * gate.coeff_width)]
+
+    def record(self, built):
+        kind = N.GB_GEN_REDUCING_EXTENSION if self.g.EXTENSION_COEFFS else N.GB_GEN_REDUCING
+        return (kind, built.row_gates[self.row], self.row, 0)
 
     def run(self, w, p):
         g, E, row = self.g, self.g.E, self.row
@@ -268,6 +279,9 @@ class _RandomAccessGenerator:
         self.g, self.row, self.copy = gate, row, copy
         self.deps = [wire(row, gate.wire_access_index(copy))]
 
+    def record(self, built):
+        return (N.GB_GEN_RANDOM_ACCESS, built.row_gates[self.row], self.row, self.copy)
+
     def run(self, w, p):
         idx = w.get(self.deps[0])
         assert idx < self.g.vec_size, "Access index %d is larger than the vector size %d" % (idx, self.g.vec_size)
@@ -295,6 +309,9 @@ class _PoseidonMdsGenerator:
     def __init__(self, gate, row):
         self.g, self.row = gate, row
         self.deps = _ext_wires(row, 0, 12 * gate.E.D)
+
+    def record(self, built):
+        return (N.GB_GEN_POSEIDON_MDS, built.row_gates[self.row], self.row, 0)
 
     def run(self, w, p):
         E, D = self.g.E, self.g.E.D
@@ -358,6 +375,9 @@ class _InterpolationGenerator:
         D = gate.E.D
         self.deps = [wire(row, 0)] + _ext_wires(row, 1, gate.num_points * D) + _ext_wires(row, gate.start_point, D)
 
+    def record(self, built):
+        return (N.GB_GEN_COSET_INTERPOLATION, built.row_gates[self.row], self.row, 0)
+
     def run(self, w, p):
         g, E, row = self.g, self.g.E, self.row
         D = E.D
@@ -410,6 +430,9 @@ class _ExponentiationGenerator:
         self.g, self.row = gate, row
         self.deps = [wire(row, c) for c in range(1 + gate.num_power_bits)]
 
+    def record(self, built):
+        return (N.GB_GEN_EXPONENTIATION, built.row_gates[self.row], self.row, 0)
+
     def run(self, w, p):
         n, row = self.g.num_power_bits, self.row
         base = w.get(wire(row, 0))
@@ -449,6 +472,9 @@ class _AddManyGenerator:
         self.g, self.row, self.i = gate, row, i
         self.deps = [wire(row, (gate.num_addends + 1) * i + j) for j in range(gate.num_addends)]
 
+    def record(self, built):
+        return (N.GB_GEN_ADD_MANY, built.row_gates[self.row], self.row, self.i)
+
     def run(self, w, p):
         w.set(wire(self.row, (self.g.num_addends + 1) * self.i + self.g.num_addends), sum(w.get(t) for t in self.deps) % p)
 
@@ -477,6 +503,9 @@ class _ApplyMat4Generator:
     def __init__(self, gate, row, op):
         self.g, self.row, self.op = gate, row, op
         self.deps = _ext_wires(row, op * 8 * gate.E.D, 4 * gate.E.D)
+
+    def record(self, built):
+        return (N.GB_GEN_APPLY_MAT4, built.row_gates[self.row], self.row, self.op)
 
     def run(self, w, p):
         E, D = self.g.E, self.g.E.D
@@ -510,6 +539,9 @@ class _Poseidon2InternalGenerator:
     def __init__(self, gate, row):
         self.g, self.row = gate, row
         self.deps = _ext_wires(row, 0, 16 * gate.E.D)
+
+    def record(self, built):
+        return (N.GB_GEN_POSEIDON2_INTERNAL, built.row_gates[self.row], self.row, 0)
 
     def run(self, w, p):
         E, D = self.g.E, self.g.E.D
