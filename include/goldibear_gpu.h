@@ -430,9 +430,30 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
  *     0 for the gates with one generator per row;
  *   GB_GEN_COPY (CopyGenerator, iop/generator.rs): `a` is the source target, `b` the destination target, `gate` is not read.
  * The host lists the generators explicitly: CircuitBuilder::build drops those of the unused operations of partly filled gates
- * (circuit_builder.rs:1252-1270), so they cannot be derived from the gate table.  Not built, GB_ERR_UNSUPPORTED: any other kind -
- * generators of program gates, the lookup pair, and the gadget generators beyond Copy (Equality, NonzeroTest, Split, WireSplit,
- * LowHigh, BaseSum, QuotientExtension, DummyProof); a circuit that has them stays on gb_prove_partition. */
+ * (circuit_builder.rs:1252-1270), so they cannot be derived from the gate table.
+ *
+ * The generators of the gadgets name arbitrary targets and take several records: a HEAD record - `kind` one of
+ * GB_GEN_EQUALITY .. GB_GEN_BASE_SUM, `gate` the generator's parameter (0 where it has none; NOT a gate index), `a` the number
+ * of targets that follow, `b` 0 - and then ceil(a / 2) CONTINUATION records of kind GB_GEN_TARGETS whose `a` and `b` are the
+ * next two targets (Target::index) in order, `gate` 0, the unused `b` of an odd count 0:
+ *   kind                       gate        targets, in order                                      reference
+ *   GB_GEN_EQUALITY            0           x, y, equal, inv                                       gadgets/arithmetic.rs:425-452
+ *   GB_GEN_NONZERO_TEST        0           to_test, dummy                                         iop/generator.rs:400-428
+ *   GB_GEN_QUOTIENT_OR_ZERO    0           numerator, denominator, quotient                       gadgets/arithmetic.rs:487-511
+ *   GB_GEN_QUOTIENT_EXTENSION  0           numerator[D], denominator[D], quotient[D]              gadgets/arithmetic_extension.rs:507-532
+ *   GB_GEN_SPLIT               0           integer, bits[0..64]                                   gadgets/split_join.rs:67-97
+ *   GB_GEN_WIRE_SPLIT          num_limbs   integer, then the WIRE_SUM target of each gate         gadgets/split_join.rs:118-161
+ *   GB_GEN_LOW_HIGH            n_log       integer, low, high                                     gadgets/range_check.rs:89-115
+ *   GB_GEN_BASE_SUM            base B      the sum target, then limbs[1..]                        gadgets/split_base.rs:84-116
+ * GB_GEN_WIRE_SPLIT takes the sum targets, row * num_wires + BaseSumGate::WIRE_SUM (= 0), not the rows.  Each runs its
+ * run_once: Equality sets inv = (x - y)^-1 or 0 and equal = 0 / 1; NonzeroTest sets dummy = 1 for zero, else the inverse;
+ * QuotientOrZero's quotient is 0 for a zero denominator; WireSplit gives each sum integer & (2^num_limbs - 1) and shifts, and with
+ * num_limbs >= 64 gives the first sum the whole value and the others 0; LowHigh with n_log = 0 gives low = 0, high = integer;
+ * BaseSum folds acc * B + limb from the last limb down, in field arithmetic.  A record index in an error message is the head's
+ * index in the array as passed, continuation records counted.
+ *
+ * Not built, GB_ERR_UNSUPPORTED: any other kind (17 .. 31 are reserved) - generators of program gates, the lookup pair, the
+ * Poseidon2-Risc0 gate and DummyProofGenerator; a circuit that has them stays on gb_prove_partition. */
 #define GB_GEN_ARITHMETIC 0
 #define GB_GEN_ARITHMETIC_EXTENSION 1
 #define GB_GEN_MUL_EXTENSION 2
@@ -450,9 +471,18 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
 #define GB_GEN_APPLY_MAT4 14
 #define GB_GEN_POSEIDON2_INTERNAL 15
 #define GB_GEN_COPY 16
+#define GB_GEN_EQUALITY 32
+#define GB_GEN_NONZERO_TEST 33
+#define GB_GEN_QUOTIENT_OR_ZERO 34
+#define GB_GEN_QUOTIENT_EXTENSION 35
+#define GB_GEN_SPLIT 36
+#define GB_GEN_WIRE_SPLIT 37
+#define GB_GEN_LOW_HIGH 38
+#define GB_GEN_BASE_SUM 39
+#define GB_GEN_TARGETS 40
 typedef struct gb_generator {
     uint32_t kind;            /* GB_GEN_* */
-    uint32_t gate;
+    uint32_t gate;            /* a gate generator's gate index; a gadget head's parameter */
     uint64_t a;
     uint64_t b;
 } gb_generator;
@@ -468,7 +498,11 @@ typedef struct gb_generator {
  * A generator with a dependency that nothing ever sets cannot run: it is left out and counted (the reference panics with
  * "{n} generators weren't run"), its outputs stay zero.  GB_ERR_INVALID: a target >= num_targets, a gate index out of range or
  * of another kind than the record's, a row, operation or constant index outside the gate's parameters, an input target listed
- * twice, unknown flags.  Calling it again replaces the schedule; gb_circuit_set_partition drops it. */
+ * twice, unknown flags; and of the gadget records, each with the record's index: a GB_GEN_TARGETS record with no head in front of
+ * it, a head whose continuation runs past the end of the array or meets another kind, a count that does not fit the kind (4, 2,
+ * 3, 3 D; 1..65; >= 2; 3; >= 2), num_limbs = 0, n_log > 63, a base < 2 (`gate` is 32 bits wide: a base >= 2^32 cannot be
+ * written), non-zero `gate` where no parameter is defined, non-zero `b` in a head, non-zero `gate` or padding in a continuation.
+ * Nothing is read past num_generators records.  Calling it again replaces the schedule; gb_circuit_set_partition drops it. */
 gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
                                     uint64_t num_inputs, const uint64_t* constants, uint32_t flags);
 /* what the schedule looks like; any out pointer may be NULL */
@@ -483,8 +517,11 @@ gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_ou
  * classes nothing sets zero.  Returns after the generated values' error word has been read back.  GB_ERR_INVALID: an input
  * >= p ("non-canonical witness element"); two inputs, or an input and a generator, or two generators that set one class to
  * different values ("Partition containing .. was set twice with different values"); a PoseidonGate / Poseidon2BabyBearGate row
- * whose swap wire is not 0 or 1; a RandomAccessGate access index >= 2^bits; a BaseSumGate value that does not fit its limbs -
- * the reference's assert!s, with the record index in gb_last_error.  Nothing faults and the circuit stays usable. */
+ * whose swap wire is not 0 or 1; a RandomAccessGate access index >= 2^bits; a BaseSumGate value that does not fit its limbs; a
+ * QuotientGeneratorExtension with a zero denominator ("Tried to invert zero"); a BaseSumGenerator limb that is neither 0 nor 1
+ * (get_bool_target: "not a bool"); a SplitGenerator / WireSplitGenerator value that does not fit its bits ("Integer too large
+ * .." - the reference checks this one with debug_assert_eq!, that is in debug builds only; here it is always checked) - the
+ * reference's assert!s, with the record index in gb_last_error.  Nothing faults and the circuit stays usable. */
 gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_t flags, void* values_dev_out);
 /* prove(): upload the inputs, run the generators (timing scope "run generators"), k_expand_partition straight from the generated
  * values ("compute full witness" is now the expansion alone), then the device-witness path of gb_prove unchanged.  The public

@@ -44,6 +44,15 @@ pub const GB_GEN_ADD_MANY: u32 = 13;
 pub const GB_GEN_APPLY_MAT4: u32 = 14;
 pub const GB_GEN_POSEIDON2_INTERNAL: u32 = 15;
 pub const GB_GEN_COPY: u32 = 16;
+pub const GB_GEN_EQUALITY: u32 = 32;
+pub const GB_GEN_NONZERO_TEST: u32 = 33;
+pub const GB_GEN_QUOTIENT_OR_ZERO: u32 = 34;
+pub const GB_GEN_QUOTIENT_EXTENSION: u32 = 35;
+pub const GB_GEN_SPLIT: u32 = 36;
+pub const GB_GEN_WIRE_SPLIT: u32 = 37;
+pub const GB_GEN_LOW_HIGH: u32 = 38;
+pub const GB_GEN_BASE_SUM: u32 = 39;
+pub const GB_GEN_TARGETS: u32 = 40;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -79,6 +88,19 @@ pub struct gb_generator {
     pub gate: u32,
     pub a: u64,
     pub b: u64,
+}
+
+/// A gadget generator (GB_GEN_EQUALITY .. GB_GEN_BASE_SUM) appended to `out` as its head record - `param` is the generator's
+/// parameter (num_limbs, n_log, the base; 0 where it has none), `a` the number of targets - and ceil(targets.len() / 2)
+/// GB_GEN_TARGETS continuation records of two `Target::index` values each, in the order include/goldibear_gpu.h lists them for
+/// the kind.  Returns the head's index, which is the record index the library's error messages name.
+pub fn push_gadget_generator(out: &mut Vec<gb_generator>, kind: u32, param: u32, targets: &[usize]) -> usize {
+    let head = out.len();
+    out.push(gb_generator { kind, gate: param, a: targets.len() as u64, b: 0 });
+    for pair in targets.chunks(2) {
+        out.push(gb_generator { kind: GB_GEN_TARGETS, gate: 0, a: pair[0] as u64, b: pair.get(1).map_or(0, |&t| t as u64) });
+    }
+    head
 }
 
 /// `gb_circuit_generators_info`

@@ -16,6 +16,12 @@ Gates: NoopGate, ConstantGate, PublicInputGate, ArithmeticGate (gates/arithmetic
 configuration - PoseidonGate (gates/poseidon_goldilocks.rs) for Goldilocks, Poseidon2BabyBearGate (gates/poseidon2_babybear.rs)
 for BabyBear - which `build()` itself needs as soon as a circuit has public inputs, because it hashes them in-circuit
 (circuit_builder.rs:1126-1137).  The other gates of the recursion circuits are in recursion_gates.py (add_gate() takes them).
+Gadgets, laid out as the reference lays them out, with their SimpleGenerators (add_simple_generator; each has deps, run(w, p) and
+record(built), for these a head tuple and the continuation tuples that carry the targets): is_equal, inverse_or_zero, not_ / and_ /
+or_ / select / _if, assert_bool (gadgets/arithmetic.rs, select.rs); split_le, split_le_base, le_sum, range_check, low_bits,
+split_low_high (split_join.rs, split_base.rs, range_check.rs); extension targets - tuples of D targets - with
+arithmetic_extension, mul / add / sub / div / div_add / inverse_extension, and base div / inverse through them
+(arithmetic_extension.rs).  A BoolTarget is the target itself.
 Not the GPU hot path: plain Python integers.
 """
 import os
@@ -234,6 +240,163 @@ class _CopyGenerator:
         w.set(self.dst, w.get(self.src))
 
 
+class _GadgetGenerator:
+    """A SimpleGenerator of a gadget: its operands are arbitrary targets.  record() is a head tuple (kind, parameter, number of
+    targets, 0) and the GB_GEN_TARGETS continuation tuples that carry the targets two by two (include/goldibear_gpu.h)."""
+    kind, param = None, 0
+
+    def targets(self):
+        raise NotImplementedError
+
+    def record(self, built):
+        return N.gadget_records(self.kind, self.param, [built.target_index(t) for t in self.targets()])
+
+
+class _EqualityGenerator(_GadgetGenerator):
+    """gadgets/arithmetic.rs:425-452"""
+    kind = N.GB_GEN_EQUALITY
+
+    def __init__(self, x, y, equal, inv):
+        self.x, self.y, self.equal, self.inv, self.deps = x, y, equal, inv, [x, y]
+
+    def targets(self):
+        return [self.x, self.y, self.equal, self.inv]
+
+    def run(self, w, p):
+        x, y = w.get(self.x), w.get(self.y)
+        w.set(self.equal, int(x == y))
+        w.set(self.inv, pow((x - y) % p, p - 2, p) if x != y else 0)
+
+
+class _NonzeroTestGenerator(_GadgetGenerator):
+    """iop/generator.rs:400-428"""
+    kind = N.GB_GEN_NONZERO_TEST
+
+    def __init__(self, to_test, dummy):
+        self.to_test, self.dummy, self.deps = to_test, dummy, [to_test]
+
+    def targets(self):
+        return [self.to_test, self.dummy]
+
+    def run(self, w, p):
+        v = w.get(self.to_test)
+        w.set(self.dummy, 1 if v == 0 else pow(v, p - 2, p))
+
+
+class _QuotientOrZeroGenerator(_GadgetGenerator):
+    """gadgets/arithmetic.rs:487-511"""
+    kind = N.GB_GEN_QUOTIENT_OR_ZERO
+
+    def __init__(self, numerator, denominator, quotient):
+        self.numerator, self.denominator, self.quotient, self.deps = numerator, denominator, quotient, [numerator, denominator]
+
+    def targets(self):
+        return [self.numerator, self.denominator, self.quotient]
+
+    def run(self, w, p):
+        num, den = w.get(self.numerator), w.get(self.denominator)
+        w.set(self.quotient, 0 if den == 0 else num * pow(den, p - 2, p) % p)
+
+
+class _QuotientExtensionGenerator(_GadgetGenerator):
+    """gadgets/arithmetic_extension.rs:507-532; the operands are D-tuples of targets"""
+    kind = N.GB_GEN_QUOTIENT_EXTENSION
+
+    def __init__(self, field, numerator, denominator, quotient):
+        self.field, self.numerator, self.denominator, self.quotient = field, list(numerator), list(denominator), list(quotient)
+        self.deps = self.numerator + self.denominator
+
+    def targets(self):
+        return self.numerator + self.denominator + self.quotient
+
+    def run(self, w, p):
+        from .recursion_gates import Ext
+        E = Ext(self.field)
+        num, den = tuple(w.get(t) for t in self.numerator), tuple(w.get(t) for t in self.denominator)
+        assert any(den), "Tried to invert zero"
+        for t, v in zip(self.quotient, E.mul(num, E.inv(den))):
+            w.set(t, v)
+
+
+class _SplitGenerator(_GadgetGenerator):
+    """gadgets/split_join.rs:67-97"""
+    kind = N.GB_GEN_SPLIT
+
+    def __init__(self, integer, bits):
+        self.integer, self.bits, self.deps = integer, list(bits), [integer]
+
+    def targets(self):
+        return [self.integer] + self.bits
+
+    def run(self, w, p):
+        v = w.get(self.integer)
+        for b in self.bits:
+            w.set(b, v & 1)
+            v >>= 1
+        assert v == 0, "Integer too large to fit in given number of bits"
+
+
+class _WireSplitGenerator(_GadgetGenerator):
+    """gadgets/split_join.rs:118-161: `gates` are the rows of the BaseSumGate<2>s"""
+    kind = N.GB_GEN_WIRE_SPLIT
+
+    def __init__(self, integer, gates, num_limbs):
+        self.integer, self.gates, self.num_limbs, self.deps = integer, list(gates), num_limbs, [integer]
+        self.param = num_limbs
+
+    def targets(self):
+        return [self.integer] + [wire(row, 0) for row in self.gates]
+
+    def run(self, w, p):
+        v = w.get(self.integer)
+        for row in self.gates:
+            truncated = v
+            if self.num_limbs < 64:
+                truncated = v & ((1 << self.num_limbs) - 1)
+                v >>= self.num_limbs
+            else:
+                v = 0
+            w.set(wire(row, 0), truncated)
+        assert v == 0, "Integer too large to fit in %d many `BaseSumGate`s" % len(self.gates)
+
+
+class _LowHighGenerator(_GadgetGenerator):
+    """gadgets/range_check.rs:89-115"""
+    kind = N.GB_GEN_LOW_HIGH
+
+    def __init__(self, integer, n_log, low, high):
+        self.integer, self.n_log, self.low, self.high, self.deps = integer, n_log, low, high, [integer]
+        self.param = n_log
+
+    def targets(self):
+        return [self.integer, self.low, self.high]
+
+    def run(self, w, p):
+        v = w.get(self.integer)
+        w.set(self.low, v & ((1 << self.n_log) - 1))
+        w.set(self.high, v >> self.n_log)
+
+
+class _BaseSumGenerator(_GadgetGenerator):
+    """gadgets/split_base.rs:84-116: the limbs are BoolTargets whatever the base"""
+    kind = N.GB_GEN_BASE_SUM
+
+    def __init__(self, row, limbs, base=2):
+        self.row, self.limbs, self.base, self.deps = row, list(limbs), base, list(limbs)
+        self.param = base
+
+    def targets(self):
+        return [wire(self.row, 0)] + self.limbs
+
+    def run(self, w, p):
+        acc = 0
+        for t in reversed(self.limbs):
+            limb = w.get(t)
+            assert limb in (0, 1), "not a bool"
+            acc = (acc * self.base + limb) % p
+        w.set(wire(self.row, 0), acc)
+
+
 class _PoseidonGenerator:
     """gates/poseidon_goldilocks.rs:436-531"""
 
@@ -416,7 +579,8 @@ class _PartitionWitness:
 
 # --------------------------------------------------------------------------------------------- builder
 class CircuitBuilder:
-    """plonk/circuit_builder.rs:142-1409 (no lookups, no zero-knowledge blinding, base arithmetic gate only)."""
+    """plonk/circuit_builder.rs:142-1409 (no lookups, no zero-knowledge blinding; base arithmetic goes through ArithmeticGate,
+    use_base_arithmetic_gate = true as in every stock configuration)."""
 
     def __init__(self, config):
         self.config, self.F = config, _Field(config.field)
@@ -430,6 +594,7 @@ class CircuitBuilder:
         self.copy_constraints, self.generators = [], []
         self.constants_to_targets, self.targets_to_constants = {}, {}
         self.base_arithmetic_results, self.current_slots, self.constant_generators = {}, {}, []
+        self.arithmetic_results = {}   # of arithmetic_extension
         self.random_wire = None
 
     # ---- targets
@@ -598,6 +763,274 @@ class CircuitBuilder:
         for t in terms:
             acc = self.mul(acc, t)
         return acc
+
+    def mul_const_add(self, c, x, y):
+        return self.mul_add(self.constant(c), x, y)
+
+    def add_many(self, terms):
+        """gadgets/arithmetic.rs:204-234: ADD_MANY_THRESHOLD = 23 addends fill one operation of an AddManyGate"""
+        from .recursion_gates import AddManyGate
+        terms, threshold = list(terms), 23
+        if len(terms) == threshold:
+            gate = AddManyGate.new_from_config(self.config, threshold)
+            row, i = self.find_slot(gate, (), ())
+            for k, t in enumerate(terms):
+                self.connect(t, wire(row, (gate.num_addends + 1) * i + k))
+            return wire(row, (gate.num_addends + 1) * i + gate.num_addends)
+        if len(terms) < threshold:
+            acc = self.zero()
+            for t in terms:
+                acc = self.add(acc, t)
+            return acc
+        return self.add_many([self.add_many(terms[k:k + threshold]) for k in range(0, len(terms), threshold)])
+
+    # ---- generators of gadgets.  A BoolTarget is the target itself: new_unsafe adds nothing to the circuit.
+    def add_simple_generator(self, generator):
+        """circuit_builder.rs add_simple_generator: an object with deps, run(w, p) and record(built)"""
+        self.generators.append(generator)
+
+    def add_virtual_bool_target_unsafe(self):
+        return self.add_virtual_target()
+
+    def add_virtual_bool_target_safe(self):
+        b = self.add_virtual_target()
+        self.assert_bool(b)
+        return b
+
+    def inverse_or_zero(self, x):
+        """gadgets/arithmetic.rs:366-376"""
+        inv, one = self.add_virtual_target(), self.one()
+        self.add_simple_generator(_QuotientOrZeroGenerator(one, x, inv))
+        return self.mul(one, inv)
+
+    def not_(self, b):
+        return self.sub(self.one(), b)
+
+    def and_(self, b1, b2):
+        return self.mul(b1, b2)
+
+    def or_(self, b1, b2):
+        res_minus_b2 = self.arithmetic(self.F.p - 1, 1, b1, b2, b1)
+        return self.add(res_minus_b2, b2)
+
+    def _if(self, b, x, y):
+        not_b = self.not_(b)
+        maybe_x = self.mul(b, x)
+        return self.mul_add(not_b, y, maybe_x)
+
+    def select(self, b, x, y):
+        """gadgets/select.rs:36-39"""
+        tmp = self.mul_sub(b, y, y)
+        return self.mul_sub(b, x, tmp)
+
+    def is_equal(self, x, y):
+        """gadgets/arithmetic.rs:404-422"""
+        zero = self.zero()
+        equal = self.add_virtual_bool_target_unsafe()
+        not_equal = self.not_(equal)
+        inv = self.add_virtual_target()
+        self.add_simple_generator(_EqualityGenerator(x, y, equal, inv))
+        diff = self.sub(x, y)
+        not_equal_check = self.mul(equal, diff)
+        diff_normalized = self.mul(diff, inv)
+        equal_check = self.sub(diff_normalized, not_equal)
+        self.connect(not_equal_check, zero)
+        self.connect(equal_check, zero)
+        return equal
+
+    def assert_bool(self, b):
+        """gadgets/range_check.rs:82-86"""
+        self.connect(self.mul_sub(b, b, b), self.zero())
+
+    # ---- gadgets/split_join.rs, split_base.rs, range_check.rs
+    def _base_sum_gate_from_config(self, base=2):
+        """BaseSumGate::<B>::new_from_config (gates/base_sum.rs:37-41)"""
+        from .recursion_gates import BaseSumGate
+        limbs, cur = 0, 1   # log_floor(ORDER - 1, B)
+        while cur * base <= min(self.F.p - 1, (1 << 64) - 1):
+            limbs, cur = limbs + 1, cur * base
+        return BaseSumGate(min(limbs, self.config.num_routed_wires - 1), base)
+
+    def split_le(self, integer, num_bits):
+        """gadgets/split_join.rs:27-64 -> num_bits little-endian BoolTargets, limb wires of k BaseSumGate<2> rows"""
+        if num_bits == 0:
+            return []
+        gate = self._base_sum_gate_from_config()
+        k = -(-num_bits // gate.num_limbs)
+        rows = [self.add_gate(gate) for _ in range(k)]
+        bits = [wire(row, 1 + i) for row in rows for i in range(gate.num_limbs)]
+        for b in bits[num_bits:]:
+            self.assert_zero(b)
+        bits = bits[:num_bits]
+        acc = self.zero()
+        for row in reversed(rows):
+            acc = self.mul_const_add(pow(2, gate.num_limbs, self.F.p), acc, wire(row, 0))
+        self.connect(acc, integer)
+        self.add_simple_generator(_WireSplitGenerator(integer, rows, gate.num_limbs))
+        return bits
+
+    def split_le_base(self, x, num_limbs, base):
+        """gadgets/split_base.rs:23-30"""
+        from .recursion_gates import BaseSumGate
+        row = self.add_gate(BaseSumGate(num_limbs, base))
+        self.connect(x, wire(row, 0))
+        return [wire(row, 1 + i) for i in range(num_limbs)]
+
+    def le_sum(self, bits):
+        """gadgets/split_base.rs:39-81: arithmetic operations while they fit one ArithmeticGate, else a BaseSumGate<2> row whose
+        limbs are connected to the bits and whose sum a BaseSumGenerator sets"""
+        bits = list(bits)
+        num_bits = len(bits)
+        if num_bits > (self.F.p).bit_length() - 1:
+            raise ValueError("%d bits may overflow the field" % num_bits)
+        if num_bits == 0:
+            return self.zero()
+        if num_bits - 1 <= ArithmeticGate.new_from_config(self.config).num_ops:
+            two = self.two()
+            total = bits[-1]
+            for bit in reversed(bits[:-1]):
+                total = self.mul_add(two, total, bit)
+            return total
+        if 1 + num_bits > self.config.num_routed_wires:
+            raise ValueError("Not enough routed wires.")
+        gate = self._base_sum_gate_from_config()
+        row = self.add_gate(gate)
+        for i, bit in enumerate(bits):
+            self.connect(bit, wire(row, 1 + i))
+        for i in range(num_bits, gate.num_limbs):
+            self.assert_zero(wire(row, 1 + i))
+        self.add_simple_generator(_BaseSumGenerator(row, bits, 2))
+        return wire(row, 0)
+
+    def range_check(self, x, n_log):
+        self.split_le(x, n_log)
+
+    def low_bits(self, x, num_low_bits, are_noncanonical_indices_ok, num_bits):
+        """gadgets/range_check.rs:28-57; F::ORDER = 2^EXP0 - 2^EXP1 + 1"""
+        exp0, exp1 = (64, 32) if self.config.field == N.GB_GOLDILOCKS else (31, 27)
+        assert num_bits <= exp0
+        res = self.split_le(x, num_bits)
+        if not are_noncanonical_indices_ok:
+            one = self.one()
+            lo_sum, hi_sum = self.add_many(res[:exp1]), self.add_many(res[exp1:])
+            hi_shifted = self.add_const(hi_sum, exp0 - exp1)
+            y = self.inverse_or_zero(hi_shifted)
+            maybe_0 = self.arithmetic(1, self.F.p - 1, hi_shifted, y, one)
+            self.assert_zero(self.mul(maybe_0, lo_sum))
+        return res[:num_low_bits]
+
+    def split_low_high(self, x, n_log, num_bits):
+        """gadgets/range_check.rs:61-80"""
+        low, high = self.add_virtual_target(), self.add_virtual_target()
+        self.add_simple_generator(_LowHighGenerator(x, n_log, low, high))
+        self.range_check(low, n_log)
+        self.range_check(high, num_bits - n_log)
+        pow2 = self.constant(1 << n_log)
+        self.connect(x, self.mul_add(high, pow2, low))
+        return low, high
+
+    # ---- gadgets/arithmetic_extension.rs: an ExtensionTarget is a tuple of D targets
+    def add_virtual_extension_target(self):
+        return tuple(self.add_virtual_targets(self.F.ext_degree))
+
+    def constant_extension(self, c):
+        return tuple(self.constant(x) for x in c)
+
+    def zero_extension(self):
+        return self.constant_extension((0,) * self.F.ext_degree)
+
+    def one_extension(self):
+        return self.constant_extension((1,) + (0,) * (self.F.ext_degree - 1))
+
+    def convert_to_ext(self, t):
+        return (t,) + (self.zero(),) * (self.F.ext_degree - 1)
+
+    def connect_extension(self, src, dst):
+        for s, d in zip(src, dst):
+            self.connect(s, d)
+
+    def target_as_constant_ext(self, t):
+        c = tuple(self.target_as_constant(x) for x in t)
+        return None if None in c else c
+
+    def arithmetic_extension(self, const_0, const_1, m0, m1, addend):
+        """gadgets/arithmetic_extension.rs:27-113: a slot of an ArithmeticExtensionGate, or of a MulExtensionGate for a zero addend"""
+        from .recursion_gates import ArithmeticExtensionGate, Ext, MulExtensionGate
+        p, E = self.F.p, Ext(self.config.field)
+        D = E.D
+        const_0, const_1 = const_0 % p, const_1 % p
+        m0, m1, addend = tuple(m0), tuple(m1), tuple(addend)
+        r = self._arithmetic_extension_special_cases(E, const_0, const_1, m0, m1, addend)
+        if r is not None:
+            return r
+        op = (const_0, const_1, m0, m1, addend)
+        if op in self.arithmetic_results:
+            return self.arithmetic_results[op]
+        if self.target_as_constant_ext(addend) == E.zero:
+            gate = MulExtensionGate.new_from_config(self.config)
+            row, i = self.find_slot(gate, (const_0,), (const_0,))
+            operands = (m0, m1)
+        else:
+            gate = ArithmeticExtensionGate.new_from_config(self.config)
+            row, i = self.find_slot(gate, (const_0, const_1), (const_0, const_1))
+            operands = (m0, m1, addend)
+        base = gate.OPERANDS * D * i
+        for j, operand in enumerate(operands):
+            self.connect_extension(operand, tuple(wire(row, base + j * D + k) for k in range(D)))
+        out = tuple(wire(row, base + (gate.OPERANDS - 1) * D + k) for k in range(D))
+        self.arithmetic_results[op] = out
+        return out
+
+    def _arithmetic_extension_special_cases(self, E, c0, c1, m0, m1, addend):
+        """gadgets/arithmetic_extension.rs:118-171"""
+        zero = self.zero_extension()
+        k0, k1, ka = self.target_as_constant_ext(m0), self.target_as_constant_ext(m1), self.target_as_constant_ext(addend)
+        first_zero = c0 == 0 or m0 == zero or m1 == zero
+        second_zero = c1 == 0 or addend == zero
+        first_const = E.zero if first_zero else (E.scale(E.mul(k0, k1), c0) if k0 is not None and k1 is not None else None)
+        second_const = E.zero if second_zero else (E.scale(ka, c1) if ka is not None else None)
+        if first_const is not None and second_const is not None:
+            return self.constant_extension(E.add(first_const, second_const))
+        if first_zero and c1 == 1:
+            return addend
+        if second_zero:
+            if k0 is not None and E.scale(k0, c0) == E.one:
+                return m1
+            if k1 is not None and E.scale(k1, c0) == E.one:
+                return m0
+        return None
+
+    def add_extension(self, a, b):
+        return self.arithmetic_extension(1, 1, self.one_extension(), a, b)
+
+    def sub_extension(self, a, b):
+        return self.arithmetic_extension(1, self.F.p - 1, self.one_extension(), a, b)
+
+    def mul_extension(self, a, b):
+        return self.arithmetic_extension(1, 0, a, b, self.zero_extension())
+
+    def mul_add_extension(self, a, b, c):
+        return self.arithmetic_extension(1, 1, a, b, c)
+
+    def div_add_extension(self, x, y, z):
+        """gadgets/arithmetic_extension.rs:479-498: x / y + z"""
+        inv, one = self.add_virtual_extension_target(), self.one_extension()
+        self.add_simple_generator(_QuotientExtensionGenerator(self.config.field, one, y, inv))
+        self.connect_extension(self.mul_extension(y, inv), one)
+        return self.mul_add_extension(x, inv, z)
+
+    def div_extension(self, x, y):
+        return self.div_add_extension(x, y, self.zero_extension())
+
+    def inverse_extension(self, x):
+        return self.div_extension(self.one_extension(), x)
+
+    def div(self, x, y):
+        """gadgets/arithmetic.rs:353-357"""
+        return self.div_extension(self.convert_to_ext(x), self.convert_to_ext(y))[0]
+
+    def inverse(self, x):
+        return self.inverse_extension(self.convert_to_ext(x))[0]
 
     # ---- hashing (plonk/config.rs:135-166, hash/poseidon_goldilocks.rs:1116-1143)
     def permute(self, state):
@@ -879,8 +1312,16 @@ class BuiltCircuit:
         return [g.target for g in self.generators if isinstance(g, _RandomValueGenerator)]
 
     def generator_records(self):
-        """prover_only.generators as gb_generator tuples (kind, gate, a, b); a RandomValueGenerator has none"""
-        return [r for r in (g.record(self) for g in self.generators) if r is not None]
+        """prover_only.generators as gb_generator tuples (kind, gate, a, b), flat: a gate generator or a CopyGenerator is one
+        tuple, a gadget generator its head and continuation tuples in a row; a RandomValueGenerator has none"""
+        out = []
+        for g in self.generators:
+            r = g.record(self)
+            if isinstance(r, list):
+                out += r
+            elif r is not None:
+                out.append(r)
+        return out
 
     @property
     def constants_columns(self):

@@ -17,9 +17,17 @@
 //   launches  a maximal run of consecutive levels that are each no wider than one workgroup is ONE launch of the chain kernel;
 //             any wider level is one launch of the level kernel.
 //
-// Record kinds that are not built answer UNSUPPORTED: every kind outside BUILT_KINDS (generator_ops.hpp: what
-// generators.hpp evaluates), program gates, the lookup pair and the gadget generators other than Copy (Equality, NonzeroTest,
-// Split, WireSplit, LowHigh, BaseSum, QuotientExtension, DummyProof), none of which has a record kind.
+// A gate generator is one record (gate, row, operation); CopyGenerator is one record of two targets.  The gadget generators
+// (Equality, NonzeroTest, QuotientOrZero, QuotientExtension, Split, WireSplit, LowHigh, BaseSum: kinds 32..39) name arbitrary
+// targets: a head record (gate = the generator's parameter, a = the number of targets, b = 0) followed by ceil(a / 2)
+// GEN_TARGETS records of two targets each.  Their dependencies and outputs are those targets, taken through the representative
+// map as Copy's are; an error report names the head's index.  A malformed sequence - a continuation without a head, one that
+// runs past the array or meets another kind, a count or parameter that does not fit the kind, non-zero b, gate or padding, a
+// target out of range - answers INVALID with the record index; nothing is read past num_records.
+//
+// Record kinds that are not built answer UNSUPPORTED: every kind outside built_kind() (generator_ops.hpp: what generators.hpp
+// evaluates; 17..31 are reserved), program gates, the lookup pair, the Poseidon2-Risc0 gate and DummyProofGenerator, none of
+// which has a record kind.
 //
 // Host code without HIP dependencies: tests/sanitize/generator_schedule.cpp compiles it alone with the sanitizers.
 #ifndef GOLDIBEAR_GENERATOR_SCHEDULE_HPP
@@ -252,10 +260,50 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
     for (size_t r = 0; r < num_records; r++) {
         const Record& rec = records[r];
         const std::string name = "generator record " + std::to_string(r);
-        if (rec.kind >= GEN_NUM_KINDS) return refuse(SCHED_UNSUPPORTED, name + ": kind " + std::to_string(rec.kind) + " is no built-in generator kind");
-        if (!((BUILT_KINDS >> rec.kind) & 1)) return refuse(SCHED_UNSUPPORTED, name + ": generators of kind " + std::to_string(rec.kind) + " are not built");
+        if (rec.kind == GEN_TARGETS) return refuse(SCHED_INVALID, name + ": a continuation record without a head record in front of it");
+        if (!built_kind(rec.kind)) return refuse(SCHED_UNSUPPORTED, name + ": kind " + std::to_string(rec.kind) + " is no built generator kind");
         Gen g{rec.kind, (uint32_t)r, (uint32_t)args.size(), 0, 0, 0, 0, 0, {0, 0}};
-        if (rec.kind == GEN_COPY) {
+        if (rec.kind >= GEN_GADGET_FIRST) {
+            // a head and its continuation: the targets, dependencies first
+            const uint64_t count = rec.a, D = c.ext_degree;
+            bool count_ok = false, param_ok = rec.gate == 0;
+            uint64_t num_in = 1;
+            switch (rec.kind) {
+                case GEN_EQUALITY: count_ok = count == 4; num_in = 2; break;
+                case GEN_NONZERO_TEST: count_ok = count == 2; break;
+                case GEN_QUOTIENT_OR_ZERO: count_ok = count == 3; num_in = 2; break;
+                case GEN_QUOTIENT_EXTENSION: count_ok = count == 3 * D; num_in = 2 * D; break;
+                case GEN_SPLIT: count_ok = count >= 1 && count <= 65; break;
+                case GEN_WIRE_SPLIT: count_ok = count >= 2; param_ok = rec.gate >= 1; break;
+                case GEN_LOW_HIGH: count_ok = count == 3; param_ok = rec.gate <= 63; break;
+                default: count_ok = count >= 2; param_ok = rec.gate >= 2; break;   // GEN_BASE_SUM: a 32-bit base
+            }
+            if (!count_ok) return refuse(SCHED_INVALID, name + ": " + std::to_string(count) + " targets do not fit a generator of kind " + std::to_string(rec.kind));
+            if (!param_ok) return refuse(SCHED_INVALID, name + ": parameter " + std::to_string(rec.gate) + " is out of range for kind " + std::to_string(rec.kind));
+            if (rec.b) return refuse(SCHED_INVALID, name + ": non-zero b in a head record");
+            const uint64_t cont = count / 2 + (count & 1);
+            if (cont > num_records - r - 1) return refuse(SCHED_INVALID, name + ": the continuation records run past the end of the array");
+            const size_t first = args.size();
+            for (uint64_t i = 0; i < cont; i++) {
+                const Record& t = records[r + 1 + i];
+                if (t.kind != GEN_TARGETS) return refuse(SCHED_INVALID, name + ": the continuation meets a record of kind " + std::to_string(t.kind));
+                if (t.gate) return refuse(SCHED_INVALID, name + ": non-zero gate in a continuation record");
+                const bool half = 2 * i + 1 == count;   // the unused b of an odd count
+                if (t.a >= NT || (!half && t.b >= NT)) return refuse(SCHED_INVALID, name + ": target out of range");
+                if (half && t.b) return refuse(SCHED_INVALID, name + ": non-zero padding in the last continuation record");
+                args.push_back((uint32_t)t.a);
+                if (!half) args.push_back((uint32_t)t.b);
+            }
+            if (rec.kind == GEN_BASE_SUM) {   // listed sum first: the limbs are the dependencies
+                std::rotate(args.begin() + first, args.begin() + first + 1, args.end());
+                num_in = count - 1;
+            }
+            g.num_in = (uint32_t)num_in;
+            g.num_out = (uint32_t)(count - num_in);
+            g.out_off = g.in_off + g.num_in;
+            g.p0 = rec.gate;
+            r += cont;
+        } else if (rec.kind == GEN_COPY) {
             if (rec.a >= NT || rec.b >= NT) return refuse(SCHED_INVALID, name + ": target out of range");
             args.push_back((uint32_t)rec.a);
             args.push_back((uint32_t)rec.b);

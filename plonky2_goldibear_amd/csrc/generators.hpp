@@ -9,6 +9,11 @@
 //   ExponentiationGenerator        gates/exponentiation.rs:248-300       PoseidonGenerator             gates/poseidon_goldilocks.rs:436-531
 //   Poseidon2BabyBearGenerator     gates/poseidon2_babybear.rs:536-676   AddManyGenerator              gates/add_many.rs:167-215
 //   ApplyMat4Generator             gates/apply_mat4.rs:216-270           Poseidon2InternalPermutationGenerator  gates/poseidon2_internal_permutation.rs:225-290
+// and the generators of the gadgets, whose operands are arbitrary targets:
+//   EqualityGenerator              gadgets/arithmetic.rs:425-452         QuotientOrZeroGenerator       gadgets/arithmetic.rs:487-511
+//   NonzeroTestGenerator           iop/generator.rs:400-428              QuotientGeneratorExtension    gadgets/arithmetic_extension.rs:507-532
+//   SplitGenerator / WireSplitGenerator  gadgets/split_join.rs:67-161    LowHighGenerator              gadgets/range_check.rs:89-115
+//   BaseSumGenerator               gadgets/split_base.rs:84-116
 // The values array holds one CANONICAL word per copy class; an evaluator converts to the device form and back (a no-op for
 // Goldilocks).  Every class index comes from the schedule, which range-checked it; values that index something - the access index
 // of RandomAccessGenerator - are compared with their bound before use.  The reference's assert!s end in the device error word,
@@ -249,6 +254,99 @@ GB_HD void gen_poseidon2_internal(const Io<F>& io) {
     for (u32 i = 0; i < 15; i++) io.out_ext((1 + i) * D, full + X::load(io, (i + 1) * D).scalar_c(F::mul(k, F::enc((u64)1 << SHIFTS[i]))));
 }
 
+// ---- the gadget generators: operands are arbitrary targets, in the order generator_schedule.hpp lists them (dependencies, then
+// outputs); the counts are the schedule's, checked against the kind there.
+template <class F>
+GB_HD void gen_equality(const Io<F>& io) {   // x, y -> equal, inv
+    const bool equal = io.raw(0) == io.raw(1);
+    io.put(0, (typename F::T)(equal ? 1 : 0));
+    if (equal) io.put(1, 0);
+    else io.out(1, F::inv(F::sub(io.in(0), io.in(1))));
+}
+
+template <class F>
+GB_HD void gen_nonzero_test(const Io<F>& io) {   // to_test -> dummy
+    if (io.raw(0) == 0) io.put(0, 1);
+    else io.out(0, F::inv(io.in(0)));
+}
+
+template <class F>
+GB_HD void gen_quotient_or_zero(const Io<F>& io) {   // numerator, denominator -> quotient
+    if (io.raw(1) == 0) io.put(0, 0);   // compared before the inversion: pow(0, p - 2) is 0 as well, but says nothing
+    else io.out(0, F::mul(io.in(0), F::inv(io.in(1))));
+}
+
+template <class F>
+GB_HD void gen_quotient_extension(const Io<F>& io) {   // numerator[D], denominator[D] -> quotient[D]
+    typedef typename F::E E;
+    constexpr u32 D = F::D;
+    E num = F::ezero(), den = F::ezero();
+    bool zero = true;
+#pragma unroll
+    for (u32 k = 0; k < D; k++) {
+        F::set_coord(num, k, io.in(k));
+        zero = zero && io.raw(D + k) == 0;
+        F::set_coord(den, k, io.in(D + k));
+    }
+    if (zero) {   // num / dem panics in the reference
+        report(io.err, ERR_DIVIDE_BY_ZERO, io.op.record, io.args[io.op.in_off + D]);
+        return;
+    }
+    const E q = F::emul(num, F::einv(den));
+#pragma unroll
+    for (u32 k = 0; k < D; k++) io.out(k, F::coord(q, k));
+}
+
+template <class F>
+GB_HD void gen_split(const Io<F>& io) {   // integer -> bits, little-endian
+    u64 v = (u64)io.raw(0);
+    for (u32 i = 0; i < io.op.num_out; i++) {
+        io.put(i, (typename F::T)(v & 1));
+        v >>= 1;
+    }
+    if (v) report(io.err, ERR_SPLIT_TOO_LARGE, io.op.record, io.args[io.op.in_off]);
+}
+
+template <class F>
+GB_HD void gen_wire_split(const Io<F>& io) {   // integer -> one sum of num_limbs bits per BaseSumGate
+    const u32 limbs = io.op.p0;
+    u64 v = (u64)io.raw(0);
+    for (u32 i = 0; i < io.op.num_out; i++) {
+        u64 t = v;
+        if (limbs < 64) {   // with 64 limbs or more the first sum takes the whole word; the shift would be undefined
+            t = v & (((u64)1 << limbs) - 1);
+            v >>= limbs;
+        } else {
+            v = 0;
+        }
+        io.put(i, (typename F::T)t);
+    }
+    if (v) report(io.err, ERR_SPLIT_TOO_LARGE, io.op.record, io.args[io.op.in_off]);
+}
+
+template <class F>
+GB_HD void gen_low_high(const Io<F>& io) {   // integer -> low, high; n_log <= 63 (the schedule's check)
+    const u64 v = (u64)io.raw(0);
+    io.put(0, (typename F::T)(v & (((u64)1 << io.op.p0) - 1)));
+    io.put(1, (typename F::T)(v >> io.op.p0));
+}
+
+template <class F>
+GB_HD void gen_base_sum(const Io<F>& io) {   // limbs -> sum, folded from the last limb down in field arithmetic
+    typedef typename F::T T;
+    const T base = F::enc((u64)io.op.p0 % F::ORDER);
+    T acc = F::zero();
+    for (u32 i = io.op.num_in; i-- > 0;) {
+        const u64 limb = (u64)io.raw(i);
+        if (limb > 1) {   // get_bool_target
+            report(io.err, ERR_NOT_BOOLEAN, io.op.record, io.args[io.op.in_off + i]);
+            return;
+        }
+        acc = F::add(F::mul(acc, base), limb ? F::one() : F::zero());
+    }
+    io.out(0, acc);
+}
+
 template <class F>
 GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err) {
     typedef typename F::T T;
@@ -286,6 +384,14 @@ GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err
         case GEN_POSEIDON2_INTERNAL:
             if constexpr (F::TAG == 1) gen_poseidon2_internal<F>(io);
             break;
+        case GEN_EQUALITY: gen_equality<F>(io); break;
+        case GEN_NONZERO_TEST: gen_nonzero_test<F>(io); break;
+        case GEN_QUOTIENT_OR_ZERO: gen_quotient_or_zero<F>(io); break;
+        case GEN_QUOTIENT_EXTENSION: gen_quotient_extension<F>(io); break;
+        case GEN_SPLIT: gen_split<F>(io); break;
+        case GEN_WIRE_SPLIT: gen_wire_split<F>(io); break;
+        case GEN_LOW_HIGH: gen_low_high<F>(io); break;
+        case GEN_BASE_SUM: gen_base_sum<F>(io); break;
         default: break;
     }
 }

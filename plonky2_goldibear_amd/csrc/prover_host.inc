@@ -1962,6 +1962,10 @@ static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_
                 return fail(ctx, GB_ERR_INVALID, rec + "Access index (target " + target + ") is larger than the vector size");
             case GN::ERR_SPLIT_TOO_LARGE:
                 return fail(ctx, GB_ERR_INVALID, rec + "Integer too large to fit in given number of limbs");
+            case GN::ERR_DIVIDE_BY_ZERO:
+                return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (the denominator at target " + target + ")");
+            case GN::ERR_NOT_BOOLEAN:
+                return fail(ctx, GB_ERR_INVALID, rec + "not a bool (target " + target + ")");
             default:
                 return fail(ctx, GB_ERR_HIP, rec + "unknown generator error word");
         }

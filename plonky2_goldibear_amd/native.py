@@ -114,6 +114,16 @@ SIGNATURES = {
 (GB_GEN_ARITHMETIC, GB_GEN_ARITHMETIC_EXTENSION, GB_GEN_MUL_EXTENSION, GB_GEN_CONSTANT, GB_GEN_BASE_SPLIT, GB_GEN_REDUCING,
  GB_GEN_REDUCING_EXTENSION, GB_GEN_RANDOM_ACCESS, GB_GEN_POSEIDON_MDS, GB_GEN_COSET_INTERPOLATION, GB_GEN_EXPONENTIATION, GB_GEN_POSEIDON,
  GB_GEN_POSEIDON2_BABYBEAR, GB_GEN_ADD_MANY, GB_GEN_APPLY_MAT4, GB_GEN_POSEIDON2_INTERNAL, GB_GEN_COPY) = range(17)
+# the gadget generators: a head record (kind, parameter, number of targets, 0) and GB_GEN_TARGETS continuation records
+(GB_GEN_EQUALITY, GB_GEN_NONZERO_TEST, GB_GEN_QUOTIENT_OR_ZERO, GB_GEN_QUOTIENT_EXTENSION, GB_GEN_SPLIT, GB_GEN_WIRE_SPLIT,
+ GB_GEN_LOW_HIGH, GB_GEN_BASE_SUM, GB_GEN_TARGETS) = range(32, 41)
+
+
+def gadget_records(kind, param, targets):
+    """one gadget generator as gb_generator tuples: the head, then ceil(len(targets) / 2) continuation records of two targets"""
+    targets = [int(t) for t in targets]
+    padded = targets + [0] * (len(targets) & 1)
+    return [(kind, int(param), len(targets), 0)] + [(GB_GEN_TARGETS, 0, padded[i], padded[i + 1]) for i in range(0, len(padded), 2)]
 # include/goldibear_gpu_test_hooks.h: exports for the test suite, outside the product ABI
 TEST_HOOK_SIGNATURES = {
     "gb_test_arm_perm_arg_failure": (_i32, [_vp]),

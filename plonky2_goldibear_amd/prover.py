@@ -326,7 +326,8 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
 
     def set_generators(self, records, input_targets, constants):
         """prover_only.generators as gb_generator records [(kind, gate, a, b)], the target indices whose values the host supplies
-        per proof, and the circuit's constants columns [num_constants][n]; after set_partition"""
+        per proof, and the circuit's constants columns [num_constants][n]; after set_partition.  A gadget generator is several
+        records in a row (native.gadget_records: a head, then its GB_GEN_TARGETS continuation): the list is flat"""
         words = np.array(records, dtype=np.uint64).reshape(-1, 4)
         rec = np.zeros(len(words), dtype=self.GENERATOR_DTYPE)
         for k, name in enumerate(("kind", "gate", "a", "b")):

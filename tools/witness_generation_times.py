@@ -13,8 +13,9 @@ For each circuit, appended to --out:
     gb_prove_partition on the mirror's values, the two alternated in one process, --reps of each;
   * beside them the Python mirror's _run_generators time for the same circuit (a Python loop, NOT the reference's Rust
     generate_partial_witness, which nobody has measured on this hardware).
-Circuits: tests/circuits.py recursion_gates_circuit (both fields), factorial_circuit, and a wide arithmetic circuit - 20
-independent multiply-adds per row - at 2^12, 2^14 and 2^16 rows.
+Circuits: a range-check circuit - range_check(x, 32) on a fresh input per check, that is a WireSplitGenerator and BaseSumGate rows -
+at 2^12 and 2^14 rows, both fields (--only-range-checks stops there); tests/circuits.py recursion_gates_circuit (both fields),
+factorial_circuit, and a wide arithmetic circuit - 20 independent multiply-adds per row - at 2^12, 2^14 and 2^16 rows.
 --bench-parent: bench.py on this tree and on a tree of the parent commit (built), alternated, each run a fresh process; the tree
 that goes first alternates from round to round.  --bench-control TREE2 puts a second copy of the parent's tree in this tree's place:
 what the comparison says about two identical trees.
@@ -58,6 +59,23 @@ def wide_arithmetic_circuit(log_rows):
         z = b.add_virtual_target()     # a distinct addend per operation (the builder shares equal operations): an input
         pw.set_target(z, 7 + 3 * i)
         b.mul_add(x, y, z)
+    return b, pw
+
+
+def range_check_circuit(field, log_rows):
+    """range_check(x_i, 32) on a fresh input per check until the rows are full: every check is a WireSplitGenerator (a head and
+    a continuation record) over one BaseSumGate row of 63 limbs (Goldilocks) or two of 30 (BabyBear, whose accumulator also
+    takes an ArithmeticGate operation), and a BaseSplitGenerator per row"""
+    from plonky2_goldibear_amd import native as N
+    from plonky2_goldibear_amd.circuit_builder import CircuitBuilder, CircuitConfig, PartialWitness
+    cfg = CircuitConfig.standard_recursion_config_gl() if field == N.GB_GOLDILOCKS else CircuitConfig.recursion_config_bb_narrow()
+    b, pw = CircuitBuilder(cfg), PartialWitness()
+    i = 0
+    while b.num_gates() < (1 << log_rows) - 8:
+        x = b.add_virtual_target()
+        pw.set_target(x, (0x9E3779B9 * (i + 1)) % min(1 << 32, b.F.p))
+        b.range_check(x, 32)
+        i += 1
     return b, pw
 
 
@@ -114,12 +132,12 @@ def measure(ctx, name, b, pw, reps, out, chain=False):
     ctx.trim()
 
 
-def bench_parent(parent, rounds, steps, out, this=ROOT, label="this commit"):
+def bench_parent(parent, rounds, steps, out, this=ROOT, label="this commit", extra=()):
     """bench.py on this tree and on the parent's, each run a fresh process, alternated - and the tree that goes first alternates
     from round to round too, so that neither tree always runs on the device the other has just warmed up"""
     import json
     import subprocess
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "3"]
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "3"] + list(extra)
     values, order = {"parent": [], "this": []}, []
     for r in range(rounds):
         pair = (("parent", parent), ("this", this))
@@ -131,8 +149,8 @@ def bench_parent(parent, rounds, steps, out, this=ROOT, label="this commit"):
             print(name, values[name][-1], flush=True)
     lo, hi = min(values["parent"]), max(values["parent"])
     inside = [lo <= v <= hi for v in values["this"]]
-    append(out, ["bench.py --gpus 1 --steps %d --warmup 3, parent commit and %s alternated (%d rounds, run order %s), `value` in "
-                 "proofs/s:" % (steps, label, rounds, "".join(order)),
+    append(out, ["bench.py --gpus 1 --steps %d --warmup 3%s, parent commit and %s alternated (%d rounds, run order %s), `value` in "
+                 "proofs/s:" % (steps, "".join(" " + x for x in extra), label, rounds, "".join(order)),
                  "  parent %s" % " ".join("%.3f" % v for v in values["parent"]),
                  "  this   %s" % " ".join("%.3f" % v for v in values["this"]),
                  "  spread of the parent's runs %.3f .. %.3f; the other tree's runs inside it: %d; above it: %d; below it: %d" % (
@@ -145,23 +163,35 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "witness_generation_times.txt"))
     ap.add_argument("--wide-log-rows", type=int, nargs="*", default=[12, 14, 16])
+    ap.add_argument("--range-check-log-rows", type=int, nargs="*", default=[12, 14])
+    ap.add_argument("--only-range-checks", action="store_true", help="the range-check circuits alone")
     ap.add_argument("--bench-parent", metavar="TREE")
     ap.add_argument("--bench-control", metavar="TREE", help="with --bench-parent: compare TREE, a second copy of the parent, instead of this tree")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--bench-steps", type=int, default=10)
+    ap.add_argument("--bench-extra", nargs="*", default=[], metavar="FLAG",
+                    help="further bench.py flags for both trees, without their dashes (no-cpu-baseline no-babybear ..): legs to leave out; `value` is the headline leg either way")
     a = ap.parse_args()
+    a.bench_extra = ["--" + x for x in a.bench_extra]
     if a.bench_parent:     # (no GPU context in this process: the two trees' bench.py runs are its children)
         if a.bench_control:   # the noise of the comparison itself: a second copy of the parent's tree in this commit's place
             ok = bench_parent(os.path.abspath(a.bench_parent), a.rounds, a.bench_steps, a.out, os.path.abspath(a.bench_control),
-                              "a second copy of the parent commit (control)")
+                              "a second copy of the parent commit (control)", extra=a.bench_extra)
         else:
-            ok = bench_parent(os.path.abspath(a.bench_parent), a.rounds, a.bench_steps, a.out)
+            ok = bench_parent(os.path.abspath(a.bench_parent), a.rounds, a.bench_steps, a.out, extra=a.bench_extra)
         return 0 if ok else 1
     import circuits as CS
     from csrc_hash import csrc_sha16
     from plonky2_goldibear_amd import GpuContext, native as N
     ctx = GpuContext(0)
     append(a.out, ["# tools/witness_generation_times.py, csrc %s, %s: times in ms" % (csrc_sha16(), time.strftime("%Y-%m-%d"))])
+    for lg in a.range_check_log_rows:
+        for field, fname in ((N.GB_GOLDILOCKS, "goldilocks"), (N.GB_BABYBEAR, "babybear")):
+            b, pw = range_check_circuit(field, lg)
+            measure(ctx, "range-check circuit, range_check(x, 32) per input (%s)" % fname, b, pw, a.reps, a.out)
+    if a.only_range_checks:
+        ctx.close()
+        return 0
     for field, fname in ((N.GB_GOLDILOCKS, "goldilocks"), (N.GB_BABYBEAR, "babybear")):
         b, pw, _ = CS.recursion_gates_circuit(field, seed=9)
         measure(ctx, "recursion_gates_circuit (%s)" % fname, b, pw, a.reps, a.out)
