@@ -452,8 +452,39 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
  * BaseSum folds acc * B + limb from the last limb down, in field arithmetic.  A record index in an error message is the head's
  * index in the array as passed, continuation records counted.
  *
- * Not built, GB_ERR_UNSUPPORTED: any other kind (17 .. 31 are reserved) - generators of program gates, the lookup pair, the
- * Poseidon2-Risc0 gate and DummyProofGenerator; a circuit that has them stays on gb_prove_partition. */
+ * GENERATOR PROGRAMS: a generator of the user's own - the generators() of a program gate (GB_GATE_PROGRAM), or a SimpleGenerator
+ * handed to CircuitBuilder::add_simple_generator (examples/square_root.rs) - as data, the counterpart of the constraint
+ * programs above and in their word layout.  A program reads num_in dependency values and the constants of one row, and produces
+ * num_out outputs in order:
+ *   word 0   num_in | num_constants << 32          word 1   num_out (high half zero)
+ *   word 2   num_regs | num_literals << 32         word 3   num_instrs (high half zero)
+ *   then num_literals canonical words, then num_instrs instruction words.
+ * An instruction word is a constraint program's: destination register in bits 2-7, operand a in bits 8-31, operand b in bits
+ * 32-55, an operand its space in the low two bits and its index in the 22 above; the spaces are 0 register, 1 DEPENDENCY i (where
+ * a constraint program has wire columns), 2 constant column i after the selectors, read at the record's row, 3 literal i.  The
+ * opcode is (w & 3) | ((w >> 56) & 0xF) << 2 - bits 56-63 are zero in a constraint program, so no word is valid in both formats
+ * with two meanings - and bits 60-63 are zero:
+ *   0 ADD  1 SUB  2 MUL   reg[dst] = a op b, as in a constraint program
+ *   3 OUT                 the next output is a (EMIT's twin); dst and b zero
+ *   4 INV                 reg[dst] = 1 / a; a = 0 is the error "Tried to invert zero"
+ *   5 INV_OR_ZERO         reg[dst] = a.try_inverse().unwrap_or(ZERO)
+ *   6 IS_ZERO             reg[dst] = 1 if a = 0, else 0
+ *   7 SQRT                reg[dst] = a square root of a; SQRT(0) = 0; a non-residue is an error (sqrt(x).unwrap() on None)
+ * The unary operations 4-7 have b zero.  With IS_ZERO and INV_OR_ZERO the generators that branch (Equality, NonzeroTest) are
+ * written branch-free.  SQRT is Tonelli-Shanks step for step as examples/square_root.rs:185-219 writes it, with
+ * z = two_adic_generator(TWO_ADICITY) (the example passes F::bits(), which exceeds the two-adicity).  Nothing in the reference
+ * pins which of the two roots comes out: it is the one this algorithm yields.
+ * Limits: GB_MAX_GENERATOR_PROGRAMS per circuit; per program GB_MAX_PROGRAM_INSTRS, GB_MAX_PROGRAM_REGS, GB_MAX_PROGRAM_LITERALS
+ * as for constraint programs, and num_in + num_out <= GB_MAX_GENERATOR_PROGRAM_TARGETS.
+ * A program generator's record is a gadget-style head of kind GB_GEN_PROGRAM: `gate` is the program's index, `a` the number of
+ * targets (= num_in + num_out) and `b` the row whose constants the program reads (0 for a program without constants), followed
+ * by ceil(a / 2) GB_GEN_TARGETS records: the num_in dependencies, then the num_out outputs.  Wire targets make it a program gate's
+ * generator, virtual targets a gadget's.  It is scheduled like every other generator (levels, one storing writer per class,
+ * comparing writers, unrunnable generators).
+ *
+ * Not built, GB_ERR_UNSUPPORTED: any other kind (17 .. 31 and 41 .. 47 are reserved), a gate generator's record that names a
+ * program gate (a program gate's generators are GB_GEN_PROGRAM records), the lookup pair, the Poseidon2-Risc0 gate and
+ * DummyProofGenerator; a circuit that has them stays on gb_prove_partition. */
 #define GB_GEN_ARITHMETIC 0
 #define GB_GEN_ARITHMETIC_EXTENSION 1
 #define GB_GEN_MUL_EXTENSION 2
@@ -480,9 +511,12 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
 #define GB_GEN_LOW_HIGH 38
 #define GB_GEN_BASE_SUM 39
 #define GB_GEN_TARGETS 40
+#define GB_GEN_PROGRAM 48
+#define GB_MAX_GENERATOR_PROGRAMS 256
+#define GB_MAX_GENERATOR_PROGRAM_TARGETS 1024
 typedef struct gb_generator {
     uint32_t kind;            /* GB_GEN_* */
-    uint32_t gate;            /* a gate generator's gate index; a gadget head's parameter */
+    uint32_t gate;            /* a gate generator's gate index; a gadget head's parameter; a program head's program index */
     uint64_t a;
     uint64_t b;
 } gb_generator;
@@ -502,9 +536,22 @@ typedef struct gb_generator {
  * it, a head whose continuation runs past the end of the array or meets another kind, a count that does not fit the kind (4, 2,
  * 3, 3 D; 1..65; >= 2; 3; >= 2), num_limbs = 0, n_log > 63, a base < 2 (`gate` is 32 bits wide: a base >= 2^32 cannot be
  * written), non-zero `gate` where no parameter is defined, non-zero `b` in a head, non-zero `gate` or padding in a continuation.
+ * Of a GB_GEN_PROGRAM head, with the record's index: no programs set, a program index out of range, a != num_in + num_out, a row
+ * >= degree, non-zero b for a program without constants, and the continuation errors above.
  * Nothing is read past num_generators records.  Calling it again replaces the schedule; gb_circuit_set_partition drops it. */
 gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
                                     uint64_t num_inputs, const uint64_t* constants, uint32_t flags);
+/* The generator programs of the circuit (above), in the table layout of gb_circuit_create_programs: program_words holds the
+ * programs one after another, program_offsets[num_programs + 1] their first words (program_offsets[0] = 0).  After
+ * gb_circuit_set_partition and before gb_circuit_set_generators, whose GB_GEN_PROGRAM records name the programs by index.  Every
+ * program is checked and copied; the tables go to device memory.  Calling it again replaces the programs and drops a schedule
+ * built on the old ones; num_programs = 0 clears them; gb_circuit_set_partition drops them with the schedule.  GB_ERR_INVALID,
+ * naming the program and the instruction: a header over the limits or with bits above num_out / num_instrs, a length that does
+ * not match the header, more constants than the circuit has, a register read before it is written, a register, dependency,
+ * constant or literal index out of range, a literal >= p, a count of OUT other than num_out, an unknown opcode, non-zero bits
+ * 60-63, a non-zero b or (for OUT) dst in a unary operation.  Nothing is read past program_offsets[num_programs] words. */
+gb_status gb_circuit_set_generator_programs(gb_circuit* c, const uint64_t* program_words, const uint32_t* program_offsets,
+                                            uint32_t num_programs);
 /* what the schedule looks like; any out pointer may be NULL */
 gb_status gb_circuit_generators_info(gb_circuit* c, uint32_t* num_levels, uint32_t* num_launches, uint32_t* num_unrunnable,
                                      uint32_t* num_checks, uint32_t* num_classes);

@@ -53,6 +53,9 @@ pub const GB_GEN_WIRE_SPLIT: u32 = 37;
 pub const GB_GEN_LOW_HIGH: u32 = 38;
 pub const GB_GEN_BASE_SUM: u32 = 39;
 pub const GB_GEN_TARGETS: u32 = 40;
+pub const GB_GEN_PROGRAM: u32 = 48;
+pub const GB_MAX_GENERATOR_PROGRAMS: u32 = 256;
+pub const GB_MAX_GENERATOR_PROGRAM_TARGETS: u32 = 1024;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -100,6 +103,17 @@ pub fn push_gadget_generator(out: &mut Vec<gb_generator>, kind: u32, param: u32,
     for pair in targets.chunks(2) {
         out.push(gb_generator { kind: GB_GEN_TARGETS, gate: 0, a: pair[0] as u64, b: pair.get(1).map_or(0, |&t| t as u64) });
     }
+    head
+}
+
+/// One program generator (GB_GEN_PROGRAM): a head record - the index of its generator program (`set_generator_programs`), the
+/// number of targets and the row whose constants the program reads (0 for a program without constants) - and the continuation
+/// records: the program's `num_in` dependencies, then its `num_out` outputs, as `Target::index` values.  Returns the head's
+/// index, which is the record index the library's error messages name.
+pub fn push_program_generator(out: &mut Vec<gb_generator>, program: u32, row: usize, dependencies: &[usize], outputs: &[usize]) -> usize {
+    let targets: Vec<usize> = dependencies.iter().chain(outputs.iter()).copied().collect();
+    let head = push_gadget_generator(out, GB_GEN_PROGRAM, program, &targets);
+    out[head].b = row as u64;
     head
 }
 
@@ -187,6 +201,8 @@ extern "C" {
     fn gb_expand_partition(c: *mut gb_circuit, values: *const c_void, flags: u32, witness_dev_out: *mut c_void) -> i32;
     fn gb_circuit_set_generators(c: *mut gb_circuit, generators: *const c_void, num_generators: u64, input_targets: *const u64,
                                  num_inputs: u64, constants: *const u64, flags: u32) -> i32;
+    fn gb_circuit_set_generator_programs(c: *mut gb_circuit, program_words: *const u64, program_offsets: *const u32,
+                                         num_programs: u32) -> i32;
     fn gb_circuit_generators_info(c: *mut gb_circuit, num_levels: *mut u32, num_launches: *mut u32, num_unrunnable: *mut u32,
                                   num_checks: *mut u32, num_classes: *mut u32) -> i32;
     fn gb_circuit_generator_classes(c: *mut gb_circuit, class_targets_out: *mut u64, capacity: u64) -> i32;
@@ -1027,6 +1043,30 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
     pub unsafe fn expand_partition(&self, values: &[W], repr: Repr, witness_dev_out: *mut c_void) -> Result<(), GpuError> {
         Self::need_len("values", values.len(), self.num_targets.get(), "set_partition")?;
         check(self.ctx.0, gb_expand_partition(self.handle, values.as_ptr() as *const c_void, repr.flags(), witness_dev_out))
+    }
+    /// The circuit's generator programs (include/goldibear_gpu.h "GENERATOR PROGRAMS"): custom witness generators - a program
+    /// gate's `generators()`, a `SimpleGenerator` of `add_simple_generator` - as data, one slice of words per program.  After
+    /// `set_partition` and before `set_generators`, whose GB_GEN_PROGRAM records (`push_program_generator`) name them by index.
+    /// Calling it again replaces them and drops the schedule; an empty list clears them.
+    pub fn set_generator_programs(&self, programs: &[&[u64]]) -> Result<(), GpuError> {
+        let too_long = |what: &str| GpuError { status: GB_ERR_INVALID, message: format!("set_generator_programs: {what}") };
+        if programs.len() > GB_MAX_GENERATOR_PROGRAMS as usize {
+            return Err(too_long("more than GB_MAX_GENERATOR_PROGRAMS programs"));
+        }
+        let mut words: Vec<u64> = Vec::new();
+        let mut offsets: Vec<u32> = vec![0];
+        for p in programs {
+            words.extend(p.iter());
+            if words.len() > u32::MAX as usize {
+                return Err(too_long("the program table does not fit 32-bit offsets"));
+            }
+            offsets.push(words.len() as u32);
+        }
+        check(self.ctx.0, unsafe {
+            gb_circuit_set_generator_programs(self.handle, words.as_ptr(), offsets.as_ptr(), programs.len() as u32)
+        })?;
+        self.num_inputs.set(None);
+        Ok(())
     }
     /// `prover_only.generators` as records (see INTEGRATION.md "Generators as records"), the targets whose values the host supplies
     /// per proof - the `PartialWitness` and every `RandomValueGenerator` target - and the constants columns

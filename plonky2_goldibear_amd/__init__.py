@@ -14,3 +14,4 @@ from .prover import CircuitData, VerifierCircuitData  # noqa: F401
 from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
 from .fri import prove_openings, verify_fri_proof  # noqa: F401
 from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401
+from .generator_program import GeneratorProgram, ProgramGenerator, pack_generator_programs  # noqa: F401

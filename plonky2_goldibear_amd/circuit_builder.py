@@ -1120,6 +1120,20 @@ class CircuitBuilder:
                 programs.append(g.program)
             else:
                 params.append(g.param)
+        # the generator programs of the generators (generator_program.ProgramGenerator), the distinct ones numbered in the order of
+        # the generators; a program generator reads the constants of its row: the built circuit holds a copy bound to them
+        # (the generator object may serve other builders, or this one built again, and is left as it is)
+        generator_programs, seen = [], set()
+        for i, gen in enumerate(gens):
+            prog = getattr(gen, "generator_program", None)
+            if prog is None:
+                continue
+            if tuple(prog.words) not in seen:
+                seen.add(tuple(prog.words))
+                generator_programs.append(prog)
+            if gen.row is not None:
+                kc = [int(c) for c in self.gate_instances[gen.row][1]]
+                gens[i] = gen.bound_to((kc + [0] * prog.num_constants)[:prog.num_constants])
         gate_table = [(g.kind, params[i], selector_indices[i], groups[selector_indices[i]][0], groups[selector_indices[i]][1],
                        getattr(g, "param2", 0), getattr(g, "param3", 0)) for i, g in enumerate(gates)]
         return BuiltCircuit(ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, len(groups), max_constants, gens, find,
@@ -1127,7 +1141,7 @@ class CircuitBuilder:
                             sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None,
                             copy_targets=sorted({t for ab in self.copy_constraints for t in ab}),
                             num_virtual_targets=self.virtual_target_index,
-                            row_gates=[gates.index(g) for g, _ in self.gate_instances])
+                            row_gates=[gates.index(g) for g, _ in self.gate_instances], generator_programs=generator_programs)
 
     def _forest(self):
         """Disjoint sets over the targets that appear in copy constraints (plonk/permutation_argument.rs:13-101)."""
@@ -1198,7 +1212,8 @@ class BuiltCircuit:
     """CircuitData (plonk/circuit_data.rs:153-300) for a built circuit: prove(PartialWitness) / verify(proof)."""
 
     def __init__(self, ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, num_selectors, max_constants, generators, find,
-                 public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0, row_gates=()):
+                 public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0, row_gates=(),
+                 generator_programs=()):
         self.config, self.F, self.degree_bits, self.programs = cfg, F, degree_bits, programs
         self.constants_sigmas, self.k_is, self.gate_table, self.gate_ids = constants_sigmas, k_is, gate_table, gate_ids
         self.num_selectors, self.max_constants = num_selectors, max_constants
@@ -1209,6 +1224,8 @@ class BuiltCircuit:
         self.copy_targets, self.num_virtual_targets = copy_targets, num_virtual_targets
         self._representative_map, self._partition_set = None, False
         self.row_gates = row_gates          # per row: the index of its gate in gate_table (what a gb_generator record names)
+        self.generator_programs = list(generator_programs)   # what a GB_GEN_PROGRAM record names by index
+        self._generator_program_index = {tuple(pr.words): i for i, pr in enumerate(self.generator_programs)}
         self._inputs = None                 # set_generators: the targets whose values the host supplies per proof
         self._input_set = frozenset()
         self.data = None
@@ -1323,6 +1340,9 @@ class BuiltCircuit:
                 out.append(r)
         return out
 
+    def generator_program_index(self, program):
+        return self._generator_program_index[tuple(program.words)]
+
     @property
     def constants_columns(self):
         return self.constants_sigmas[self.num_selectors:self.num_selectors + self.max_constants]
@@ -1339,6 +1359,8 @@ class BuiltCircuit:
         if not self._partition_set:
             self.data.set_partition(self.representative_map, self.public_input_targets)
             self._partition_set = True
+        if self.generator_programs:
+            self.data.set_generator_programs(self.generator_programs)
         self.data.set_generators(self.generator_records(), [self.target_index(t) for t in input_targets], self.constants_columns)
         self._input_targets = list(input_targets)
 

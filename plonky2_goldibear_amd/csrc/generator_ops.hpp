@@ -45,12 +45,17 @@ enum Kind : uint32_t {
     GEN_BASE_SUM = 39,             // sum, limbs[1..]; parameter B
     GEN_TARGETS = 40,              // continuation
     GEN_GADGET_FIRST = GEN_EQUALITY,
-    GEN_GADGET_END = GEN_TARGETS   // one past the last head kind
+    GEN_GADGET_END = GEN_TARGETS,   // one past the last head kind of the built-in gadgets: 41 .. 47 are reserved and refused
+    // a generator program (below): a head record (gate = the program's index, a = the number of targets, b = the row whose
+    // constants the program reads) and its GEN_TARGETS records: the num_in dependencies, then the num_out outputs
+    GEN_PROGRAM = 48
 };
 
 constexpr uint32_t GROUP = 256;   // the chain kernel's workgroup: a level up to this wide stays inside a chain launch
 // the kinds generators.hpp evaluates (generator_schedule.hpp refuses the others): every gate generator, Copy and the gadget heads
-constexpr bool built_kind(uint32_t kind) { return kind < GEN_NUM_KINDS || (kind >= GEN_GADGET_FIRST && kind < GEN_GADGET_END); }
+constexpr bool built_kind(uint32_t kind) {
+    return kind < GEN_NUM_KINDS || (kind >= GEN_GADGET_FIRST && kind < GEN_GADGET_END) || kind == GEN_PROGRAM;
+}
 constexpr uint32_t OUT_CHECK = 0x80000000u, OUT_SKIP = 0xFFFFFFFFu, MAX_CLASSES = 0x7FFFFFFFu;
 
 struct Op {
@@ -60,7 +65,8 @@ struct Op {
     uint32_t num_in;
     uint32_t out_off;   // args[out_off .. out_off + num_out): output classes | OUT_CHECK, or OUT_SKIP
     uint32_t num_out;
-    uint32_t p0, p1;    // the gate's parameters as its evaluator reads them; a gadget generator's parameter is p0
+    uint32_t p0, p1;    // the gate's parameters as its evaluator reads them; a gadget generator's parameter is p0;
+                        // GEN_PROGRAM: p0 the program's index, p1 the first of its row's constants in the row-constants array
     uint64_t k[2];      // the row's constants, canonical words
 };
 
@@ -73,7 +79,10 @@ enum Error : uint32_t {
     ERR_SPLIT_TOO_LARGE = 4,   // BaseSplitGenerator: "Integer too large to fit in given number of limbs"; SplitGenerator and
                                // WireSplitGenerator: the reference's debug_assert_eq!(integer_value, 0, ..)
     ERR_DIVIDE_BY_ZERO = 5,    // QuotientGeneratorExtension: num / dem with dem == 0 ("Tried to invert zero")
-    ERR_NOT_BOOLEAN = 6        // BaseSumGenerator: get_bool_target, "not a bool"
+    ERR_NOT_BOOLEAN = 6,       // BaseSumGenerator: get_bool_target, "not a bool"
+    ERR_NO_SQUARE_ROOT = 7,    // a generator program's SQRT of a non-residue (examples/square_root.rs: sqrt(x).unwrap() on None)
+    ERR_NO_PROGRAM_TABLES = 8  // a GEN_PROGRAM op met by run_op without its `programs`: the caller's mistake.  Host builds report it;
+                               // for the kernels generator_schedule.hpp device_schedule() refuses such a schedule on the host
 };
 constexpr uint32_t ERROR_WORDS = 4;   // code, record, class, 0
 
@@ -83,9 +92,28 @@ struct Launch {
     uint32_t chain;
 };
 
+// Generator programs (include/goldibear_gpu.h, "generator programs"): a witness generator as a straight-line program in the
+// word layout of the constraint programs (gates.hpp run_program).  The opcode is (w & 3) | ((w >> 56) & 0xF) << 2: ADD, SUB and
+// MUL as there, OUT in EMIT's place, and the unary operations reg[dst] = op(a) above them.  generator_programs.hpp checks the
+// words; the decoded headers, the instruction words and the literals of all programs lie in three flat tables.
+enum ProgramOpcode : uint32_t {
+    GP_ADD = 0, GP_SUB = 1, GP_MUL = 2, GP_OUT = 3, GP_INV = 4, GP_INV_OR_ZERO = 5, GP_IS_ZERO = 6, GP_SQRT = 7, GP_NUM_OPCODES = 8
+};
+constexpr uint32_t MAX_GENERATOR_PROGRAMS = 256, MAX_PROGRAM_TARGETS = 1024;
+constexpr uint32_t gen_program_opcode(uint64_t w) { return ((uint32_t)w & 3) | (((uint32_t)(w >> 56) & 0xF) << 2); }
+struct ProgramHeader {
+    uint32_t num_in, num_constants, num_out, num_regs, num_literals, num_instrs;
+    uint32_t lit_off, instr_off;   // first literal / first instruction word in the flat tables
+};
+
 struct DeviceSchedule {   // the schedule's arrays on the device
     const Op* ops;
     const uint32_t *args, *level_off;
+    // with generator programs: their tables (literals in the field's device form, one per word), the row constants of the
+    // schedule's program generators (canonical) and the registers of the largest program among them (0: the schedule holds none)
+    const ProgramHeader* programs = nullptr;
+    const uint64_t *program_instrs = nullptr, *program_lits = nullptr, *row_constants = nullptr;
+    uint32_t program_regs = 0;
 };
 
 }  // namespace gen

@@ -25,9 +25,15 @@
 // runs past the array or meets another kind, a count or parameter that does not fit the kind, non-zero b, gate or padding, a
 // target out of range - answers INVALID with the record index; nothing is read past num_records.
 //
+// A generator program (GEN_PROGRAM, generator_programs.hpp) is one more generator of this shape: its head names the program (gate),
+// the number of targets (a = num_in + num_out of the program) and the row whose constants it reads (b; 0 for a program without
+// constants); the first num_in targets are its dependencies, the rest its outputs.  With wire targets it is the generator of a
+// program gate, with virtual targets a gadget's.  The schedule copies constants[j][row], j < num_constants, into row_constants;
+// the Op carries the program's index (p0) and the offset of its constants there (p1).
+//
 // Record kinds that are not built answer UNSUPPORTED: every kind outside built_kind() (generator_ops.hpp: what generators.hpp
-// evaluates; 17..31 are reserved), program gates, the lookup pair, the Poseidon2-Risc0 gate and DummyProofGenerator, none of
-// which has a record kind.
+// evaluates; 17..31 and 41..47 are reserved), a gate generator's record that names a program gate, the lookup pair, the
+// Poseidon2-Risc0 gate and DummyProofGenerator, none of which has a record kind.
 //
 // Host code without HIP dependencies: tests/sanitize/generator_schedule.cpp compiles it alone with the sanitizers.
 #ifndef GOLDIBEAR_GENERATOR_SCHEDULE_HPP
@@ -42,6 +48,7 @@
 #include <vector>
 
 #include "generator_ops.hpp"
+#include "generator_programs.hpp"
 
 namespace gbk {
 namespace gen {
@@ -75,6 +82,7 @@ struct CircuitDesc {
     const GateDesc* gates = nullptr;
     uint32_t num_gates = 0;
     const uint64_t* constants = nullptr;            // [num_constants][2^degree_bits] canonical words
+    const GeneratorPrograms* programs = nullptr;    // of gb_circuit_set_generator_programs; null: none set
 };
 
 struct Schedule {
@@ -88,7 +96,26 @@ struct Schedule {
     std::vector<uint32_t> args;
     std::vector<uint32_t> level_off;     // [num_levels + 1] into ops; entry l is level l + 1
     std::vector<Launch> launches;
+    std::vector<uint64_t> row_constants;   // the constants of the program generators' rows, canonical (Op::p1 points into it)
+    uint32_t program_regs = 0;             // the registers of the largest program a generator of the schedule runs; 0: none does
 };
+
+// The DeviceSchedule of a Schedule whose arrays lie on the device: how the launches' callers make one.  program_regs and the
+// program tables travel with the ops, never apart: the kernels of a schedule without programs (program_regs == 0) hold no code
+// for a program op and would leave its outputs zero without a word.  false, with a message: a program op without registers or
+// without one of the tables.
+inline bool device_schedule(const Schedule& s, const Op* ops, const uint32_t* args, const uint32_t* level_off, const ProgramHeader* programs,
+                            const uint64_t* program_instrs, const uint64_t* program_lits, const uint64_t* row_constants, DeviceSchedule* out,
+                            std::string* msg) {
+    for (const Op& op : s.ops)
+        if (op.kind == GEN_PROGRAM && (!s.program_regs || !programs || !program_instrs || !program_lits || !row_constants)) {
+            *msg = "generator record " + std::to_string(op.record) + ": a program generator in a schedule " +
+                   (s.program_regs ? "without the program tables" : "that asks for no program registers");
+            return false;
+        }
+    *out = DeviceSchedule{ops, args, level_off, programs, program_instrs, program_lits, row_constants, s.program_regs};
+    return true;
+}
 
 namespace detail {
 
@@ -257,6 +284,9 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
     gens.reserve(num_records);
     std::vector<uint32_t> args;   // targets first, classes after the translation below
     std::vector<uint32_t> dcols, ocols;
+    std::vector<uint64_t> s_row_constants;
+    uint32_t program_regs = 0;
+    bool any_program = false;
     for (size_t r = 0; r < num_records; r++) {
         const Record& rec = records[r];
         const std::string name = "generator record " + std::to_string(r);
@@ -268,7 +298,21 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
             const uint64_t count = rec.a, D = c.ext_degree;
             bool count_ok = false, param_ok = rec.gate == 0;
             uint64_t num_in = 1;
+            const ProgramHeader* prog = nullptr;
+            if (rec.kind == GEN_PROGRAM) {
+                if (!c.programs || c.programs->empty()) return refuse(SCHED_INVALID, name + ": no generator programs are set");
+                if (rec.gate >= c.programs->headers.size())
+                    return refuse(SCHED_INVALID, name + ": program index " + std::to_string(rec.gate) + " of " + std::to_string(c.programs->headers.size()));
+                prog = &c.programs->headers[rec.gate];
+                if (count != (uint64_t)prog->num_in + prog->num_out)
+                    return refuse(SCHED_INVALID, name + ": " + std::to_string(count) + " targets, the program has " + std::to_string(prog->num_in) +
+                                  " dependencies and " + std::to_string(prog->num_out) + " outputs");
+                if (prog->num_constants > c.num_constants) return refuse(SCHED_INVALID, name + ": the program reads more constants than the circuit has");
+                if (prog->num_constants ? rec.b >= n : rec.b != 0)
+                    return refuse(SCHED_INVALID, name + (prog->num_constants ? ": row out of range" : ": non-zero b for a program that reads no constants"));
+            }
             switch (rec.kind) {
+                case GEN_PROGRAM: count_ok = param_ok = true; num_in = prog->num_in; break;
                 case GEN_EQUALITY: count_ok = count == 4; num_in = 2; break;
                 case GEN_NONZERO_TEST: count_ok = count == 2; break;
                 case GEN_QUOTIENT_OR_ZERO: count_ok = count == 3; num_in = 2; break;
@@ -280,7 +324,7 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
             }
             if (!count_ok) return refuse(SCHED_INVALID, name + ": " + std::to_string(count) + " targets do not fit a generator of kind " + std::to_string(rec.kind));
             if (!param_ok) return refuse(SCHED_INVALID, name + ": parameter " + std::to_string(rec.gate) + " is out of range for kind " + std::to_string(rec.kind));
-            if (rec.b) return refuse(SCHED_INVALID, name + ": non-zero b in a head record");
+            if (rec.b && !prog) return refuse(SCHED_INVALID, name + ": non-zero b in a head record");
             const uint64_t cont = count / 2 + (count & 1);
             if (cont > num_records - r - 1) return refuse(SCHED_INVALID, name + ": the continuation records run past the end of the array");
             const size_t first = args.size();
@@ -302,6 +346,17 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
             g.num_out = (uint32_t)(count - num_in);
             g.out_off = g.in_off + g.num_in;
             g.p0 = rec.gate;
+            if (prog) {
+                if (s_row_constants.size() >> 31) return refuse(SCHED_UNSUPPORTED, "2^31 row constants of program generators or more");
+                g.p1 = (uint32_t)s_row_constants.size();
+                for (uint32_t j = 0; j < prog->num_constants; j++) {
+                    const uint64_t k = c.constants[(uint64_t)j * n + rec.b];
+                    if (k >= c.order) return refuse(SCHED_INVALID, name + ": non-canonical constant");
+                    s_row_constants.push_back(k);
+                }
+                program_regs = std::max(program_regs, prog->num_regs);
+                any_program = true;
+            }
             r += cont;
         } else if (rec.kind == GEN_COPY) {
             if (rec.a >= NT || rec.b >= NT) return refuse(SCHED_INVALID, name + ": target out of range");
@@ -427,6 +482,7 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
 
     struct Entry {
         uint32_t level, kind, gen, deferred;
+        uint32_t program;   // of a program generator: a wave runs one program where the level allows it
     };
     std::vector<Entry> entries;
     std::vector<uint32_t> glevel(G, NONE), frontier, next, newly;
@@ -458,8 +514,9 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
                     now = true;
                 }
             }
-            if (now || !g.num_out) entries.push_back(Entry{level, g.kind, gi, 0});
-            if (later) entries.push_back(Entry{level + 1, g.kind, gi, 1});
+            const uint32_t program = g.kind == GEN_PROGRAM ? g.p0 : 0;
+            if (now || !g.num_out) entries.push_back(Entry{level, g.kind, gi, 0, program});
+            if (later) entries.push_back(Entry{level + 1, g.kind, gi, 1, program});
             max_level = std::max(max_level, later ? level + 1 : level);
         }
         next.clear();
@@ -473,7 +530,7 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
 
     // ---- the ops, level by level and kind by kind
     std::stable_sort(entries.begin(), entries.end(), [](const Entry& x, const Entry& y) {
-        return x.level != y.level ? x.level < y.level : x.kind < y.kind;
+        return x.level != y.level ? x.level < y.level : x.kind != y.kind ? x.kind < y.kind : x.program < y.program;
     });
     s.ops.reserve(entries.size());
     s.level_off.assign((size_t)max_level + 1, 0);
@@ -505,6 +562,8 @@ inline ScheduleStatus build_schedule(const CircuitDesc& c, const Record* records
         s.level_off[max_level] = run;
     }
     s.args = std::move(args);
+    s.row_constants = std::move(s_row_constants);
+    s.program_regs = any_program ? std::max(program_regs, 1u) : 0;
 
     // ---- launches
     for (uint32_t l = 0; l < max_level;) {

@@ -22,6 +22,8 @@
 // Depends on the field headers and gates.hpp only (and the plain words of generator_ops.hpp): tests/device/generators.hip and
 // tests/host_shim/generators.cpp include it on their own.
 #pragma once
+#include <type_traits>
+
 #include "gates.hpp"
 #include "generator_ops.hpp"
 
@@ -347,11 +349,108 @@ GB_HD void gen_base_sum(const Io<F>& io) {   // limbs -> sum, folded from the la
     io.out(0, acc);
 }
 
+// ---- generator programs (generator_ops.hpp; include/goldibear_gpu.h gives the words)
+// sqrt as examples/square_root.rs:185-219 writes it - Euler's criterion, then Tonelli-Shanks with z = two_adic_generator(S),
+// S the field's two-adicity - on device-form values.  The root is the one these steps yield; false: x is no residue.  Every loop
+// is bounded by S: v falls in every round, and a residue's b reaches one within v squarings.
 template <class F>
-GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err) {
+GB_HD bool field_sqrt(typename F::T x, typename F::T* root) {
+    typedef typename F::T T;
+    constexpr u32 S = F::TWO_ADICITY;
+    constexpr u64 t = (F::ORDER - 1) >> S;
+    *root = x;
+    if (x == F::zero()) return true;
+    if (F::pow(x, (F::ORDER - 1) / 2) != F::one()) return false;
+    T z = F::two_adic_generator(S), w = F::pow(x, (t - 1) / 2);
+    T r = F::mul(w, x), b = F::mul(r, w);
+    u32 v = S;
+    for (u32 round = 0; round < S && b != F::one(); round++) {
+        u32 k = 0;
+        for (T b2k = b; k < v && b2k != F::one(); k++) b2k = F::mul(b2k, b2k);
+        if (k >= v) return false;   // (not reached for a residue)
+        w = z;
+        for (u32 i = 0; i + k + 1 < v; i++) w = F::mul(w, w);
+        z = F::mul(w, w);
+        b = F::mul(b, z);
+        r = F::mul(r, w);
+        v = k;
+    }
+    *root = r;
+    return true;
+}
+
+// what run_op needs to run a program generator: the tables of DeviceSchedule and this lane's register file (gates::LdsRegs on the
+// device, gates::ArrayRegs on the host).  NoPrograms: a schedule without program generators - a GEN_PROGRAM op there is the
+// caller's mistake.  Host code reports ERR_NO_PROGRAM_TABLES; the kernels without programs hold no code for it, and
+// generator_schedule.hpp device_schedule refuses on the host to hand them a schedule with such an op.
+struct NoPrograms {};
+template <class R>
+struct Programs {
+    const ProgramHeader* headers;
+    const uint64_t *instrs, *lits, *row_constants;
+    R regs;
+};
+
+// the interpreter: the operand decode of gates::run_program; space 1 is the dependencies, space 2 the row's constants, OUT ends in
+// io.put, so store-or-compare and OUT_SKIP are those of every other generator.  An error ends the program: its outputs stay as
+// they are and the error word ends the proof.  (A program's error names no class: OUT_SKIP in the class word.)
+template <class F, class R>
+GB_HD void gen_program(const Io<F>& io, const Programs<R>& pr) {
+    typedef typename F::T T;
+    const ProgramHeader& h = pr.headers[io.op.p0];
+    const uint64_t* ins = pr.instrs + h.instr_off;
+    const uint64_t* lits = pr.lits + h.lit_off;
+    const uint64_t* konst = pr.row_constants + io.op.p1;
+    auto load = [&](u32 o) -> T {
+        const u32 i = gates::prog_index(o);
+        switch (gates::prog_space(o)) {
+            case gates::PROG_REG: return pr.regs.get(i);
+            case gates::PROG_WIRE: return io.in(i);
+            case gates::PROG_CONST: return F::enc(konst[i]);
+            default: return (T)lits[i];
+        }
+    };
+    u32 next_out = 0;
+    for (u32 pc = 0; pc < h.num_instrs; pc++) {
+        const u64 w = ins[pc];
+        const T a = load(gates::prog_operand(w, 0));
+        T res = a;
+        switch (gen_program_opcode(w)) {
+            case GP_ADD: res = F::add(a, load(gates::prog_operand(w, 1))); break;
+            case GP_SUB: res = F::sub(a, load(gates::prog_operand(w, 1))); break;
+            case GP_MUL: res = F::mul(a, load(gates::prog_operand(w, 1))); break;
+            case GP_OUT: io.out(next_out++, a); continue;
+            case GP_INV:
+                if (a == F::zero()) {
+                    report(io.err, ERR_DIVIDE_BY_ZERO, io.op.record, OUT_SKIP);
+                    return;
+                }
+                res = F::inv(a);
+                break;
+            case GP_INV_OR_ZERO: res = F::inv(a); break;   // pow(0, p - 2) = 0
+            case GP_IS_ZERO: res = a == F::zero() ? F::one() : F::zero(); break;
+            default:   // GP_SQRT
+                if (!field_sqrt<F>(a, &res)) {
+                    report(io.err, ERR_NO_SQUARE_ROOT, io.op.record, OUT_SKIP);
+                    return;
+                }
+                break;
+        }
+        pr.regs.set(gates::prog_dst(w), res);
+    }
+}
+
+template <class F, class P = NoPrograms>
+GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err, const P& programs = P()) {
     typedef typename F::T T;
     const Io<F> io{op, args, values, err};
     switch (op.kind) {
+        case GEN_PROGRAM:
+            if constexpr (!std::is_same<P, NoPrograms>::value) gen_program<F>(io, programs);
+#if !defined(__HIP_DEVICE_COMPILE__)
+            else report(err, ERR_NO_PROGRAM_TABLES, op.record, OUT_SKIP);
+#endif
+            break;
         case GEN_ARITHMETIC:
             io.out(0, F::add(F::mul(F::mul(io.in(0), io.in(1)), F::enc(op.k[0])), F::mul(io.in(2), F::enc(op.k[1]))));
             break;
@@ -397,24 +496,46 @@ GB_HD void run_op(const Op& op, const u32* args, typename F::T* values, u32* err
 }
 
 #if defined(__HIPCC__)
+// The program tables as a kernel argument.  PROGRAMS = false is the kernel of a schedule without program generators: no LDS, and
+// no code for GEN_PROGRAM (the host keeps such an op away from it, generator_schedule.hpp device_schedule: a report here costs the
+// chain kernels registers, 180 -> 184 and 125 -> 127 VGPRs).  PROGRAMS = true: a program's registers are indexed at run time, so they live in dynamic LDS
+// and not in a per-lane array (which would go to scratch), [program_regs][GROUP] words, a register's row lane-consecutive, as in
+// k_gate_programs; a lane only ever touches its own words, so the chain kernel's barrier has nothing to do with them.
+struct ProgramTables {
+    const ProgramHeader* headers = nullptr;
+    const uint64_t *instrs = nullptr, *lits = nullptr, *row_constants = nullptr;
+};
+template <class F, bool PROGRAMS>
+__device__ __forceinline__ void run_scheduled_op(const Op& op, const u32* args, typename F::T* values, u32* err, const ProgramTables& pt) {
+    if constexpr (PROGRAMS) {
+        typedef typename F::T T;
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem_generator_regs[];
+        const Programs<gates::LdsRegs<T>> pr{pt.headers, pt.instrs, pt.lits, pt.row_constants,
+                                             gates::LdsRegs<T>{reinterpret_cast<T*>(smem_generator_regs) + threadIdx.x, GROUP}};
+        run_op<F>(op, args, values, err, pr);
+    } else {
+        run_op<F>(op, args, values, err);
+    }
+}
+
 // one thread per generator of a level
-template <class F>
+template <class F, bool PROGRAMS = false>
 __global__ __launch_bounds__(GROUP) void k_generate_level(const Op* __restrict__ ops, const u32* __restrict__ args, u32 first, u32 count,
-                                                          typename F::T* values, u32* err) {
+                                                          typename F::T* values, u32* err, ProgramTables pt = ProgramTables()) {
     const u32 i = blockIdx.x * GROUP + threadIdx.x;
-    if (i < count) run_op<F>(ops[first + i], args, values, err);
+    if (i < count) run_scheduled_op<F, PROGRAMS>(ops[first + i], args, values, err, pt);
 }
 
 // ONE workgroup walks levels first_level .. first_level + num_levels of level_off, each at most GROUP wide, with a barrier
 // between levels: __syncthreads() is a workgroup-scope release, the barrier and a workgroup-scope acquire, which is all a
 // hand-off inside one workgroup - one CU, one vector L1 - needs.  Nothing is handed to another workgroup.
-template <class F>
+template <class F, bool PROGRAMS = false>
 __global__ __launch_bounds__(GROUP) void k_generate_chain(const Op* __restrict__ ops, const u32* __restrict__ args,
                                                           const u32* __restrict__ level_off, u32 first_level, u32 num_levels,
-                                                          typename F::T* values, u32* err) {
+                                                          typename F::T* values, u32* err, ProgramTables pt = ProgramTables()) {
     for (u32 l = 0; l < num_levels; l++) {
         const u32 lo = level_off[first_level + l], hi = level_off[first_level + l + 1];
-        for (u32 i = lo + threadIdx.x; i < hi; i += GROUP) run_op<F>(ops[i], args, values, err);
+        for (u32 i = lo + threadIdx.x; i < hi; i += GROUP) run_scheduled_op<F, PROGRAMS>(ops[i], args, values, err, pt);
         __syncthreads();
     }
 }
@@ -436,21 +557,30 @@ __global__ __launch_bounds__(GROUP) void k_gather_public(const u32* __restrict__
     if (i < ERROR_WORDS) out[count + i] = err[i];
 }
 
-// the launches of one generation pass on `stream`; `values` holds the inputs, everything else zero; err is zero
-template <class F>
-inline void launch_generators(const DeviceSchedule& d, const Launch* launches, size_t num_launches, const u32* level_off_host,
-                              typename F::T* values, u32* err, hipStream_t stream) {
+// the launches of one generation pass on `stream`; `values` holds the inputs, everything else zero; err is zero.  A schedule
+// without program generators (d.program_regs == 0) launches the kernels without programs and no LDS.
+template <class F, bool PROGRAMS>
+inline void launch_generators_as(const DeviceSchedule& d, const Launch* launches, size_t num_launches, const u32* level_off_host,
+                                 typename F::T* values, u32* err, hipStream_t stream) {
+    const size_t lds = PROGRAMS ? (size_t)d.program_regs * GROUP * sizeof(typename F::T) : 0;
+    const ProgramTables pt{d.programs, d.program_instrs, d.program_lits, d.row_constants};
     for (size_t k = 0; k < num_launches; k++) {
         const Launch& L = launches[k];
         if (L.chain) {
-            hipLaunchKernelGGL(k_generate_chain<F>, dim3(1), dim3(GROUP), 0, stream, d.ops, d.args, d.level_off, L.first_level, L.num_levels,
-                               values, err);
+            hipLaunchKernelGGL((k_generate_chain<F, PROGRAMS>), dim3(1), dim3(GROUP), lds, stream, d.ops, d.args, d.level_off, L.first_level,
+                               L.num_levels, values, err, pt);
         } else {
             const u32 first = level_off_host[L.first_level], count = level_off_host[L.first_level + 1] - first;
-            hipLaunchKernelGGL(k_generate_level<F>, dim3((count + GROUP - 1) / GROUP), dim3(GROUP), 0, stream, d.ops, d.args, first, count,
-                               values, err);
+            hipLaunchKernelGGL((k_generate_level<F, PROGRAMS>), dim3((count + GROUP - 1) / GROUP), dim3(GROUP), lds, stream, d.ops, d.args, first,
+                               count, values, err, pt);
         }
     }
+}
+template <class F>
+inline void launch_generators(const DeviceSchedule& d, const Launch* launches, size_t num_launches, const u32* level_off_host,
+                              typename F::T* values, u32* err, hipStream_t stream) {
+    if (d.program_regs) launch_generators_as<F, true>(d, launches, num_launches, level_off_host, values, err, stream);
+    else launch_generators_as<F, false>(d, launches, num_launches, level_off_host, values, err, stream);
 }
 #endif
 

@@ -64,16 +64,31 @@ struct gb_circuit {
         gbk::gen::Schedule sched;
         gbk::gen::Op* ops_dev = nullptr;
         uint32_t *args_dev = nullptr, *level_off_dev = nullptr, *input_cls_dev = nullptr, *pi_cls_dev = nullptr, *err_dev = nullptr;
+        uint64_t* row_constants_dev = nullptr;   // the constants of the program generators' rows (Schedule::row_constants)
+        gbk::gen::DeviceSchedule device{nullptr, nullptr, nullptr};   // of device_schedule(): the arrays above and the program tables
         std::vector<std::pair<uint64_t, uint32_t>> input_index;   // (target, index into input_targets), ascending
         std::vector<uint8_t> input_fast;    // the input may be re-drawn inside a kept matrix (gb_prove_inputs_retry)
         std::vector<uint64_t> kept_pis;     // the public inputs of the attempt that left part.matrix == kept_for behind
         const void* kept_for = nullptr;
     } gens;
+    // gb_circuit_set_generator_programs: the checked programs on the host (the schedule reads the headers) and their tables on the
+    // device, literals in the field's device form.  A schedule is built on them: replacing them drops it.
+    struct GeneratorPrograms {
+        gbk::gen::GeneratorPrograms host;
+        gbk::gen::ProgramHeader* headers_dev = nullptr;
+        uint64_t *instrs_dev = nullptr, *lits_dev = nullptr;
+    } gen_programs;
     void drop_generators() {   // (the caller has waited for the stream)
         for (void* p : {(void*)gens.ops_dev, (void*)gens.args_dev, (void*)gens.level_off_dev, (void*)gens.input_cls_dev, (void*)gens.pi_cls_dev,
-                        (void*)gens.err_dev})
+                        (void*)gens.err_dev, (void*)gens.row_constants_dev})
             if (p) (void)hipFree(p);
         gens = Generators{};
+    }
+    void drop_generator_programs() {   // (the caller has waited for the stream)
+        drop_generators();
+        for (void* p : {(void*)gen_programs.headers_dev, (void*)gen_programs.instrs_dev, (void*)gen_programs.lits_dev})
+            if (p) (void)hipFree(p);
+        gen_programs = GeneratorPrograms{};
     }
     void drop_retry() {
         if (retry.wires) gb_batch_free(retry.wires);
@@ -86,7 +101,7 @@ struct gb_circuit {
         gens.kept_for = nullptr;
     }
     void drop_partition() {   // (the caller has waited for the stream)
-        drop_generators();
+        drop_generator_programs();
         if (part.slots_dev) (void)hipFree(part.slots_dev);
         if (part.staged_host) (void)hipHostFree(part.staged_host);
         if (part.staged_read) (void)hipEventDestroy(part.staged_read);
@@ -1937,8 +1952,7 @@ static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_
         }
         gbk::scatter_inputs<F>(g.input_cls_dev, in_dev, (u32)ni, values_dev, st);
     }
-    const GN::DeviceSchedule ds{g.ops_dev, g.args_dev, g.level_off_dev};
-    gbk::run_generators<F>(ds, sc.launches.data(), sc.launches.size(), sc.level_off.data(), values_dev, g.err_dev, st);
+    gbk::run_generators<F>(g.device, sc.launches.data(), sc.launches.size(), sc.level_off.data(), values_dev, g.err_dev, st);
     u64* back_dev = tmp.get<u64>(npi + GN::ERROR_WORDS);
     if (!back_dev) return fail(ctx, GB_ERR_OOM, "generator read-back");
     gbk::gather_public<F>(g.pi_cls_dev, (u32)npi, values_dev, g.err_dev, back_dev, st);
@@ -1963,9 +1977,14 @@ static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_
             case GN::ERR_SPLIT_TOO_LARGE:
                 return fail(ctx, GB_ERR_INVALID, rec + "Integer too large to fit in given number of limbs");
             case GN::ERR_DIVIDE_BY_ZERO:
+                if (cls >= sc.class_reps.size()) return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (INV in a generator program)");
                 return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (the denominator at target " + target + ")");
+            case GN::ERR_NO_SQUARE_ROOT:
+                return fail(ctx, GB_ERR_INVALID, rec + "SQRT of a non-residue in a generator program (called `Option::unwrap()` on a `None` value)");
             case GN::ERR_NOT_BOOLEAN:
                 return fail(ctx, GB_ERR_INVALID, rec + "not a bool (target " + target + ")");
+            case GN::ERR_NO_PROGRAM_TABLES:   // the schedule always sets program_regs with a program generator: not reachable from the ABI
+                return fail(ctx, GB_ERR_HIP, rec + "a program generator was run without the program tables");
             default:
                 return fail(ctx, GB_ERR_HIP, rec + "unknown generator error word");
         }
@@ -2437,6 +2456,44 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
                                      : abi_expand_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, witness_dev_out);
 } GB_CATCH_CIRCUIT(c)
 
+// ---- generator programs: witness generators as data (generator_programs.hpp checks them, generators.hpp gen_program runs them)
+gb_status gb_circuit_set_generator_programs(gb_circuit* c, const uint64_t* program_words, const uint32_t* program_offsets,
+                                            uint32_t num_programs) try {
+    namespace GN = gbk::gen;
+    if (gb_status s = stage_guard(c)) return s;
+    gb_ctx* ctx = c->ctx;
+    if (!c->part.set)
+        return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generator_programs: gb_circuit_set_partition has not been called on this circuit");
+    GN::GeneratorPrograms parsed;
+    std::string msg;
+    const uint64_t order = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::ORDER : (uint64_t)BbF::ORDER;
+    if (!GN::parse_generator_programs(program_words, program_offsets, num_programs, order, c->cfg.num_constants, &parsed, &msg))
+        return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generator_programs: " + msg);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    c->drop_retry();
+    c->drop_generator_programs();   // and the schedule built on the old ones
+    if (parsed.empty()) return GB_OK;
+    std::vector<uint64_t> lits(parsed.lits.size());   // device form, once
+    for (size_t i = 0; i < lits.size(); i++)
+        lits[i] = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::enc(parsed.lits[i]) : (uint64_t)BbF::enc(parsed.lits[i]);
+    auto upload = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
+        hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
+        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    gb_circuit::GeneratorPrograms& gp = c->gen_programs;
+    void* p = nullptr;
+    HIP_TRY(ctx, upload(parsed.headers.data(), parsed.headers.size() * sizeof(GN::ProgramHeader), &p));
+    gp.headers_dev = static_cast<GN::ProgramHeader*>(p);
+    HIP_TRY(ctx, upload(parsed.instrs.data(), parsed.instrs.size() * sizeof(uint64_t), &p));
+    gp.instrs_dev = static_cast<uint64_t*>(p);
+    HIP_TRY(ctx, upload(lits.data(), lits.size() * sizeof(uint64_t), &p));
+    gp.lits_dev = static_cast<uint64_t*>(p);
+    gp.host = std::move(parsed);
+    return GB_OK;
+} GB_CATCH_CIRCUIT(c)
+
 // ---- the witness generators (templates above: generate_stage, prove_inputs)
 // replaces the host's generate_partial_witness (plonk/prover.rs:136-158, iop/generator.rs:25-106): the generators as data, scheduled once
 gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
@@ -2468,6 +2525,7 @@ gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint6
     d.gates = gates.data();
     d.num_gates = (uint32_t)gates.size();
     d.constants = constants;
+    d.programs = &c->gen_programs.host;
     GN::Schedule sched;
     std::string msg;
     if (const int ss = GN::build_schedule(d, static_cast<const GN::Record*>(generators), num_generators, input_targets, num_inputs, GN::GROUP, &sched,
@@ -2513,6 +2571,14 @@ gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint6
     g.pi_cls_dev = static_cast<uint32_t*>(p);
     HIP_TRY(ctx, upload(nullptr, 0, &p));
     g.err_dev = static_cast<uint32_t*>(p);
+    HIP_TRY(ctx, upload(sched.row_constants.data(), sched.row_constants.size() * sizeof(uint64_t), &p));
+    g.row_constants_dev = static_cast<uint64_t*>(p);
+    if (!GN::device_schedule(sched, g.ops_dev, g.args_dev, g.level_off_dev, c->gen_programs.headers_dev, c->gen_programs.instrs_dev,
+                             c->gen_programs.lits_dev, g.row_constants_dev, &g.device, &msg)) {
+        c->drop_generators();
+        return fail(ctx, GB_ERR_HIP, msg);
+    }
+    std::vector<uint64_t>().swap(sched.row_constants);
     // the kernels read ops and args from the device; the host keeps what it launches and reports with
     std::vector<GN::Op>().swap(sched.ops);
     std::vector<uint32_t>().swap(sched.args);

@@ -95,6 +95,7 @@ SIGNATURES = {
     "gb_prove_partition_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, C.POINTER(_sz)]),
     "gb_expand_partition": (_i32, [_vp, _vp, _u32, _vp]),
     "gb_circuit_set_generators": (_i32, [_vp, _vp, _u64, C.POINTER(_u64), _u64, C.POINTER(_u64), _u32]),
+    "gb_circuit_set_generator_programs": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u32), _u32]),
     "gb_circuit_generators_info": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gb_circuit_generator_classes": (_i32, [_vp, C.POINTER(_u64), _u64]),
     "gb_generate_partition": (_i32, [_vp, _vp, _u32, _vp]),
@@ -117,6 +118,8 @@ SIGNATURES = {
 # the gadget generators: a head record (kind, parameter, number of targets, 0) and GB_GEN_TARGETS continuation records
 (GB_GEN_EQUALITY, GB_GEN_NONZERO_TEST, GB_GEN_QUOTIENT_OR_ZERO, GB_GEN_QUOTIENT_EXTENSION, GB_GEN_SPLIT, GB_GEN_WIRE_SPLIT,
  GB_GEN_LOW_HIGH, GB_GEN_BASE_SUM, GB_GEN_TARGETS) = range(32, 41)
+# a generator program's head: (kind, program index, number of targets, the row of its constants), then GB_GEN_TARGETS records
+GB_GEN_PROGRAM = 48
 
 
 def gadget_records(kind, param, targets):

@@ -342,6 +342,15 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
                                                     k.ctypes.data_as(u64p) if k.size else None, 0), self.ctx.handle)
         self.num_inputs = int(t.size)
 
+    def set_generator_programs(self, programs):
+        """the circuit's generator programs (generator_program.GeneratorProgram or lists of words), which the GB_GEN_PROGRAM
+        records of set_generators name by index; after set_partition and before set_generators.  An empty list clears them."""
+        from .generator_program import pack_generator_programs
+        words, offsets = pack_generator_programs(programs)
+        N.check(self._lib.gb_circuit_set_generator_programs(self.handle, words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                            offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(offsets) - 1),
+                self.ctx.handle)
+
     def generators_info(self):
         """-> dict(num_levels, num_launches, num_unrunnable, num_checks, num_classes) of the schedule"""
         names = ("num_levels", "num_launches", "num_unrunnable", "num_checks", "num_classes")

@@ -17,6 +17,9 @@ Circuits: a range-check circuit - range_check(x, 32) on a fresh input per check,
 at 2^12 and 2^14 rows, both fields (--only-range-checks stops there); tests/circuits.py recursion_gates_circuit (both fields),
 factorial_circuit, and a wide arithmetic circuit - 20 independent multiply-adds per row - at 2^12, 2^14 and 2^16 rows.
 --bench-parent: bench.py on this tree and on a tree of the parent commit (built), alternated, each run a fresh process; the tree
+--only-generator-programs: the wide arithmetic circuit of either field at 2^12 and 2^14 rows twice - as it is (compiled
+generators, GB_GEN_ARITHMETIC records) and with its ArithmeticGate as a program gate whose generators are generator programs
+(tests/generator_program_circuits.py; GB_GEN_PROGRAM records, interpreted) - and the ratio of the two "run generators" scopes.
 that goes first alternates from round to round.  --bench-control TREE2 puts a second copy of the parent's tree in this tree's place:
 what the comparison says about two identical trees.
 """
@@ -45,13 +48,17 @@ def append(out, lines):
         f.write(text)
 
 
-def wide_arithmetic_circuit(log_rows):
-    """every row an ArithmeticGate with 20 independent operations x * y + z_i on inputs: one level, as wide as it gets"""
-    from plonky2_goldibear_amd.circuit_builder import CircuitBuilder, CircuitConfig, PartialWitness
+def wide_arithmetic_circuit(log_rows, field=None):
+    """every row an ArithmeticGate with 20 (BabyBear: the narrow configuration's) independent operations x * y + z_i on inputs:
+    one level, as wide as it gets"""
+    from plonky2_goldibear_amd import native as N
+    from plonky2_goldibear_amd.circuit_builder import ArithmeticGate, CircuitBuilder, CircuitConfig, PartialWitness
     # ((64 - degree_bits) * num_challenges >= 100, circuit_builder.rs:1190-1192)
-    b = CircuitBuilder(CircuitConfig.standard_recursion_config_gl(num_challenges=3 if log_rows >= 15 else 2))
+    cfg = CircuitConfig.recursion_config_bb_narrow() if field == N.GB_BABYBEAR else \
+        CircuitConfig.standard_recursion_config_gl(num_challenges=3 if log_rows >= 15 else 2)
+    b = CircuitBuilder(cfg)
     pw = PartialWitness()
-    ops = ((1 << log_rows) - 8) * 20
+    ops = ((1 << log_rows) - 8) * ArithmeticGate.new_from_config(cfg).num_ops
     x, y = b.add_virtual_targets(2)
     pw.set_target(x, 1000003)
     pw.set_target(y, 998244353)
@@ -79,7 +86,7 @@ def range_check_circuit(field, log_rows):
     return b, pw
 
 
-def measure(ctx, name, b, pw, reps, out, chain=False):
+def measure(ctx, name, b, pw, reps, out, chain=False, mirror_reps=3):
     c = b.build(ctx)
     c.set_generators(pw=pw)
     info = c.data.generators_info()
@@ -106,7 +113,7 @@ def measure(ctx, name, b, pw, reps, out, chain=False):
             call()
             wall[k].append((time.perf_counter() - t0) * 1e3)
     mirror = []
-    for _ in range(min(reps, 3)):
+    for _ in range(min(reps, mirror_reps)):
         t0 = time.perf_counter()
         c._run_generators(pw, rng())
         mirror.append((time.perf_counter() - t0) * 1e3)
@@ -130,6 +137,7 @@ def measure(ctx, name, b, pw, reps, out, chain=False):
     append(out, lines)
     data.free()
     ctx.trim()
+    return gen
 
 
 def bench_parent(parent, rounds, steps, out, this=ROOT, label="this commit", extra=()):
@@ -165,6 +173,9 @@ def main():
     ap.add_argument("--wide-log-rows", type=int, nargs="*", default=[12, 14, 16])
     ap.add_argument("--range-check-log-rows", type=int, nargs="*", default=[12, 14])
     ap.add_argument("--only-range-checks", action="store_true", help="the range-check circuits alone")
+    ap.add_argument("--only-generator-programs", action="store_true",
+                    help="the wide arithmetic circuit with compiled generators and with generator programs, both fields")
+    ap.add_argument("--program-log-rows", type=int, nargs="*", default=[12, 14])
     ap.add_argument("--bench-parent", metavar="TREE")
     ap.add_argument("--bench-control", metavar="TREE", help="with --bench-parent: compare TREE, a second copy of the parent, instead of this tree")
     ap.add_argument("--rounds", type=int, default=3)
@@ -185,6 +196,20 @@ def main():
     from plonky2_goldibear_amd import GpuContext, native as N
     ctx = GpuContext(0)
     append(a.out, ["# tools/witness_generation_times.py, csrc %s, %s: times in ms" % (csrc_sha16(), time.strftime("%Y-%m-%d"))])
+    if a.only_generator_programs:
+        import generator_program_circuits as GPC
+        for lg in a.program_log_rows:
+            for field, fname in ((N.GB_GOLDILOCKS, "goldilocks"), (N.GB_BABYBEAR, "babybear")):
+                b, pw = wide_arithmetic_circuit(lg, field)
+                compiled = measure(ctx, "wide arithmetic circuit, compiled generators (%s)" % fname, b, pw, a.reps, a.out, mirror_reps=1)
+                b, pw = wide_arithmetic_circuit(lg, field)
+                GPC.with_generated_program_gates(b)
+                interpreted = measure(ctx, "wide arithmetic circuit, program gates with generator programs (%s)" % fname, b, pw, a.reps, a.out,
+                                      mirror_reps=1)
+                append(a.out, ["  interpreted / compiled generators, \"run generators\" at 2^%d rows (%s): %.3f / %.3f ms = %.2fx" % (
+                    lg, fname, interpreted, compiled, interpreted / compiled)])
+        ctx.close()
+        return 0
     for lg in a.range_check_log_rows:
         for field, fname in ((N.GB_GOLDILOCKS, "goldilocks"), (N.GB_BABYBEAR, "babybear")):
             b, pw = range_check_circuit(field, lg)
