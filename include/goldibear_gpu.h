@@ -73,7 +73,8 @@ const char* gb_last_error(const gb_ctx* ctx); /* valid until the next call on ct
 gb_status gb_ctx_synchronize(gb_ctx* ctx);
 /* Freed batches keep their device blocks in a per-context pool for reuse by later commits of the
  * same shape (the reference allocates fresh Vecs per PolynomialBatch); this returns them to HIP - together with what failed
- * attempts keep for gb_prove_retry, the work buffers of transforms above 2^22 rows and the page-locked staging ring of pageable
+ * attempts keep for gb_prove_retry, what the first gb_check_witness prepared on each circuit (the next check builds it again),
+ * the work buffers of transforms above 2^22 rows and the page-locked staging ring of pageable
  * inputs (four slots of max(64 MiB, one column): 256 MiB of host memory up to 2^23 Goldilocks rows, 512 MiB at 2^24; its copy
  * threads). */
 gb_status gb_ctx_trim(gb_ctx* ctx);
@@ -83,7 +84,9 @@ gb_status gb_ctx_stream(gb_ctx* ctx, void** stream_out);
  *   "copy_threads"   threads of the context that stage PAGEABLE host columns into the library's page-locked ring (below):
  *                    default 4; 0 = the calling thread copies; -1 = no ring, hipMemcpyAsync straight from pageable memory
  *   "retry_verify"   1: gb_prove_retry first compares the caller's whole matrix with the copy the failed attempt kept and
- *                    returns GB_ERR_INVALID if they differ in more than witness[wire][row] (one read-back of the witness) */
+ *                    returns GB_ERR_INVALID if they differ in more than witness[wire][row] (one read-back of the witness)
+ *   "check_witness"  1: every gb_prove* that does the full computation checks its witness first (gb_check_witness, below) and
+ *                    returns GB_ERR_UNSATISFIED instead of proof bytes that cannot verify; default 0: gb_prove* runs nothing new */
 gb_status gb_ctx_set_option(gb_ctx* ctx, const char* key, int64_t value);
 
 /* ---- host memory ---------------------------------------------------------------------------
@@ -583,6 +586,67 @@ gb_status gb_prove_inputs(gb_circuit* c, const void* input_values, uint32_t flag
  * computation. */
 gb_status gb_prove_inputs_retry(gb_circuit* c, const void* input_values, uint32_t flags, uint32_t wire, uint64_t row,
                                 void* proof_out, size_t proof_cap, size_t* proof_len);
+
+/* ---- does this witness satisfy this circuit, and if not, where does it fail? ------------------------------------------------
+ * gb_prove* on a witness that breaks a gate or a copy constraint returns GB_OK and bytes that gb_verify rejects with
+ * "vanishing(zeta) != Z_H(zeta) * quotient(zeta)": the reference's only guard, the trim_to_len of plonk/prover.rs:367 ("Quotient
+ * has failed, the vanishing polynomial is not divisible by Z_H"), is vacuous where quotient_degree_factor is
+ * max_quotient_degree_factor and a power of two, as in every configuration served here.  The check evaluates the constraints of
+ * plonk/vanishing_poly.rs on H itself, where they must vanish, on the device (csrc/kernels_check.hip), and names what fails:
+ *   gate violation      row r, gate g (an index into the gate table), constraint i: g is ACTIVE on r - compute_filter
+ *                       (gates/gate.rs:391-404) of its selector column's value is non-zero - and constraint i of its
+ *                       eval_unfiltered is the first that is not zero there.  PublicInputGate is evaluated against the hash of
+ *                       the public inputs handed in, computed as gb_prove computes it; NoopGate has no constraints.
+ *   selector violation  a selector value that is neither a gate index of its column's group nor UNUSED_SELECTOR (with a single
+ *                       selector column, whose filters have no UNUSED factor: nor that): the circuit data is broken, not the
+ *                       witness.  No gate is evaluated for that column on that row.
+ *   copy violation      on a circuit with a partition (gb_circuit_set_partition): a wire cell whose value differs from the value
+ *                       of the FIRST cell of its class - the lowest row * num_wires + column.  The slot map defines the classes;
+ *                       sigma is not decoded, and without a partition copies are not checked (copies_checked = 0).
+ * A circuit made by plain gb_circuit_create is checked as the gate table {Noop, ConstantGate, PublicInputGate} it stands for: the
+ * gate index is the selector value.  The first check on a circuit transforms its selector and constant columns to values on H
+ * (the LDE the circuit keeps holds the coset g H, not H) and builds a row list per gate; that stays with the circuit until
+ * gb_circuit_free / gb_ctx_trim.  Timing scopes: "check witness: prepare", "check witness", and inside the latter one per launch -
+ * "check witness: gate kind K" (K = GB_GATE_*), "check witness: copies", "check witness: canonical words". */
+#define GB_ERR_UNSATISFIED 20
+#define GB_VIOLATION_GATE 1
+#define GB_VIOLATION_SELECTOR 2
+#define GB_VIOLATION_COPY 3
+typedef struct gb_violation {   /* 48 bytes */
+    uint32_t kind;         /* GB_VIOLATION_* */
+    uint32_t gate;         /* GATE: index in the gate table */
+    uint64_t row;          /* COPY: the cell's row */
+    uint32_t index;        /* GATE: first failing constraint, eval_unfiltered order; SELECTOR: selector column; COPY: the cell's wire */
+    uint32_t other_wire;   /* COPY: wire of the class's first cell */
+    uint64_t other_row;    /* COPY: its row */
+    uint64_t value;        /* GATE: that constraint's unfiltered value; SELECTOR: the selector value; COPY: the cell's value (canonical) */
+    uint64_t other_value;  /* COPY: the first cell's value */
+} gb_violation;
+typedef struct gb_check_result {
+    uint64_t num_gate_violations;     /* entries (row, gate) with a failing constraint, all of them, not just the listed */
+    uint64_t num_selector_violations;
+    uint64_t num_copy_violations;
+    uint32_t copies_checked;          /* 0: no partition set */
+    uint32_t num_listed;
+} gb_check_result;
+/* witness: [num_wires][2^degree_bits] canonical values, accepted as gb_prove accepts its witness (GB_INPUT_HOST / GB_INPUT_DEVICE /
+ * GB_INPUT_P3_REPR for a host's words; with GB_INPUT_DEVICE it is what gb_expand_partition wrote) - and an element that is not
+ * below p is GB_ERR_INVALID ("non-canonical witness element").  violations_out: gb_violation[capacity], or NULL with capacity 0;
+ * result: a gb_check_result, may be NULL (both travel as void* like the generator records of gb_circuit_set_generators).
+ * GB_OK: no violation.  GB_ERR_UNSATISFIED: at least one; gb_last_error names the first (kind, row, gate index, constraint),
+ * violations_out holds the first min(capacity, total) in this order - selector violations by (row, column), gate violations by
+ * (row, gate), copy violations by cell index - and the counts in `result` are exact whatever the capacity.  A check keeps no retry
+ * state, and for gb_prove_retry it is another call in between: what a failed attempt left on the circuit is released, and a retry
+ * after a check is the full computation. */
+gb_status gb_check_witness(gb_circuit* c, const void* witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs,
+                           void* violations_out, size_t capacity, void* result);
+/* what gb_prove_partition / gb_prove_inputs run up to the device matrix - the expansion, or the generators and the expansion, with
+ * the same errors, the public inputs read from the values as those functions read them - then the check */
+gb_status gb_check_partition(gb_circuit* c, const void* values, uint32_t flags, void* violations_out, size_t capacity, void* result);
+gb_status gb_check_inputs(gb_circuit* c, const void* input_values, uint32_t flags, void* violations_out, size_t capacity, void* result);
+/* gb_ctx_set_option "check_witness" (default 0): 1 = every gb_prove*, gb_prove_partition* and gb_prove_inputs* that does the full
+ * computation runs the check on its witness before the wires commitment and returns GB_ERR_UNSATISFIED instead of bytes that
+ * cannot verify.  The incremental retry paths are not re-checked: only the random wire changed, and no gate constrains it. */
 
 /* verify() of a proof produced for this circuit (plonk/verifier.rs:17-128, fri/verifier.rs:67-250,
  * plonk/get_challenges.rs:26-101), restated for the dummy gate set and run on the HOST like the reference's verifier: the

@@ -22,6 +22,10 @@ pub const GB_OK: i32 = 0;
 pub const GB_ERR_INVALID: i32 = 1;
 pub const GB_ERR_PERM_ARG_ZERO: i32 = 16;
 pub const GB_ERR_VERIFY: i32 = 19;
+pub const GB_ERR_UNSATISFIED: i32 = 20;
+pub const GB_VIOLATION_GATE: u32 = 1;
+pub const GB_VIOLATION_SELECTOR: u32 = 2;
+pub const GB_VIOLATION_COPY: u32 = 3;
 pub const GB_GOLDILOCKS: u32 = 0;
 pub const GB_BABYBEAR: u32 = 1;
 pub const GB_INPUT_HOST: u32 = 0;
@@ -140,6 +144,45 @@ pub struct gb_gate {
     pub param3: u32,
 }
 
+/// One entry of the witness check's list (include/goldibear_gpu.h: gb_violation).  `kind` is GB_VIOLATION_GATE (gate, row,
+/// index = first failing constraint, value), GB_VIOLATION_SELECTOR (row, index = selector column, value) or GB_VIOLATION_COPY
+/// (row, index = wire, value; other_row, other_wire, other_value: the first cell of the class).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gb_violation {
+    pub kind: u32,
+    pub gate: u32,
+    pub row: u64,
+    pub index: u32,
+    pub other_wire: u32,
+    pub other_row: u64,
+    pub value: u64,
+    pub other_value: u64,
+}
+
+/// The counts of a witness check (include/goldibear_gpu.h: gb_check_result): exact whatever the list's capacity.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gb_check_result {
+    pub num_gate_violations: u64,
+    pub num_selector_violations: u64,
+    pub num_copy_violations: u64,
+    pub copies_checked: u32,
+    pub num_listed: u32,
+}
+
+/// What a witness check found: the first `max_violations` violations in the header's order, and the counts.
+#[derive(Clone, Debug, Default)]
+pub struct CheckOutcome {
+    pub violations: Vec<gb_violation>,
+    pub result: gb_check_result,
+}
+impl CheckOutcome {
+    pub fn satisfied(&self) -> bool {
+        self.result.num_gate_violations + self.result.num_selector_violations + self.result.num_copy_violations == 0
+    }
+}
+
 /// Challenger<F, H> by value (iop/challenger.rs:18-31) for `gb_prove_openings`: canonical values as u64 for either field;
 /// challenges pop from the END of `output_buffer`.
 #[repr(C)]
@@ -211,6 +254,12 @@ extern "C" {
                        proof_cap: usize, proof_len: *mut usize) -> i32;
     fn gb_prove_inputs_retry(c: *mut gb_circuit, input_values: *const c_void, flags: u32, wire: u32, row: u64, proof_out: *mut c_void,
                              proof_cap: usize, proof_len: *mut usize) -> i32;
+    fn gb_check_witness(c: *mut gb_circuit, witness: *const c_void, flags: u32, public_inputs: *const u64, num_public_inputs: usize,
+                        violations_out: *mut c_void, capacity: usize, result: *mut c_void) -> i32;
+    fn gb_check_partition(c: *mut gb_circuit, values: *const c_void, flags: u32, violations_out: *mut c_void, capacity: usize,
+                          result: *mut c_void) -> i32;
+    fn gb_check_inputs(c: *mut gb_circuit, input_values: *const c_void, flags: u32, violations_out: *mut c_void, capacity: usize,
+                       result: *mut c_void) -> i32;
     fn gb_commit_values(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
                         cap_height: u32, salts: *const c_void, flags: u32, out: *mut *mut gb_batch) -> i32;
     fn gb_commit_coeffs(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
@@ -1129,6 +1178,50 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
                                   buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
         };
         self.finish_proof(st, buf, len)
+    }
+    /// GB_OK and GB_ERR_UNSATISFIED both carry a result; anything else is an error.
+    fn finish_check(&self, st: i32, mut violations: Vec<gb_violation>, result: gb_check_result) -> Result<CheckOutcome, GpuError> {
+        if st != GB_OK && st != GB_ERR_UNSATISFIED {
+            check(self.ctx.0, st)?;
+        }
+        violations.truncate(result.num_listed as usize);
+        Ok(CheckOutcome { violations, result })
+    }
+    /// Does this witness (`[num_wires][degree]`, as `prove` takes it) satisfy the circuit?  Every active gate's constraints on
+    /// every row and, on a circuit with a partition, the copy constraints; at most `max_violations` are listed.
+    pub fn check_witness(&self, witness: &[W], public_inputs: &[u64], max_violations: usize, repr: Repr) -> Result<CheckOutcome, GpuError> {
+        let c = &self.config;
+        need("witness", witness.len(), (c.num_wires as usize) << c.degree_bits)?;
+        need("public_inputs", public_inputs.len(), c.num_public_inputs as usize)?;
+        let mut out = vec![gb_violation::default(); max_violations.max(1)];
+        let mut res = gb_check_result::default();
+        let st = unsafe {
+            gb_check_witness(self.handle, witness.as_ptr() as *const c_void, repr.flags(), public_inputs.as_ptr(), public_inputs.len(),
+                             out.as_mut_ptr() as *mut c_void, max_violations, &mut res as *mut gb_check_result as *mut c_void)
+        };
+        self.finish_check(st, out, res)
+    }
+    /// The same from `PartitionWitness.values` (after `set_partition`): `prove_partition`'s expansion, then the check.
+    pub fn check_partition(&self, values: &[W], max_violations: usize, repr: Repr) -> Result<CheckOutcome, GpuError> {
+        Self::need_len("values", values.len(), self.num_targets.get(), "set_partition")?;
+        let mut out = vec![gb_violation::default(); max_violations.max(1)];
+        let mut res = gb_check_result::default();
+        let st = unsafe {
+            gb_check_partition(self.handle, values.as_ptr() as *const c_void, repr.flags(), out.as_mut_ptr() as *mut c_void, max_violations,
+                               &mut res as *mut gb_check_result as *mut c_void)
+        };
+        self.finish_check(st, out, res)
+    }
+    /// The same from the inputs (after `set_generators`): the generators and the expansion on the device, then the check.
+    pub fn check_inputs(&self, input_values: &[W], max_violations: usize, repr: Repr) -> Result<CheckOutcome, GpuError> {
+        Self::need_len("input_values", input_values.len(), self.num_inputs.get(), "set_generators")?;
+        let mut out = vec![gb_violation::default(); max_violations.max(1)];
+        let mut res = gb_check_result::default();
+        let st = unsafe {
+            gb_check_inputs(self.handle, input_values.as_ptr() as *const c_void, repr.flags(), out.as_mut_ptr() as *mut c_void, max_violations,
+                            &mut res as *mut gb_check_result as *mut c_void)
+        };
+        self.finish_check(st, out, res)
     }
     /// Give up after `PermArgZero` (`ProverError::TooManyPermArgFailures`, prover.rs:221-225): releases what the failed attempt
     /// left on the device for `prove_retry` (~12 GB at 2^20 Goldilocks rows).  No-op when nothing is held.

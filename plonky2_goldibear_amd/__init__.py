@@ -8,6 +8,7 @@ polynomial  the transforms on their own: fft / ifft / coset_fft / coset_ifft / l
 """
 from .native import GB_BABYBEAR, GB_GOLDILOCKS, GoldibearError, ShapeError  # noqa: F401
 from .native import PermArgZeroError, TooManyPermArgFailuresError, VerifyError  # noqa: F401
+from .native import UnsatisfiedError, Violation  # noqa: F401
 from .polynomial_batch import GpuContext, MerkleTree, PolynomialBatch  # noqa: F401
 from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  # noqa: F401
 from .prover import CircuitData, VerifierCircuitData  # noqa: F401

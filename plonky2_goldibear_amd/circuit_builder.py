@@ -1420,6 +1420,24 @@ class BuiltCircuit:
         data.drop_retry()
         raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
 
+    # ---- does the witness these generators make satisfy the circuit?  (include/goldibear_gpu.h gb_check_partition / gb_check_inputs)
+    def check(self, pw, rng=None, max_violations=16):
+        """the host generators as in prove(), the expansion and the check on the device -> (violations, result); the violations
+        are native.Violation objects (describe(self) names the gate), an empty list means satisfied"""
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        if not self._partition_set:
+            self.data.set_partition(self.representative_map, self.public_input_targets)
+            self._partition_set = True
+        return self.data.check_partition(self.generate_partition_witness(pw, rng), max_violations=max_violations)
+
+    def check_inputs(self, pw, rng=None, max_violations=16):
+        """the device generators as in prove_inputs(), then the check: what a generator program that disagrees with its gate
+        program breaks, by row, gate and constraint"""
+        if self._input_targets is None:
+            self.set_generators(pw=pw)
+        return self.data.check_inputs(self.input_values(pw, rng), max_violations=max_violations)
+
     @property
     def _input_targets(self):
         return self._inputs

@@ -100,8 +100,10 @@ struct gb_ctx {
     // gb_ctx_set_option
     int copy_threads = 4;                                   // "copy_threads": -1 = no staging ring (hipMemcpyAsync straight from pageable memory)
     bool retry_verify = false;                              // "retry_verify": gb_prove_retry compares the whole matrix with the kept copy
+    bool check_witness = false;                             // "check_witness": gb_prove* check their device witness before the wires commitment
 };
 static void drop_all_retry_state(gb_ctx* ctx);              // prover_host.inc
+static void drop_all_check_state(gb_ctx* ctx);              // prover_host.inc: what gb_check_witness keeps with the circuits
 
 struct gb_batch {
     gb_ctx* ctx = nullptr;
@@ -1167,6 +1169,7 @@ gb_status gb_ctx_trim(gb_ctx* ctx) try {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     drop_all_retry_state(ctx);
+    drop_all_check_state(ctx);
     for (auto& kv : ctx->pool) (void)hipFree(kv.second);
     ctx->pool.clear();
     for (DeviceBuf& wb : ctx->big_work) {   // the coset tables hold these fields' addresses; the next lookup grows them again
@@ -1318,6 +1321,8 @@ gb_status gb_ctx_set_option(gb_ctx* ctx, const char* key, int64_t value) try {
         ctx->copy_threads = (int)value;
     } else if (k == "retry_verify") {
         ctx->retry_verify = value != 0;
+    } else if (k == "check_witness") {
+        ctx->check_witness = value != 0;
     } else {
         return fail(ctx, GB_ERR_INVALID, "unknown option: " + k);
     }

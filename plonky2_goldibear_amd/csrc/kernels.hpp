@@ -240,6 +240,12 @@ struct ProgramParams {
     const u64* instrs;            // instruction words of all programs (ProgramInfo::instr_off)
     const typename F::T* lits;    // literals of all programs, device form (ProgramInfo::lit_off)
 };
+// the witness check (kernels_check.hip): the gate set and the number of rows; no challenges, nothing is folded
+template <class F>
+struct CheckParams {
+    gates::GateSet gs;
+    u32 n;
+};
 template <class F>
 struct PolyGroups {
     const typename F::T* ptr[4];
@@ -265,6 +271,37 @@ bool quotient_shape_supported(u32 field, u32 chunk, u32 num_challenges);
 template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs = nullptr);
+// ---- the witness check (kernels_check.hip's launchers; witness_check.hpp has the row logic).  hv: the selector and constant
+// columns as values on H, [num_selectors + num_constants][n], natural order, device form; wit: [num_wires][n] canonical words.
+// counts[MAX_LISTS] and offsets[MAX_LISTS + 1]: rows per list (a list per gate, then the rows with a selector violation) and
+// their exclusive scan
+template <class F>
+void check_count_rows(const gates::GateSet& gs, const typename F::T* hv, u32 n, u32* counts, u32* offsets, hipStream_t st);
+// rows[offsets[l] .. offsets[l + 1]): the rows of list l, ascending
+template <class F>
+void check_fill_rows(const gates::GateSet& gs, const typename F::T* hv, u32 n, const u32* offsets, u32* rows, hipStream_t st);
+// out[i][col]: the canonical selector values of row rows[i]
+template <class F>
+void check_selector_values(const typename F::T* hv, u32 n, u32 num_selectors, const u32* rows, u32 count, u64* out, hipStream_t st);
+// gate g on the `count` rows of its list: fail_index[i] = the first constraint of row rows[i] that is not zero (or 0xFFFFFFFF),
+// fail_value[i] its canonical value, *num_failed += the entries that have one.  pi_hash: device form
+template <class F>
+void check_gate_rows(const CheckParams<F>& p, u32 g, const ProgramParams<F>* programs, const u32* rows, u32 count, const typename F::T* hv,
+                     const typename F::T* wit, const typename F::T* pi_hash, u32* fail_index, u64* fail_value, u32* num_failed, hipStream_t st);
+// first[slot] = the lowest cell row * num_wires + column of the slot's class (slots: the map of gb_circuit_set_partition)
+void check_first_cells(const u32* slots, u64 cells, u32 num_slots, u32* first, hipStream_t st);
+// bit c of mask (64 cells per word) = cell c differs from the first cell of its class; *num_failed += those
+template <class F>
+void check_copies(const u32* slots, const u32* first, u32 num_slots, const typename F::T* wit, u32 n, u32 num_wires, u64* mask,
+                  u32* num_failed, hipStream_t st);
+// out[i] = {value of cells[i], the first cell of its class, that cell's value}
+template <class F>
+void check_copy_report(const u32* slots, const u32* first, u32 num_slots, const typename F::T* wit, u32 n, u32 num_wires, const u32* cells,
+                       u32 count, u64* out, hipStream_t st);
+// *flag |= 1 if a word of v is not below p
+template <class F>
+void check_canonical(const typename F::T* v, size_t count, u32* flag, hipStream_t st);
+
 // l0[j] = Z_H(x_j) / (n (x_j - 1)), zh = device copy of the 2^rate_bits values of Z_H on the cosets
 template <class F>
 void l0_table(u32 log_n, u32 rate_bits, const PowTab<F>& w_N, const typename F::T* zh, typename F::T* l0, hipStream_t st);

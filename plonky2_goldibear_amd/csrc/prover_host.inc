@@ -78,6 +78,27 @@ struct gb_circuit {
         gbk::gen::ProgramHeader* headers_dev = nullptr;
         uint64_t *instrs_dev = nullptr, *lits_dev = nullptr;
     } gen_programs;
+    // gb_check_witness (check_host.inc): what the first check on the circuit builds and later ones reuse - the selector and constant
+    // columns as values on H, the row list of every gate - and, per partition, the first cell of every copy class.  Released by
+    // gb_circuit_free and gb_ctx_trim; the first cells also when gb_circuit_set_partition replaces the map.
+    struct Check {
+        bool ready = false;
+        void* hvals = nullptr;               // [num_selectors + num_constants][n], natural order, device form
+        uint32_t* lists_dev = nullptr;       // counts [MAX_LISTS], then offsets [MAX_LISTS + 1]
+        uint32_t* rows = nullptr;            // the lists, one behind the other
+        std::vector<uint32_t> counts, offsets;   // host copies: [num_gates + 1], [num_gates + 2]
+        uint32_t* first_cell = nullptr;      // [number of slots]
+    } chk;
+    void drop_check_copies() {   // (the caller has waited for the stream)
+        if (chk.first_cell) (void)hipFree(chk.first_cell);
+        chk.first_cell = nullptr;
+    }
+    void drop_check() {          // (the caller has waited for the stream)
+        drop_check_copies();
+        for (void* p : {chk.hvals, (void*)chk.lists_dev, (void*)chk.rows})
+            if (p) (void)hipFree(p);
+        chk = Check{};
+    }
     void drop_generators() {   // (the caller has waited for the stream)
         for (void* p : {(void*)gens.ops_dev, (void*)gens.args_dev, (void*)gens.level_off_dev, (void*)gens.input_cls_dev, (void*)gens.pi_cls_dev,
                         (void*)gens.err_dev, (void*)gens.row_constants_dev})
@@ -102,6 +123,7 @@ struct gb_circuit {
     }
     void drop_partition() {   // (the caller has waited for the stream)
         drop_generator_programs();
+        drop_check_copies();
         if (part.slots_dev) (void)hipFree(part.slots_dev);
         if (part.staged_host) (void)hipHostFree(part.staged_host);
         if (part.staged_read) (void)hipEventDestroy(part.staged_read);
@@ -266,6 +288,9 @@ static gb_status need_arity_list(gb_circuit* c) {
 }
 static void drop_all_retry_state(gb_ctx* ctx) {
     for (gb_circuit* c : ctx->circuits) c->drop_retry();
+}
+static void drop_all_check_state(gb_ctx* ctx) {   // gb_ctx_trim (the caller has waited for the stream)
+    for (gb_circuit* c : ctx->circuits) c->drop_check();
 }
 // the catch-all of the entry points that take a circuit: what an interrupted attempt may have kept for gb_prove_retry goes too
 static gb_status unwound_circuit(gb_circuit* c, const char* fn) noexcept {
@@ -1050,6 +1075,9 @@ struct RetryHint {   // gb_prove_retry: the one wire that differs from the witne
     uint32_t wire;
     uint64_t row;
 };
+// option "check_witness" (check_host.inc): GB_ERR_UNSATISFIED where the witness breaks a gate or a copy constraint
+template <class F>
+gb_status check_before_commit(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs);
 template <class F>
 gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs,
                 const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
@@ -1203,6 +1231,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         }
     } else {
         c->drop_retry();
+        if (ctx->check_witness && (s = check_before_commit<F>(c, witness, flags, public_inputs, num_public_inputs))) return s;
         if (!(flags & GB_INPUT_DEVICE) && lg >= 12) {
             void* p = nullptr;
             if (pool_alloc(ctx, wit_bytes, &p) != hipSuccess) return fail(ctx, GB_ERR_OOM, "witness staging");
@@ -2246,6 +2275,7 @@ gb_status gb_circuit_free(gb_circuit* c) try {
     }
     c->drop_retry();
     c->drop_partition();
+    c->drop_check();
     c->release();
     delete c;
     return GB_OK;
@@ -2711,3 +2741,5 @@ gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t 
 } GB_CATCH(ctx)
 
 }  // extern "C"
+
+#include "check_host.inc"

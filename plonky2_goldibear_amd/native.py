@@ -17,6 +17,8 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 GB_OK, GB_ERR_INVALID, GB_ERR_HIP, GB_ERR_OOM, GB_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 GB_ERR_PERM_ARG_ZERO, GB_ERR_OPENING_IN_SUBGROUP, GB_ERR_BUFFER_TOO_SMALL, GB_ERR_VERIFY = 16, 17, 18, 19
+GB_ERR_UNSATISFIED = 20   # gb_check_*, and gb_prove* under the option "check_witness": the witness does not satisfy the circuit
+GB_VIOLATION_GATE, GB_VIOLATION_SELECTOR, GB_VIOLATION_COPY = 1, 2, 3
 GB_GOLDILOCKS, GB_BABYBEAR = 0, 1
 GB_INPUT_HOST, GB_INPUT_DEVICE = 0, 1
 GB_INPUT_P3_REPR = 2   # host elements are the reference's field types as they lie in memory (p3 words), not canonical values
@@ -101,6 +103,9 @@ SIGNATURES = {
     "gb_generate_partition": (_i32, [_vp, _vp, _u32, _vp]),
     "gb_prove_inputs": (_i32, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_inputs_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, C.POINTER(_sz)]),
+    "gb_check_witness": (_i32, [_vp, _vp, _u32, C.POINTER(_u64), _sz, _vp, _sz, _vp]),
+    "gb_check_partition": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp]),
+    "gb_check_inputs": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp]),
     "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
     "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
     "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
@@ -183,10 +188,87 @@ class ShapeError(GoldibearError, ValueError):
     """GB_ERR_INVALID: where the reference would assert!/panic! on a shape violation."""
 
 
+# ---- the witness check (include/goldibear_gpu.h: gb_check_witness, gb_check_partition, gb_check_inputs)
+class gb_violation(C.Structure):
+    _fields_ = [("kind", _u32), ("gate", _u32), ("row", _u64), ("index", _u32), ("other_wire", _u32), ("other_row", _u64),
+                ("value", _u64), ("other_value", _u64)]
+
+
+class gb_check_result(C.Structure):
+    _fields_ = [("num_gate_violations", _u64), ("num_selector_violations", _u64), ("num_copy_violations", _u64),
+                ("copies_checked", _u32), ("num_listed", _u32)]
+
+
+class Violation:
+    """one gb_violation: kind (GB_VIOLATION_*) and the fields that kind uses (the others are zero)"""
+    FIELDS = tuple(name for name, _ in gb_violation._fields_)
+    __slots__ = FIELDS
+
+    def __init__(self, kind, gate=0, row=0, index=0, other_wire=0, other_row=0, value=0, other_value=0):
+        for name, v in zip(self.FIELDS, (kind, gate, row, index, other_wire, other_row, value, other_value)):
+            setattr(self, name, int(v))
+
+    @classmethod
+    def from_struct(cls, s):
+        return cls(*[getattr(s, name) for name in cls.FIELDS])
+
+    def as_tuple(self):
+        return tuple(getattr(self, name) for name in self.FIELDS)
+
+    def __eq__(self, other):
+        return isinstance(other, Violation) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def __repr__(self):
+        return "Violation(%s)" % ", ".join("%s=%d" % (name, getattr(self, name)) for name in self.FIELDS)
+
+    def describe(self, built=None):
+        """one line: the gate's id string from built.gate_ids (circuit_builder.BuiltCircuit; without it the gate's index), the row
+        and the constraint; a copy violation prints both cells"""
+        if self.kind == GB_VIOLATION_GATE:
+            ids = getattr(built, "gate_ids", None)
+            name = ids[self.gate] if ids is not None and self.gate < len(ids) else "gate %d" % self.gate
+            return "row %d: %s, constraint %d = %d" % (self.row, name, self.index, self.value)
+        if self.kind == GB_VIOLATION_SELECTOR:
+            return "row %d: selector column %d holds %d, which names no gate of its group" % (self.row, self.index, self.value)
+        return "row %d, wire %d = %d differs from the first cell of its copy class, row %d, wire %d = %d" % (
+            self.row, self.index, self.value, self.other_row, self.other_wire, self.other_value)
+
+
+def _parse_first_violation(message):
+    """the violation gb_last_error names after GB_ERR_UNSATISFIED (csrc/check_host.inc describe_violation)"""
+    import re
+    m = re.search(r"gate violation at row (\d+): gate (\d+), constraint (\d+) = (\d+)", message)
+    if m:
+        row, gate, index, value = map(int, m.groups())
+        return [Violation(GB_VIOLATION_GATE, gate=gate, row=row, index=index, value=value)]
+    m = re.search(r"selector violation at row (\d+): selector column (\d+) holds (\d+)", message)
+    if m:
+        row, col, value = map(int, m.groups())
+        return [Violation(GB_VIOLATION_SELECTOR, row=row, index=col, value=value)]
+    m = re.search(r"copy violation at row (\d+), wire (\d+) = (\d+): the first cell of its class \(row (\d+), wire (\d+)\) holds (\d+)", message)
+    if m:
+        row, w, value, orow, ow, ovalue = map(int, m.groups())
+        return [Violation(GB_VIOLATION_COPY, row=row, index=w, other_wire=ow, other_row=orow, value=value, other_value=ovalue)]
+    return []
+
+
+class UnsatisfiedError(GoldibearError):
+    """GB_ERR_UNSATISFIED: the witness breaks a gate, a selector or a copy constraint.  `violations`: what the call listed - from
+    gb_prove* under the option "check_witness" the first one, read off the message."""
+
+    def __init__(self, status, message, violations=None):
+        super().__init__(status, message)
+        self.violations = list(violations) if violations is not None else _parse_first_violation(message)
+
+
 def check(status, ctx_handle=None):
     if status == GB_OK:
         return
     msg = load().gb_last_error(ctx_handle)
     msg = msg.decode() if msg else ""
-    cls = {GB_ERR_INVALID: ShapeError, GB_ERR_PERM_ARG_ZERO: PermArgZeroError, GB_ERR_VERIFY: VerifyError}.get(status, GoldibearError)
+    cls = {GB_ERR_INVALID: ShapeError, GB_ERR_PERM_ARG_ZERO: PermArgZeroError, GB_ERR_VERIFY: VerifyError,
+           GB_ERR_UNSATISFIED: UnsatisfiedError}.get(status, GoldibearError)
     raise cls(status, msg)

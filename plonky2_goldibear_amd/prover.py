@@ -402,6 +402,46 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         N.check(st, self.ctx.handle)
         return self._proof_buf[: n.value].tobytes()
 
+    # ---- does the witness satisfy the circuit?  (include/goldibear_gpu.h: gb_check_witness, gb_check_partition, gb_check_inputs)
+    def _check_call(self, call, max_violations):
+        """-> (violations, result): the listed violations as native.Violation objects (an empty list: satisfied) and the counts"""
+        cap = int(max_violations)
+        out = (N.gb_violation * max(1, cap))()
+        res = N.gb_check_result()
+        st = call(C.cast(out, C.c_void_p) if cap else None, cap, C.cast(C.pointer(res), C.c_void_p))
+        if st not in (N.GB_OK, N.GB_ERR_UNSATISFIED):
+            N.check(st, self.ctx.handle)
+        return [N.Violation.from_struct(out[i]) for i in range(res.num_listed)], res
+
+    def check_witness(self, witness, public_inputs=(), max_violations=16, p3_repr=False):
+        """evaluate every active gate's constraints on the rows of `witness` ([num_wires][n], host or device as for prove) and, on
+        a circuit with a partition, the copy constraints: -> (violations, result), at most max_violations listed - selector
+        violations by (row, column), gate violations by (row, gate), copy violations by cell - the counts of `result` exact"""
+        ptr, shape, flags, keep = _as_input(witness, self.field)
+        if p3_repr:
+            flags |= N.GB_INPUT_P3_REPR
+        want = (self.cfg.num_wires, 1 << self.cfg.degree_bits)
+        if tuple(shape) != want:
+            raise N.ShapeError(N.GB_ERR_INVALID, "witness must be %r, got %r" % (want, tuple(shape)))
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        pis_ptr = pis.ctypes.data_as(C.POINTER(C.c_uint64)) if pis.size else None
+        got = self._check_call(lambda out, cap, res: self._lib.gb_check_witness(self.handle, ptr, flags, pis_ptr, pis.size, out, cap, res),
+                               max_violations)
+        del keep
+        return got
+
+    def check_partition(self, values, max_violations=16, p3_repr=False):
+        """the same from PartitionWitness.values: the expansion of prove_partition, then the check"""
+        v, flags = self._partition_values(values, p3_repr)
+        return self._check_call(lambda out, cap, res: self._lib.gb_check_partition(self.handle, v.ctypes.data, flags, out, cap, res),
+                                max_violations)
+
+    def check_inputs(self, input_values, max_violations=16, p3_repr=False):
+        """the same from the inputs: the generators and the expansion of prove_inputs on the device, then the check"""
+        v, flags = self._input_values(input_values, p3_repr)
+        vp = v.ctypes.data if v.size else None
+        return self._check_call(lambda out, cap, res: self._lib.gb_check_inputs(self.handle, vp, flags, out, cap, res), max_violations)
+
     @property
     def constants_sigmas_commitment(self):
         """ProverOnlyCircuitData.constants_sigmas_commitment (plonk/circuit_data.rs:532-534): a PolynomialBatch view that the
