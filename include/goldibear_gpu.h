@@ -600,9 +600,12 @@ gb_status gb_prove_inputs_retry(gb_circuit* c, const void* input_values, uint32_
  *   selector violation  a selector value that is neither a gate index of its column's group nor UNUSED_SELECTOR (with a single
  *                       selector column, whose filters have no UNUSED factor: nor that): the circuit data is broken, not the
  *                       witness.  No gate is evaluated for that column on that row.
- *   copy violation      on a circuit with a partition (gb_circuit_set_partition): a wire cell whose value differs from the value
- *                       of the FIRST cell of its class - the lowest row * num_wires + column.  The slot map defines the classes;
- *                       sigma is not decoded, and without a partition copies are not checked (copies_checked = 0).
+ *   copy violation      a wire cell whose value differs from the value of the FIRST cell of its class - the lowest
+ *                       row * num_wires + column.  On a circuit with a partition (gb_circuit_set_partition) the slot map defines
+ *                       the classes (copies_checked = 1); without one, the cycles of the permutation that
+ *                       gb_circuit_decode_sigmas (below) has read out of the sigma columns (copies_checked = 2); with neither,
+ *                       copies are not checked (copies_checked = 0) - the check never decodes sigma by itself.  Not checked
+ *                       either way: lookups, and the Z / partial-product columns, which the prover computes itself.
  * A circuit made by plain gb_circuit_create is checked as the gate table {Noop, ConstantGate, PublicInputGate} it stands for: the
  * gate index is the selector value.  The first check on a circuit transforms its selector and constant columns to values on H
  * (the LDE the circuit keeps holds the coset g H, not H) and builds a row list per gate; that stays with the circuit until
@@ -626,7 +629,7 @@ typedef struct gb_check_result {
     uint64_t num_gate_violations;     /* entries (row, gate) with a failing constraint, all of them, not just the listed */
     uint64_t num_selector_violations;
     uint64_t num_copy_violations;
-    uint32_t copies_checked;          /* 0: no partition set */
+    uint32_t copies_checked;          /* 0: not checked, 1: the partition's classes, 2: the classes decoded from sigma */
     uint32_t num_listed;
 } gb_check_result;
 /* witness: [num_wires][2^degree_bits] canonical values, accepted as gb_prove accepts its witness (GB_INPUT_HOST / GB_INPUT_DEVICE /
@@ -647,6 +650,41 @@ gb_status gb_check_inputs(gb_circuit* c, const void* input_values, uint32_t flag
 /* gb_ctx_set_option "check_witness" (default 0): 1 = every gb_prove*, gb_prove_partition* and gb_prove_inputs* that does the full
  * computation runs the check on its witness before the wires commitment and returns GB_ERR_UNSATISFIED instead of bytes that
  * cannot verify.  The incremental retry paths are not re-checked: only the random wire changed, and no gate constrains it. */
+
+/* ---- the copy constraints from sigma alone -----------------------------------------------------------------------------------
+ * The sigma columns ARE the copy permutation, written as field elements: sigma[col][row] = k_is[col'] w^row' sends the cell
+ * (col, row) to (col', row') (plonk/permutation_argument.rs, circuit_builder.rs:1005-1040).  gb_circuit_decode_sigmas reads
+ * (col', row') back out of every value on the device (csrc/kernels_sigma.hip, csrc/sigma_decode.hpp) - the coset by
+ * s^n = k_is[col']^n, the row by a discrete logarithm in the group of order n = 2^degree_bits - checks that the result is a
+ * permutation of the routed cells, and labels every wire cell with the lowest cell of its cycle (a cell is
+ * row * num_wires + column, as in gb_violation; non-routed wires and fixed points label themselves).  The cycles are the copy
+ * classes: from then on the witness check compares every cell with the first cell of its class on this circuit too, and with the
+ * option "check_witness" gb_prove* refuses a broken copy with GB_ERR_UNSATISFIED.  Any gb_circuit_create* handle, either field.
+ * The labels stay with the circuit until gb_circuit_free / gb_ctx_trim; a call on a circuit that has them does no device work -
+ * except that, where a partition has been set since, it compares the two (below).
+ * GB_ERR_INVALID, the circuit as usable as before and no labels kept:
+ *   "k_is do not name distinct cosets"   two k_is[j]^n coincide (or a k_is[j] is 0)
+ *   "sigma names no routed cell at row r, wire c: the value v .."   the lowest cell whose value is in none of the cosets
+ *                                        k_is[j] H, j < num_routed_wires - 0, or a coset of a non-routed wire
+ *   "sigma is not a permutation: row r, wire c and another cell both go to row r', wire c'"   the lowest cell whose target is shared
+ *   "partition and sigma disagree at row r, wire c (partition: first cell A, sigma: first cell B)"   a partition is set and, for
+ *                                        the lowest routed cell where they differ, the first cell of its class in the slot map
+ *                                        is not its label: the representative_map does not describe the wiring of these sigmas
+ *   flags other than 0.
+ * GB_ERR_UNSUPPORTED: more than 2^32 wire cells.  Timing scopes: "decode sigmas: decode", "decode sigmas: classes", "decode
+ * sigmas: compare" (the sigma values on H are resident with the circuit: there is no transform). */
+typedef struct gb_sigma_info {
+    uint64_t routed_cells;       /* num_routed_wires * 2^degree_bits */
+    uint64_t moved_cells;        /* cells with sigma(cell) != cell */
+    uint64_t num_classes;        /* cycles of length >= 2 */
+    uint64_t largest_class;      /* cells in the longest cycle (1 if none) */
+    uint32_t rounds;             /* doubling rounds the class pass ran */
+    uint32_t compared_partition; /* 1: a partition was set and its classes were compared */
+} gb_sigma_info;
+gb_status gb_circuit_decode_sigmas(gb_circuit* c, uint32_t flags, void* info /* gb_sigma_info, may be NULL */);
+/* first_cell_out[num_wires * 2^degree_bits] (host): the label of every wire cell.  GB_ERR_INVALID if the sigmas have not been
+ * decoded. */
+gb_status gb_circuit_copy_classes(gb_circuit* c, uint32_t* first_cell_out);
 
 /* verify() of a proof produced for this circuit (plonk/verifier.rs:17-128, fri/verifier.rs:67-250,
  * plonk/get_challenges.rs:26-101), restated for the dummy gate set and run on the HOST like the reference's verifier: the

@@ -171,6 +171,18 @@ pub struct gb_check_result {
     pub num_listed: u32,
 }
 
+/// What `decode_sigmas` found (include/goldibear_gpu.h: gb_sigma_info): the copy permutation's cycles as copy classes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gb_sigma_info {
+    pub routed_cells: u64,
+    pub moved_cells: u64,
+    pub num_classes: u64,
+    pub largest_class: u64,
+    pub rounds: u32,
+    pub compared_partition: u32,
+}
+
 /// What a witness check found: the first `max_violations` violations in the header's order, and the counts.
 #[derive(Clone, Debug, Default)]
 pub struct CheckOutcome {
@@ -260,6 +272,8 @@ extern "C" {
                           result: *mut c_void) -> i32;
     fn gb_check_inputs(c: *mut gb_circuit, input_values: *const c_void, flags: u32, violations_out: *mut c_void, capacity: usize,
                        result: *mut c_void) -> i32;
+    fn gb_circuit_decode_sigmas(c: *mut gb_circuit, flags: u32, info: *mut c_void) -> i32;
+    fn gb_circuit_copy_classes(c: *mut gb_circuit, first_cell_out: *mut u32) -> i32;
     fn gb_commit_values(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
                         cap_height: u32, salts: *const c_void, flags: u32, out: *mut *mut gb_batch) -> i32;
     fn gb_commit_coeffs(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
@@ -1222,6 +1236,22 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
                             &mut res as *mut gb_check_result as *mut c_void)
         };
         self.finish_check(st, out, res)
+    }
+    /// Read the copy permutation back out of the sigma columns and keep its cycles as copy classes: from then on `check_witness`
+    /// - and `prove*` under the option "check_witness" - check the copy constraints of a circuit that has no partition.  With a
+    /// partition set, also checks that the partition's classes are the same wiring (`InvalidInput` names the first cell where
+    /// they are not).  A repeated call does no device work.
+    pub fn decode_sigmas(&self) -> Result<gb_sigma_info, GpuError> {
+        let mut info = gb_sigma_info::default();
+        check(self.ctx.0, unsafe { gb_circuit_decode_sigmas(self.handle, 0, &mut info as *mut gb_sigma_info as *mut c_void) })?;
+        Ok(info)
+    }
+    /// After `decode_sigmas`: per wire cell `row * num_wires + column`, the lowest cell of its copy class.
+    pub fn copy_classes(&self) -> Result<Vec<u32>, GpuError> {
+        let c = &self.config;
+        let mut out = vec![0u32; (c.num_wires as usize) << c.degree_bits];
+        check(self.ctx.0, unsafe { gb_circuit_copy_classes(self.handle, out.as_mut_ptr()) })?;
+        Ok(out)
     }
     /// Give up after `PermArgZero` (`ProverError::TooManyPermArgFailures`, prover.rs:221-225): releases what the failed attempt
     /// left on the device for `prove_retry` (~12 GB at 2^20 Goldilocks rows).  No-op when nothing is held.

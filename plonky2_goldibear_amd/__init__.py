@@ -11,7 +11,7 @@ from .native import PermArgZeroError, TooManyPermArgFailuresError, VerifyError  
 from .native import UnsatisfiedError, Violation  # noqa: F401
 from .polynomial_batch import GpuContext, MerkleTree, PolynomialBatch  # noqa: F401
 from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  # noqa: F401
-from .prover import CircuitData, VerifierCircuitData  # noqa: F401
+from .prover import CircuitData, SigmaInfo, VerifierCircuitData  # noqa: F401
 from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
 from .fri import prove_openings, verify_fri_proof  # noqa: F401
 from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401

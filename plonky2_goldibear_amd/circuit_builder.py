@@ -1438,6 +1438,20 @@ class BuiltCircuit:
             self.set_generators(pw=pw)
         return self.data.check_inputs(self.input_values(pw, rng), max_violations=max_violations)
 
+    # ---- the copy constraints from sigma alone (include/goldibear_gpu.h gb_circuit_decode_sigmas / gb_circuit_copy_classes)
+    def decode_sigmas(self):
+        """CircuitData.decode_sigmas of the built circuit: the sigma columns read back as copy classes -> SigmaInfo; with the
+        partition set (check(), prove_partition()), also that the representative map describes the same wiring"""
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        return self.data.decode_sigmas()
+
+    def copy_classes(self):
+        """CircuitData.copy_classes: per wire cell row * num_wires + column the lowest cell of its copy class"""
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        return self.data.copy_classes()
+
     @property
     def _input_targets(self):
         return self._inputs

@@ -64,8 +64,10 @@ struct TableCache {
     std::vector<void*> owned;                                    // the shared 4096-point tables above
     std::map<u32, Owner<Tables>> tables;                         // by log_n
     std::map<std::tuple<u32, u32, T, int>, Owner<Cosets>> cosets;   // by (log_n, rate_bits, shift (device form), inverse)
+    std::map<u32, Owner<gbk::sigma::DlogTables<F>>> dlog;           // by log_n: gb_circuit_decode_sigmas' discrete-log tables
     void release() {
         for (void* p : owned) hipFree(p);
+        for (auto& kv : dlog) for (void* p : kv.second.owned) hipFree(p);
         for (auto& kv : tables) for (void* p : kv.second.owned) hipFree(p);
         for (auto& kv : cosets) for (void* p : kv.second.owned) hipFree(p);
     }

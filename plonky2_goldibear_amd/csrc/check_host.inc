@@ -2,7 +2,8 @@
 // where not?  Included at the end of prover_host.inc.  The kernels are kernels_check.hip's, the row logic
 // witness_check.hpp's; this file prepares a circuit on its first check (the selector and constant columns as values on H, a row
 // list per gate), runs one launch per gate that has rows and the copy pass, reads the counts back first and the per-entry results
-// only where a count is not zero, and puts the violations in the order the header gives.
+// only where a count is not zero, and puts the violations in the order the header gives.  The copy classes are the partition's
+// where the circuit has one, else those gb_circuit_decode_sigmas read out of the sigma columns (sigma_host.inc), else none.
 
 #include "witness_check.hpp"
 
@@ -56,6 +57,19 @@ gb_status check_prepare(Circuit<F>* c) {
     gbk::check_fill_rows<F>(c->gates, (const T*)k.hvals, (u32)n, offsets_dev, k.rows, st);
     if (hipGetLastError() != hipSuccess) return failed(fail(ctx, GB_ERR_HIP, "kernel launch failed"));
     k.ready = true;
+    return GB_OK;
+}
+
+// the first cell of every class of the partition's slot map, once per partition (the circuit has one, with fewer than 2^32 cells)
+static gb_status check_first_cells_of_partition(gb_circuit* c) {
+    gb_ctx* ctx = c->ctx;
+    gb_circuit::Check& k = c->chk;
+    if (k.first_cell) return GB_OK;
+    const u32 num_slots = (u32)c->part.reps.size();
+    void* p = nullptr;
+    HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(1, num_slots) * sizeof(u32)));
+    k.first_cell = static_cast<u32*>(p);
+    gbk::check_first_cells(c->part.slots_dev, (u64)c->cfg.num_wires << c->cfg.degree_bits, num_slots, k.first_cell, c->ctx->stream);
     return GB_OK;
 }
 
@@ -131,23 +145,22 @@ gb_status check_matrix(Circuit<F>* c, TmpAlloc& tmp, const typename F::T* wit, c
         gbk::check_gate_rows<F>(cp, g, c->programs.num_programs ? &pp : nullptr, k.rows + off, k.counts[g], (const T*)k.hvals, wit, pi_dev,
                                 fail_index + off, fail_value + off, words + 2 + g, st);
     }
-    // copies: the first cell of every class once per partition, then one pass over the cells
-    const bool copies = c->part.set && c->part.slots_dev;
-    const u32 num_slots = (u32)c->part.reps.size();
+    // copies: the classes of the partition's slot map (their first cells once per partition), or without a partition the labels
+    // gb_circuit_decode_sigmas left - a slot map whose slots are the first cells themselves; then one pass over the cells
+    const bool by_partition = c->part.set && c->part.slots_dev;
+    const bool copies = by_partition || k.sigma_labels;
+    const u32* slots = by_partition ? c->part.slots_dev : k.sigma_labels;
+    const u32 num_slots = by_partition ? (u32)c->part.reps.size() : (u32)cells;
     u64* mask = nullptr;
     const size_t mask_words = (size_t)((cells + 63) / 64);
     if (copies) {
         if (cells > 0xFFFFFFFFull) return fail(ctx, GB_ERR_UNSUPPORTED, "copy check: more than 2^32 wire cells");
-        if (!k.first_cell) {
-            void* p = nullptr;
-            HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(1, num_slots) * sizeof(u32)));
-            k.first_cell = static_cast<u32*>(p);
-            gbk::check_first_cells(c->part.slots_dev, cells, num_slots, k.first_cell, st);
-        }
+        if (by_partition)
+            if ((s = check_first_cells_of_partition(c))) return s;
         mask = tmp.get<u64>(mask_words);
         if (!mask) return fail(ctx, GB_ERR_OOM, "copy check mask");
         Scope sp(ctx, "check witness: copies");
-        gbk::check_copies<F>(c->part.slots_dev, k.first_cell, num_slots, wit, (u32)n, nw, mask, words + 1, st);
+        gbk::check_copies<F>(slots, by_partition ? k.first_cell : nullptr, num_slots, wit, (u32)n, nw, mask, words + 1, st);
     }
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
     std::vector<u32> hw(nwords);
@@ -214,7 +227,7 @@ gb_status check_matrix(Circuit<F>* c, TmpAlloc& tmp, const typename F::T* wit, c
         if ((s = upload_tmp(ctx, tmp, bad, &bad_dev))) return s;
         u64* rep_dev = tmp.get<u64>(3 * bad.size());
         if (!rep_dev) return fail(ctx, GB_ERR_OOM, "copy report");
-        gbk::check_copy_report<F>(c->part.slots_dev, k.first_cell, num_slots, wit, (u32)n, nw, bad_dev, (u32)bad.size(), rep_dev, st);
+        gbk::check_copy_report<F>(slots, by_partition ? k.first_cell : nullptr, num_slots, wit, (u32)n, nw, bad_dev, (u32)bad.size(), rep_dev, st);
         std::vector<u64> rep(3 * bad.size());
         if ((s = read_back(ctx, rep.data(), rep_dev, rep.size() * sizeof(u64)))) return s;
         for (size_t i = 0; i < bad.size(); i++) {
@@ -224,7 +237,7 @@ gb_status check_matrix(Circuit<F>* c, TmpAlloc& tmp, const typename F::T* wit, c
     }
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
     if (out) std::copy(listed.begin(), listed.end(), out);
-    if (result) *result = gb_check_result{num_gate, num_selector, num_copy, copies ? 1u : 0u, (uint32_t)listed.size()};
+    if (result) *result = gb_check_result{num_gate, num_selector, num_copy, copies ? (by_partition ? 1u : 2u) : 0u, (uint32_t)listed.size()};
     if (!(num_gate + num_selector + num_copy)) return GB_OK;
     std::string msg = "the witness does not satisfy the circuit: " + std::to_string(num_selector) + " selector, " + std::to_string(num_gate) +
                       " gate, " + std::to_string(num_copy) + " copy violations";

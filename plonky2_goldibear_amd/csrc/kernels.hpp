@@ -11,6 +11,7 @@
 #include "gate_set.hpp"
 #include "generator_ops.hpp"
 #include "challenge_slices.hpp"
+#include "sigma_decode.hpp"
 
 namespace gbk {
 
@@ -290,7 +291,8 @@ void check_gate_rows(const CheckParams<F>& p, u32 g, const ProgramParams<F>* pro
                      const typename F::T* wit, const typename F::T* pi_hash, u32* fail_index, u64* fail_value, u32* num_failed, hipStream_t st);
 // first[slot] = the lowest cell row * num_wires + column of the slot's class (slots: the map of gb_circuit_set_partition)
 void check_first_cells(const u32* slots, u64 cells, u32 num_slots, u32* first, hipStream_t st);
-// bit c of mask (64 cells per word) = cell c differs from the first cell of its class; *num_failed += those
+// bit c of mask (64 cells per word) = cell c differs from the first cell of its class; *num_failed += those.  first = null: a
+// slot IS its class's first cell (the labels of gb_circuit_decode_sigmas as the slot map, num_slots = the number of cells)
 template <class F>
 void check_copies(const u32* slots, const u32* first, u32 num_slots, const typename F::T* wit, u32 n, u32 num_wires, u64* mask,
                   u32* num_failed, hipStream_t st);
@@ -301,6 +303,42 @@ void check_copy_report(const u32* slots, const u32* first, u32 num_slots, const 
 // *flag |= 1 if a word of v is not below p
 template <class F>
 void check_canonical(const typename F::T* v, size_t count, u32* flag, hipStream_t st);
+
+// ---- the copy permutation out of the sigma columns (kernels_sigma.hip's launchers; sigma_decode.hpp has the arithmetic).  The
+// routed cells are numbered i = col * n + row as the sigma values lie, `count` = num_routed_wires * n of them (below 2^32); a wire
+// cell is row * num_wires + col.  state[i] = {next, label}: the cell sigma sends i to (sigma's numbering) and the lowest cell
+// number met so far on i's cycle.
+template <class F>
+struct SigmaDecodeParams {
+    sigma::DlogTables<F> t;                     // device pointers
+    const typename F::T *k_pow_n, *k_inv;       // [num_routed], device form: k_is[j]^n and 1 / k_is[j]
+    u32 num_routed, num_wires;
+};
+// words of the decode pass: the lowest cell whose value names no routed cell and the lowest cell whose target is shared (both
+// start as all ones), and whether some target was hit twice
+static constexpr u32 SIGMA_WORD_NO_CELL = 0, SIGMA_WORD_SHARED = 1, SIGMA_WORD_DOUBLE_HIT = 2, SIGMA_WORDS = 3;
+// the tables of a decode launch live in LDS up to this size, in global memory above it
+static constexpr size_t SIGMA_LDS_MAX_BYTES = 48 << 10;
+// state[i] = {target of sigma[i] or sigma::NO_CELL, i's cell number}; seen: one bit per target, zeroed by the caller
+template <class F>
+void sigma_decode(const SigmaDecodeParams<F>& p, const typename F::T* sigma, u32 count, uint2* state, u32* seen, u32* words,
+                  hipStream_t st);
+// after a double hit: words[SIGMA_WORD_SHARED] = the lowest cell whose target another cell has too; hits: [count] scratch
+void sigma_shared_target(const uint2* state, u32 count, u32* hits, u32* words, hipStream_t st);
+// out[i] = {SIGMA_CLOSED, the label of i's whole cycle} where the cycle has at most SIGMA_WALK + 1 cells, else in[i]
+static constexpr u32 SIGMA_WALK = 8, SIGMA_CLOSED = 0xFFFFFFFFu;
+// ... and stats = {classes of two cells or more, the cells in them, the largest class (0: none)} of the closed cycles
+void sigma_walk(const uint2* in, uint2* out, u32 count, u64* stats, hipStream_t st);
+// one doubling round in -> out over the cells that are not closed; *changed = 1 if a label fell.  copy_closed: `out` does not
+// hold the closed cells yet (the first round after the walk)
+void sigma_round(const uint2* in, uint2* out, u32 count, bool copy_closed, u32* changed, hipStream_t st);
+// stats += the same of the cycles the walk left open (after the rounds); sizes: [count] scratch
+void sigma_class_stats(const uint2* state, u32 count, u32 lg, u32 num_wires, u32* sizes, u64* stats, hipStream_t st);
+// labels[cell] of all wire cells: the lowest cell of the cell's cycle, a non-routed cell itself
+void sigma_labels(const uint2* state, u64 cells, u32 lg, u32 num_wires, u32 num_routed, u32* labels, hipStream_t st);
+// *lowest (starts as all ones) = the lowest routed cell whose class in the slot map starts at another cell than its label
+void sigma_compare(const u32* labels, const u32* slots, const u32* first, u32 num_slots, u64 cells, u32 num_wires, u32 num_routed,
+                   u32* lowest, hipStream_t st);
 
 // l0[j] = Z_H(x_j) / (n (x_j - 1)), zh = device copy of the 2^rate_bits values of Z_H on the cosets
 template <class F>

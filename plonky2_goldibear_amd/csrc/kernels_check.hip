@@ -1,5 +1,5 @@
 // The witness check (gb_check_witness): the gate constraints evaluated on H itself, where a satisfied witness makes them vanish,
-// and the copy constraints read off the partition's slot map.  kernels_gates.hip evaluates every gate at every point of the LDE
+// and the copy constraints read off the partition's slot map - or off the labels gb_circuit_decode_sigmas left (kernels_sigma.hip).  kernels_gates.hip evaluates every gate at every point of the LDE
 // coset g H and folds with alpha; here a row runs the ONE gate its selector names, unfolded, and reports the first constraint that
 // is not zero.  The row logic is witness_check.hpp's (GB_HD, shared with the host).
 //   preparation (per circuit)  k_check_count -> k_check_scan -> k_check_fill: a list of rows per gate, ascending, and one of the
@@ -154,7 +154,8 @@ __global__ __launch_bounds__(CHECK_BLOCK) void k_first_cell(const u32* __restric
     if (slot < num_slots) atomicMin(&first[slot], (u32)cell);
 }
 
-// one thread per cell, in cell order: does it hold what the first cell of its class holds?  A wave writes its ballot as one word
+// one thread per cell, in cell order: does it hold what the first cell of its class holds (first = null: the slot is that cell -
+// the labels decoded from sigma)?  A wave writes its ballot as one word
 // of `mask` (bit order = cell order, so the host reads the violations off in ascending order) and adds its count.
 template <class F>
 __global__ __launch_bounds__(CHECK_BLOCK) void k_check_copies(const u32* __restrict__ slots, const u32* __restrict__ first, u32 num_slots,
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(CHECK_BLOCK) void k_check_copies(const u32* __restr
     bool bad = false;
     if (cell < cells) {
         const u32 slot = slots[cell];
-        const u32 fc = slot < num_slots ? first[slot] : (u32)cell;
+        const u32 fc = slot < num_slots ? (first ? first[slot] : slot) : (u32)cell;
         if (fc != (u32)cell && fc < cells)
             bad = wit[(size_t)(cell % num_wires) * n + cell / num_wires] != wit[(size_t)(fc % num_wires) * n + fc / num_wires];
     }
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(CHECK_BLOCK) void k_copy_report(const u32* __restri
     const u32 i = blockIdx.x * CHECK_BLOCK + threadIdx.x;
     if (i >= count) return;
     const u32 cell = cells[i], slot = slots[cell];
-    const u32 fc = slot < num_slots ? first[slot] : cell;
+    const u32 fc = slot < num_slots ? (first ? first[slot] : slot) : cell;
     out[3 * (size_t)i] = wit[(size_t)(cell % num_wires) * n + cell / num_wires];
     out[3 * (size_t)i + 1] = fc;
     out[3 * (size_t)i + 2] = wit[(size_t)(fc % num_wires) * n + fc / num_wires];

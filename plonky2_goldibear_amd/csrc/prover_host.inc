@@ -80,7 +80,7 @@ struct gb_circuit {
     } gen_programs;
     // gb_check_witness (check_host.inc): what the first check on the circuit builds and later ones reuse - the selector and constant
     // columns as values on H, the row list of every gate - and, per partition, the first cell of every copy class.  Released by
-    // gb_circuit_free and gb_ctx_trim; the first cells also when gb_circuit_set_partition replaces the map.
+    // gb_circuit_free and gb_ctx_trim (the decoded labels too); the first cells also when gb_circuit_set_partition replaces the map.
     struct Check {
         bool ready = false;
         void* hvals = nullptr;               // [num_selectors + num_constants][n], natural order, device form
@@ -88,13 +88,26 @@ struct gb_circuit {
         uint32_t* rows = nullptr;            // the lists, one behind the other
         std::vector<uint32_t> counts, offsets;   // host copies: [num_gates + 1], [num_gates + 2]
         uint32_t* first_cell = nullptr;      // [number of slots]
+        // gb_circuit_decode_sigmas (sigma_host.inc): per wire cell the lowest cell of its cycle under sigma - the copy pass reads
+        // them as a slot map whose slots are first cells - and what the call reported; sigma_compared: against the partition set now
+        uint32_t* sigma_labels = nullptr;    // [num_wires * n]
+        gb_sigma_info sigma_info{};
+        bool sigma_compared = false;
     } chk;
     void drop_check_copies() {   // (the caller has waited for the stream)
         if (chk.first_cell) (void)hipFree(chk.first_cell);
         chk.first_cell = nullptr;
+        chk.sigma_compared = false;
+    }
+    void drop_sigma_labels() {   // (the caller has waited for the stream)
+        if (chk.sigma_labels) (void)hipFree(chk.sigma_labels);
+        chk.sigma_labels = nullptr;
+        chk.sigma_info = gb_sigma_info{};
+        chk.sigma_compared = false;
     }
     void drop_check() {          // (the caller has waited for the stream)
         drop_check_copies();
+        drop_sigma_labels();
         for (void* p : {chk.hvals, (void*)chk.lists_dev, (void*)chk.rows})
             if (p) (void)hipFree(p);
         chk = Check{};
@@ -2743,3 +2756,4 @@ gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t 
 }  // extern "C"
 
 #include "check_host.inc"
+#include "sigma_host.inc"

@@ -106,6 +106,8 @@ SIGNATURES = {
     "gb_check_witness": (_i32, [_vp, _vp, _u32, C.POINTER(_u64), _sz, _vp, _sz, _vp]),
     "gb_check_partition": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp]),
     "gb_check_inputs": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp]),
+    "gb_circuit_decode_sigmas": (_i32, [_vp, _u32, _vp]),
+    "gb_circuit_copy_classes": (_i32, [_vp, C.POINTER(_u32)]),
     "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
     "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
     "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
@@ -197,6 +199,11 @@ class gb_violation(C.Structure):
 class gb_check_result(C.Structure):
     _fields_ = [("num_gate_violations", _u64), ("num_selector_violations", _u64), ("num_copy_violations", _u64),
                 ("copies_checked", _u32), ("num_listed", _u32)]
+
+
+class gb_sigma_info(C.Structure):
+    _fields_ = [("routed_cells", _u64), ("moved_cells", _u64), ("num_classes", _u64), ("largest_class", _u64), ("rounds", _u32),
+                ("compared_partition", _u32)]
 
 
 class Violation:

@@ -6,6 +6,7 @@
 `prove_with_partition_witness` (plonk/prover.rs:160-447) from an already generated
 `MatrixWitness.wire_values` matrix to `ProofWithPublicInputs` bytes.
 """
+import collections
 import ctypes as C
 import sys
 import weakref
@@ -79,6 +80,10 @@ class _FriParamsOps:
         arr, n = (C.c_uint32 * 32)(), C.c_uint32()
         N.check(self._lib.gb_circuit_fri_reduction_arity_bits(self.handle, arr, C.byref(n)), getattr(getattr(self, "ctx", None), "handle", None))
         return [int(arr[i]) for i in range(n.value)]
+
+
+SigmaInfo = collections.namedtuple("SigmaInfo", [name for name, _ in N.gb_sigma_info._fields_])
+SigmaInfo.__doc__ = "gb_sigma_info: what CircuitData.decode_sigmas found"
 
 
 class CircuitData(_ProofBytesOps, _FriParamsOps):
@@ -441,6 +446,23 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         v, flags = self._input_values(input_values, p3_repr)
         vp = v.ctypes.data if v.size else None
         return self._check_call(lambda out, cap, res: self._lib.gb_check_inputs(self.handle, vp, flags, out, cap, res), max_violations)
+
+    # ---- the copy constraints from sigma alone (include/goldibear_gpu.h: gb_circuit_decode_sigmas, gb_circuit_copy_classes)
+    def decode_sigmas(self, flags=0):
+        """read the copy permutation back out of the sigma columns on the device and keep its cycles as copy classes -> SigmaInfo.
+        From then on check_witness - and prove* under the option "check_witness" - check the copy constraints of a circuit that
+        has no partition (copies_checked = 2); with a partition set, the partition's classes are compared with the decoded ones
+        (ShapeError names the first cell where they differ).  A repeated call does no device work."""
+        info = N.gb_sigma_info()
+        N.check(self._lib.gb_circuit_decode_sigmas(self.handle, flags, C.cast(C.pointer(info), C.c_void_p)), self.ctx.handle)
+        return SigmaInfo(*[int(getattr(info, name)) for name, _ in N.gb_sigma_info._fields_])
+
+    def copy_classes(self):
+        """after decode_sigmas: u32[2^degree_bits * num_wires], per wire cell row * num_wires + column the lowest cell of its copy
+        class (a non-routed wire and a cell sigma does not move: itself)"""
+        out = np.empty(self.cfg.num_wires << self.cfg.degree_bits, dtype=np.uint32)
+        N.check(self._lib.gb_circuit_copy_classes(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32))), self.ctx.handle)
+        return out
 
     @property
     def constants_sigmas_commitment(self):
