@@ -686,6 +686,48 @@ gb_status gb_circuit_decode_sigmas(gb_circuit* c, uint32_t flags, void* info /* 
  * decoded. */
 gb_status gb_circuit_copy_classes(gb_circuit* c, uint32_t* first_cell_out);
 
+/* ---- copy constraints to sigma columns and representative map ------------------------------------------------------------------
+ * The other direction: "generate sigma polynomials" of CircuitBuilder::build (plonk/circuit_builder.rs:1005-1040, 1220-1224;
+ * plonk/permutation_argument.rs) on the device (csrc/kernels_wiring.hip, csrc/wiring.hpp), a stage of its own on a context like
+ * gb_fft.  Target indices are those of gb_circuit_set_partition: wire (row, column) is row * num_wires + column, virtual target
+ * i is degree * num_wires + i.  copy_constraints ([num_copies][2], the Target::index of both sides) and k_is ([num_routed_wires],
+ * canonical) are host pointers.  sigmas_out is [num_routed_wires][2^degree_bits] canonical values on H: a host pointer, or with
+ * GB_INPUT_DEVICE a device pointer of the caller (16-byte aligned) written on the context's stream - ready to be named by the
+ * column pointers of gb_circuit_create*_cols(.., GB_INPUT_DEVICE).  The call returns when everything is written.
+ * Every result but `rounds` is a function of the arguments alone, whatever the order in which the device ran its threads:
+ *   classes              the connected components of the targets under the pairs
+ *   representative map   representative_map_out[t] (host, [num_targets]; may be NULL) = the lowest target index of t's class: a valid
+ *                        ProverOnlyCircuitData.representative_map for gb_circuit_set_partition.  It need not be the reference's,
+ *                        whose roots depend on the order of its merges; nothing in a proof depends on which member it is.
+ *   sigmas               within a class the routed wire cells in ascending row * num_wires + column order each point to the next,
+ *                        the last to the first (the order wire_partition pushes them in, permutation_argument.rs:94-100):
+ *                        sigma[col][row] = k_is[col'] w^row', w = two_adic_generator(degree_bits), and k_is[col] w^row for a cell
+ *                        alone in its class - byte for byte the reference's values.  Virtual targets join classes and appear in
+ *                        no sigma.
+ * num_copies = 0 gives the identity sigmas and the identity map.
+ * GB_ERR_INVALID, the outputs unspecified and the context as usable as before: a null argument; an unknown field tag;
+ * num_routed_wires = 0 or > num_wires; num_targets < degree * num_wires; a k_is entry >= p; flag bits other than
+ * GB_INPUT_DEVICE; and, checked on the device before an index is used as an address,
+ *   "copy constraint i names target t, but there are N targets"   the lowest pair with an entry >= num_targets
+ *   "Tried to route a wire that isn't routable: copy constraint i, target t (row r, wire c)"   the lowest pair that names a wire
+ *                        cell of a column >= num_routed_wires (circuit_builder.rs:543-551)
+ * GB_ERR_UNSUPPORTED: num_targets >= 2^32, or degree_bits above the field's two-adicity.  GB_ERR_OOM as elsewhere.
+ * Timing scopes: "wiring: upload", "wiring: classes", "wiring: order", "wiring: sigmas". */
+typedef struct gb_wiring_info {
+    uint64_t routed_cells;     /* num_routed_wires * 2^degree_bits */
+    uint64_t moved_cells;      /* routed cells with sigma(cell) != cell */
+    uint64_t num_classes;      /* classes holding >= 2 routed wire cells */
+    uint64_t largest_class;    /* routed wire cells in the largest such class (1 if none) */
+    uint64_t merged_targets;   /* targets whose representative is not themselves */
+    uint32_t rounds;           /* compression passes over the forest, the last one - which moved no pointer - included; a pass lets
+                                  every target jump up to 4 ancestors.  A diagnostic: the shape the lock-free merges leave the
+                                  forest in, and so this count, depends on the order the device ran them in */
+    uint32_t reserved;
+} gb_wiring_info;
+gb_status gb_wiring_sigmas(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, uint32_t num_wires, uint32_t num_routed_wires,
+                           const void* k_is, const uint64_t* copy_constraints, uint64_t num_copies, uint64_t num_targets, uint32_t flags,
+                           void* sigmas_out, uint64_t* representative_map_out, void* info /* gb_wiring_info, may be NULL */);
+
 /* verify() of a proof produced for this circuit (plonk/verifier.rs:17-128, fri/verifier.rs:67-250,
  * plonk/get_challenges.rs:26-101), restated for the dummy gate set and run on the HOST like the reference's verifier: the
  * Fiat-Shamir replay, vanishing(zeta) == Z_H(zeta) * quotient(zeta), the proof of work, every Merkle path and the FRI

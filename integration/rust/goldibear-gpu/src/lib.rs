@@ -183,6 +183,27 @@ pub struct gb_sigma_info {
     pub compared_partition: u32,
 }
 
+/// What `wiring_sigmas` made (include/goldibear_gpu.h: gb_wiring_info).  `rounds` is a diagnostic that depends on the device's schedule.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gb_wiring_info {
+    pub routed_cells: u64,
+    pub moved_cells: u64,
+    pub num_classes: u64,
+    pub largest_class: u64,
+    pub merged_targets: u64,
+    pub rounds: u32,
+    pub reserved: u32,
+}
+
+/// The sigma columns ([num_routed_wires][2^degree_bits], canonical), the representative map and the counts.
+#[derive(Clone, Debug, Default)]
+pub struct Wiring<W> {
+    pub sigmas: Vec<W>,
+    pub representative_map: Vec<u64>,
+    pub info: gb_wiring_info,
+}
+
 /// What a witness check found: the first `max_violations` violations in the header's order, and the counts.
 #[derive(Clone, Debug, Default)]
 pub struct CheckOutcome {
@@ -274,6 +295,9 @@ extern "C" {
                        result: *mut c_void) -> i32;
     fn gb_circuit_decode_sigmas(c: *mut gb_circuit, flags: u32, info: *mut c_void) -> i32;
     fn gb_circuit_copy_classes(c: *mut gb_circuit, first_cell_out: *mut u32) -> i32;
+    fn gb_wiring_sigmas(ctx: *mut gb_ctx, field: u32, degree_bits: u32, num_wires: u32, num_routed_wires: u32, k_is: *const c_void,
+                        copy_constraints: *const u64, num_copies: u64, num_targets: u64, flags: u32, sigmas_out: *mut c_void,
+                        representative_map_out: *mut u64, info: *mut c_void) -> i32;
     fn gb_commit_values(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
                         cap_height: u32, salts: *const c_void, flags: u32, out: *mut *mut gb_batch) -> i32;
     fn gb_commit_coeffs(ctx: *mut gb_ctx, field: u32, cols: *const c_void, ncols: usize, log_n: u32, rate_bits: u32,
@@ -517,6 +541,25 @@ impl GpuContext {
                 Transform::Lde => gb_lde(self.0, f, p, p, num_polys, log_n, 0, ext as u32, sp, GB_INPUT_HOST),
             }
         })
+    }
+}
+
+impl GpuContext {
+    /// "generate sigma polynomials" of `CircuitBuilder::build` (plonk/circuit_builder.rs:1005-1040) on the device: the copy
+    /// constraints as pairs of `Target::index` -> sigma columns on H and a representative map (the lowest index of every class).
+    /// `k_is`: one canonical word per routed wire; `num_targets`: `degree * num_wires + virtual targets`.
+    pub fn wiring_sigmas<W: Copy + Default>(&self, degree_bits: u32, num_wires: u32, k_is: &[W], copy_constraints: &[[u64; 2]],
+                                            num_targets: u64) -> Result<Wiring<W>, GpuError> {
+        let routed = k_is.len() << degree_bits;
+        let mut out = Wiring { sigmas: vec![W::default(); routed], representative_map: vec![0u64; num_targets as usize],
+                               info: gb_wiring_info::default() };
+        check(self.0, unsafe {
+            gb_wiring_sigmas(self.0, field_tag::<W>(), degree_bits, num_wires, k_is.len() as u32, k_is.as_ptr() as *const c_void,
+                             copy_constraints.as_ptr() as *const u64, copy_constraints.len() as u64, num_targets, GB_INPUT_HOST,
+                             out.sigmas.as_mut_ptr() as *mut c_void, out.representative_map.as_mut_ptr(),
+                             &mut out.info as *mut gb_wiring_info as *mut c_void)
+        })?;
+        Ok(out)
     }
 }
 

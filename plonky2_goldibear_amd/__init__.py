@@ -5,6 +5,7 @@ native     ctypes binding of that ABI (no fallback: raises if the library is mis
 polynomial_batch  host-side mirror of PolynomialBatch / MerkleTree (fri/oracle.rs, hash/merkle_tree.rs)
 fri         the polynomial commitment scheme on its own: prove_openings on any FriInstanceInfo, verify_fri_proof (fri/oracle.rs, fri/verifier.rs)
 polynomial  the transforms on their own: fft / ifft / coset_fft / coset_ifft / lde / lde_onto_coset (field/src/polynomial/mod.rs)
+wiring      copy constraints -> sigma columns and representative map on the device: sigma_polys (plonk/permutation_argument.rs)
 """
 from .native import GB_BABYBEAR, GB_GOLDILOCKS, GoldibearError, ShapeError  # noqa: F401
 from .native import PermArgZeroError, TooManyPermArgFailuresError, VerifyError  # noqa: F401
@@ -12,6 +13,7 @@ from .native import UnsatisfiedError, Violation  # noqa: F401
 from .polynomial_batch import GpuContext, MerkleTree, PolynomialBatch  # noqa: F401
 from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  # noqa: F401
 from .prover import CircuitData, SigmaInfo, VerifierCircuitData  # noqa: F401
+from .wiring import WiringInfo, sigma_polys  # noqa: F401
 from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
 from .fri import prove_openings, verify_fri_proof  # noqa: F401
 from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401

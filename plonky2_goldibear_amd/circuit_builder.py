@@ -1060,7 +1060,14 @@ class CircuitBuilder:
         return state[:self.F.hout]
 
     # ---- build (circuit_builder.rs:1110-1378)
-    def build(self, ctx=None):
+    def build(self, ctx=None, wiring="host"):
+        """wiring: "host" - the forest and the sigma columns by the loops below (_forest, _sigma); "device" - by
+        wiring.sigma_polys on `ctx` (gb_wiring_sigmas): the same sigma values, and a representative map whose representatives
+        are the lowest target of every class, which the built circuit then uses throughout"""
+        if wiring not in ("host", "device"):
+            raise ValueError("wiring is \"host\" or \"device\"")
+        if wiring == "device" and ctx is None:
+            raise ValueError("wiring=\"device\" needs a GPU context")
         cfg, F = self.config, self.F
         p = F.p
         pi_hash = self.hash_n_to_hash_no_pad(list(self.public_inputs))
@@ -1097,8 +1104,12 @@ class CircuitBuilder:
                 consts[i, row] = c
         k_is = np.array([pow(F.generator, i, p) for i in range(cfg.num_routed_wires)], dtype=F.dtype)
         subgroup = F._powers(F.two_adic_generator(degree_bits), degree)
-        find = self._forest()
-        sigma = self._sigma(find, degree, k_is, subgroup)
+        representative_map = None
+        if wiring == "device":
+            sigma, representative_map, find = self._wiring_on_device(ctx, degree_bits, k_is)
+        else:
+            find = self._forest()
+            sigma = self._sigma(find, degree, k_is, subgroup)
         constants_sigmas = np.concatenate([np.array(sel_cols, dtype=F.dtype).reshape(len(groups), degree), consts, sigma])
         # gate generators, dropping the unused operations of partly filled gates (:1252-1270)
         incomplete = {}
@@ -1141,7 +1152,27 @@ class CircuitBuilder:
                             sorted({t for ab in self.copy_constraints for t in ab if t[0] == "w"}), programs=programs or None,
                             copy_targets=sorted({t for ab in self.copy_constraints for t in ab}),
                             num_virtual_targets=self.virtual_target_index,
-                            row_gates=[gates.index(g) for g, _ in self.gate_instances], generator_programs=generator_programs)
+                            row_gates=[gates.index(g) for g, _ in self.gate_instances], generator_programs=generator_programs,
+                            representative_map=representative_map)
+
+    def _wiring_on_device(self, ctx, degree_bits, k_is):
+        """the copy constraints as pairs of Target::index -> (sigma, representative map, find) from wiring.sigma_polys; `find`
+        reads the map, so the Python witness path places a class's value where the map says its representative is"""
+        from .wiring import sigma_polys
+        nw, cells = self.config.num_wires, self.config.num_wires << degree_bits
+
+        def index(t):
+            return t[1] * nw + t[2] if t[0] == "w" else cells + t[1]
+
+        pairs = np.array([(index(a), index(b)) for a, b in self.copy_constraints], dtype=np.uint64).reshape(-1, 2)
+        sigma, rep, _ = sigma_polys(ctx, self.config.field, degree_bits, nw, self.config.num_routed_wires, k_is, pairs,
+                                    cells + self.virtual_target_index)
+
+        def find(t):
+            r = int(rep[index(t)])
+            return wire(r // nw, r % nw) if r < cells else ("v", r - cells)
+
+        return sigma, rep, find
 
     def _forest(self):
         """Disjoint sets over the targets that appear in copy constraints (plonk/permutation_argument.rs:13-101)."""
@@ -1213,7 +1244,7 @@ class BuiltCircuit:
 
     def __init__(self, ctx, cfg, F, degree_bits, constants_sigmas, k_is, gate_table, num_selectors, max_constants, generators, find,
                  public_inputs, random_wire, gate_ids, copy_wires, programs=None, copy_targets=(), num_virtual_targets=0, row_gates=(),
-                 generator_programs=()):
+                 generator_programs=(), representative_map=None):
         self.config, self.F, self.degree_bits, self.programs = cfg, F, degree_bits, programs
         self.constants_sigmas, self.k_is, self.gate_table, self.gate_ids = constants_sigmas, k_is, gate_table, gate_ids
         self.num_selectors, self.max_constants = num_selectors, max_constants
@@ -1222,7 +1253,7 @@ class BuiltCircuit:
         # every target a copy constraint names (wires and virtual targets) and the count of virtual targets: what
         # representative_map is built from
         self.copy_targets, self.num_virtual_targets = copy_targets, num_virtual_targets
-        self._representative_map, self._partition_set = None, False
+        self._representative_map, self._partition_set = representative_map, False   # (a map from wiring.sigma_polys, or built on demand)
         self.row_gates = row_gates          # per row: the index of its gate in gate_table (what a gb_generator record names)
         self.generator_programs = list(generator_programs)   # what a GB_GEN_PROGRAM record names by index
         self._generator_program_index = {tuple(pr.words): i for i, pr in enumerate(self.generator_programs)}

@@ -1463,5 +1463,6 @@ gb_status gb_permute(gb_ctx* ctx, uint32_t field, const void* in, void* out, uin
 
 #include "poly_host.inc"
 #include "prover_host.inc"
+#include "wiring_host.inc"
 #include "verifier_host.inc"
 #include "compress_host.inc"

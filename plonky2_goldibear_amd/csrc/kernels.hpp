@@ -12,6 +12,7 @@
 #include "generator_ops.hpp"
 #include "challenge_slices.hpp"
 #include "sigma_decode.hpp"
+#include "wiring.hpp"
 
 namespace gbk {
 
@@ -339,6 +340,40 @@ void sigma_labels(const uint2* state, u64 cells, u32 lg, u32 num_wires, u32 num_
 // *lowest (starts as all ones) = the lowest routed cell whose class in the slot map starts at another cell than its label
 void sigma_compare(const u32* labels, const u32* slots, const u32* first, u32 num_slots, u64 cells, u32 num_wires, u32 num_routed,
                    u32* lowest, hipStream_t st);
+
+// ---- copy constraints -> sigma columns and representative map (kernels_wiring.hip's launchers; wiring.hpp has what a thread does).
+// Targets, cells and routed cells are all below 2^32.  parent: [num_targets], the forest.
+void wiring_init(u32* parent, u32 num_targets, hipStream_t st);
+// one slice of `count` pairs ([count][2] target indices as the caller wrote them) that starts at pair `first`; err = {the lowest
+// pair with an entry >= num_targets, the lowest pair that names a wire cell of a column >= num_routed}, all ones to start with
+void wiring_union(const u64* pairs, u32 count, u64 first, u32* parent, u64 num_targets, u64 cells, u32 num_wires, u32 num_routed, u64* err,
+                  hipStream_t st);
+// one compression pass; *changed = 1 if a pointer moved
+void wiring_jump(u32* parent, u32 num_targets, u32* changed, hipStream_t st);
+// count[label]++ over the routed cells (count: [degree * num_wires], zeroed by the caller)
+void wiring_count(const u32* parent, u32 routed, u32 num_routed, u32 num_wires, u32* count, hipStream_t st);
+// exclusive scan of data[0 .. count) in place; sums: [wiring_scan_tiles(count)] scratch
+u32 wiring_scan_tiles(u32 count);
+void wiring_scan(u32* data, u32 count, u32* sums, hipStream_t st);
+// the routed cells whose label counts two or more, in ascending cell order: tile_count[wiring_sort_tiles(routed)] first, then
+// (after its scan) keys[pos] = label, cells[pos] = cell for the m kept ones
+u32 wiring_sort_tiles(u32 count);
+void wiring_keep_count(const u32* parent, const u32* count, u32 routed, u32 num_routed, u32 num_wires, u32* tile_count, hipStream_t st);
+void wiring_compact(const u32* parent, const u32* count, u32 routed, u32 num_routed, u32 num_wires, const u32* tile_start, u32 m, u32* keys,
+                    u32* cells, hipStream_t st);
+// one stable pass of the radix sort by digit `pass` of the key; hist: [wiring::RADIX * wiring_sort_tiles(m)], sums: the scan's scratch for that many words
+void wiring_sort_pass(const u32* keys, const u32* cells, u32 m, u32 pass, u32* hist, u32* sums, u32* keys_out, u32* cells_out, hipStream_t st);
+// succ[col * n + row] = the cell that follows in the cell's run (succ: [routed], all ones where the caller left a cell alone);
+// stats[0] += runs, stats[1] = max(stats[1], the longest run)
+void wiring_successors(const u32* keys, const u32* cells, u32 m, const u32* count, u32 lg, u32 num_wires, u32 routed, u32* succ, u64* stats,
+                       hipStream_t st);
+// out[col * n + row] = k_is[col'] w^row' (canonical) of the successor, or of the cell itself; lo / hi: the split root tables
+template <class F>
+void wiring_sigmas(const typename F::T* lo, const typename F::T* hi, const typename F::T* k_is, const u32* succ, u32 routed, u32 lg,
+                   u32 num_wires, typename F::T* out, hipStream_t st);
+void wiring_widen(const u32* parent, u32 num_targets, u64* out, hipStream_t st);
+// *merged += the targets with parent[t] != t
+void wiring_merged(const u32* parent, u32 num_targets, u64* merged, hipStream_t st);
 
 // l0[j] = Z_H(x_j) / (n (x_j - 1)), zh = device copy of the 2^rate_bits values of Z_H on the cosets
 template <class F>

@@ -108,6 +108,7 @@ SIGNATURES = {
     "gb_check_inputs": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp]),
     "gb_circuit_decode_sigmas": (_i32, [_vp, _u32, _vp]),
     "gb_circuit_copy_classes": (_i32, [_vp, C.POINTER(_u32)]),
+    "gb_wiring_sigmas": (_i32, [_vp, _u32, _u32, _u32, _u32, _vp, C.POINTER(_u64), _u64, _u64, _u32, _vp, C.POINTER(_u64), _vp]),
     "gb_fft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
     "gb_ifft": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _vp, _u32]),
     "gb_lde": (_i32, [_vp, _u32, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _u32]),
@@ -204,6 +205,11 @@ class gb_check_result(C.Structure):
 class gb_sigma_info(C.Structure):
     _fields_ = [("routed_cells", _u64), ("moved_cells", _u64), ("num_classes", _u64), ("largest_class", _u64), ("rounds", _u32),
                 ("compared_partition", _u32)]
+
+
+class gb_wiring_info(C.Structure):
+    _fields_ = [("routed_cells", _u64), ("moved_cells", _u64), ("num_classes", _u64), ("largest_class", _u64), ("merged_targets", _u64),
+                ("rounds", _u32), ("reserved", _u32)]
 
 
 class Violation:
