@@ -56,10 +56,17 @@ enum {
      * any u64 representative of the value, not necessarily below p; p3-baby-bear / p3-monty-31: the Montgomery word
      * x * 2^32 mod p), so a Vec<F> is handed over without an as_canonical_*() pass.  Without it elements are canonical.
      * Applies to `cols` / `witness` / `salts`; results (proof bytes, accessors) are canonical either way. */
-    GB_INPUT_P3_REPR = 2
+    GB_INPUT_P3_REPR = 2,
+    /* gb_prove_salted*, gb_prove_partition, gb_prove_inputs only: `salts` is a HOST pointer to 32 seed bytes, whatever memory space
+     * the witness is in, and the library generates the salt columns on the device (see gb_prove_salted, gb_random_elements) */
+    GB_SALTS_FROM_SEED = 4
 };
 
 #define GB_SALT_SIZE 4 /* fri/oracle.rs:25 */
+#define GB_SEED_SIZE 32
+/* nonce[0] of the streams the library itself draws from a seed (gb_random_elements); callers' own streams use other values */
+#define GB_STREAM_SALTS 1    /* (1, s, j): salt column j of commitment s (0 wires, 1 Zs / partial products, 2 quotient) */
+#define GB_STREAM_BLINDING 2 /* (2, 0, 0): the values of a circuit's blinding rows, in the order the builder created their targets */
 
 /* ---- context ------------------------------------------------------------------------------- */
 /* One context = one HIP stream (+ a copy stream) and one proving thread.  Several contexts of one process prove concurrently -
@@ -370,8 +377,26 @@ gb_status gb_circuit_drop_retry(gb_circuit* c);
  * products and quotient commitments).  salts: [3][GB_SALT_SIZE][N = 2^(degree_bits + rate_bits)] canonical elements in
  * LDE-point order - the columns the reference draws with F::rand_vec (fri/oracle.rs:144-148) - for those three commitments,
  * in the same memory space as `witness` (flags); a host input for the same reason the PublicInputGate's random wires are
- * (determinism contract: same inputs, same proof bytes).  The circuit's blinding rows (circuit_builder.rs:935-975
- * blind_and_pad) are the builder's business and part of `witness`. */
+ * (determinism contract: same inputs, same proof bytes).
+ *
+ * With GB_SALTS_FROM_SEED in `flags` the randomness is a function of a seed instead: `salts` is a HOST pointer to GB_SEED_SIZE
+ * bytes, whatever memory space the witness is in, and salt element [s][j][t] is element t of the stream (seed, (GB_STREAM_SALTS,
+ * s, j)) of gb_random_elements - s the commitment (0 wires, 1 Zs / partial products, 2 quotient), j the salt column, t the
+ * LDE-point index: the [3][GB_SALT_SIZE][N] layout above, and the proof bytes are those of the same call with that matrix.  The
+ * library generates the four columns of a commitment on the device just before the commitment consumes them, into one block of
+ * GB_SALT_SIZE * N elements that the three commitments share (256 MiB at 2^20 Goldilocks rows and rate 3, against the 768 MiB a
+ * salt matrix occupies on the host and again on the device); nothing crosses the bus.  The contract: ONE SEED PER PROOF.  The
+ * library draws no entropy of its own - the seed is the caller's, from the operating system's generator; a seed used for two
+ * different witnesses gives both proofs the same salts and voids the hiding of both.  The flag on a circuit that is not
+ * zero-knowledge is the error salts on such a circuit are; the flag with salts = NULL (the entry points without a salts argument
+ * included) is GB_ERR_INVALID; without the flag nothing changes.  It is accepted by gb_prove_salted, gb_prove_salted_cols,
+ * gb_prove_partition and gb_prove_inputs.  gb_commit_* take no seed: a caller composes gb_random_elements(.., GB_INPUT_DEVICE, buf)
+ * with their device `salts` argument.
+ *
+ * Salting alone is not zero-knowledge: the circuit needs the blinding rows of CircuitBuilder::blind (circuit_builder.rs:879-980)
+ * too - openings at zeta and g zeta and the FRI queries otherwise still leak the witness polynomials.  Those rows are the
+ * builder's business and part of `witness`; the Python builder mirror adds them under a zero-knowledge config and fills them from
+ * the stream (seed, (GB_STREAM_BLINDING, 0, 0)). */
 gb_status gb_prove_salted(gb_circuit* c, const void* witness, uint32_t flags, const uint64_t* public_inputs,
                           size_t num_public_inputs, const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len);
 gb_status gb_prove_salted_cols(gb_circuit* c, const void* const* wire_cols, uint32_t flags, const uint64_t* public_inputs,
@@ -396,7 +421,8 @@ gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative
                                    const uint64_t* public_input_targets, size_t num_public_inputs);
 /* gb_prove / gb_prove_salted from the partition witness: values[num_targets], entry i = partition_witness.values[i]
  * .unwrap_or(ZERO), canonical words or with GB_INPUT_P3_REPR the field types' in-memory words.  A HOST pointer:
- * GB_INPUT_DEVICE is GB_ERR_INVALID.  salts: NULL unless the circuit is zero-knowledge, otherwise as for gb_prove_salted (host).
+ * GB_INPUT_DEVICE is GB_ERR_INVALID.  salts: NULL unless the circuit is zero-knowledge, otherwise as for gb_prove_salted (host) -
+ * the [3][GB_SALT_SIZE][N] matrix or, with GB_SALTS_FROM_SEED in `flags`, the GB_SEED_SIZE seed bytes.
  * The public inputs are read from `values` through the map (get_targets, prover.rs:177).  Result, errors and proof bytes are those
  * of gb_prove / gb_prove_salted on the matrix full_witness() would build - GB_ERR_PERM_ARG_ZERO included; a value >= p in an
  * entry that a wire cell or a public input reads is GB_ERR_INVALID ("non-canonical witness element"), entries nothing reads are
@@ -575,7 +601,8 @@ gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_ou
 gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_t flags, void* values_dev_out);
 /* prove(): upload the inputs, run the generators (timing scope "run generators"), k_expand_partition straight from the generated
  * values ("compute full witness" is now the expansion alone), then the device-witness path of gb_prove unchanged.  The public
- * inputs are read from the generated values, in the same read-back as the error word.  salts as for gb_prove_partition.  The
+ * inputs are read from the generated values, in the same read-back as the error word.  salts as for gb_prove_partition (the
+ * matrix, or the seed with GB_SALTS_FROM_SEED).  The
  * proof bytes are those of gb_prove_partition on the same values; errors are gb_generate_partition's and gb_prove's. */
 gb_status gb_prove_inputs(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
                           size_t proof_cap, size_t* proof_len);
@@ -893,6 +920,21 @@ gb_status gb_merkle_tree_cap(gb_batch* tree, void* out);
 gb_status gb_merkle_tree_leaf(gb_batch* tree, uint64_t leaf_index, void* row, void* siblings, uint32_t* nsib);
 /* .digests in the reference's layout (:50-58): out[2 * (2^log_leaves - 2^cap_height)][H] */
 gb_status gb_merkle_tree_digests(gb_batch* tree, void* out);
+
+/* ---- field elements from a seed ---------------------------------------------------------------------------------------------
+ * A stream is (seed[GB_SEED_SIZE], nonce[3]).  Element e of it, for e >> 2 < 2^32: the ChaCha20 block (RFC 8439 2.3: 20 rounds,
+ * the "expand 32-byte k" constants) with words 4-11 the seed as eight little-endian words, word 12 the counter e >> 2 and words
+ * 13-15 nonce[0..2]; of its 64 serialized bytes, bytes 16 (e & 3) .. 16 (e & 3) + 15 as a little-endian 128-bit integer x; the
+ * element is x mod p, canonical.  Four elements per block in both fields, no rejection - position e depends on no other - and a
+ * bias below 2^-64 (Goldilocks) / 2^-97 (BabyBear).  nonce[0] = GB_STREAM_SALTS and GB_STREAM_BLINDING are the library's own
+ * streams (gb_prove_salted with GB_SALTS_FROM_SEED; the builder's blinding rows).
+ * Writes elements first_element .. first_element + count - 1 as canonical words of the field's width (u64 / u32) to `out`: host
+ * memory, or with flags = GB_INPUT_DEVICE a 16-byte-aligned device buffer of the caller, written on the context's stream - ready
+ * as the device `salts` of gb_commit_*.  The elements are computed on the device either way.  GB_ERR_INVALID: seed, nonce or out
+ * NULL; a range whose last block index does not fit 32 bits (first_element + count > 2^34); an unknown field; other flag bits; a
+ * misaligned device destination. */
+gb_status gb_random_elements(gb_ctx* ctx, uint32_t field, const uint8_t* seed, const uint32_t* nonce, uint64_t first_element,
+                             uint64_t count, uint32_t flags, void* out);
 
 /* ---- bare kernels (parity tests and microbenchmarks) ---------------------------------------- */
 /* `count` Poseidon-12 (GL) / Poseidon2-16 (BB) permutations: in/out [count][width], host memory.

@@ -30,6 +30,10 @@ pub const GB_GOLDILOCKS: u32 = 0;
 pub const GB_BABYBEAR: u32 = 1;
 pub const GB_INPUT_HOST: u32 = 0;
 pub const GB_INPUT_P3_REPR: u32 = 2;
+pub const GB_SALTS_FROM_SEED: u32 = 4;
+pub const GB_SEED_SIZE: usize = 32;
+pub const GB_STREAM_SALTS: u32 = 1;
+pub const GB_STREAM_BLINDING: u32 = 2;
 pub const GB_MAX_FRI_LAYERS: usize = 32;
 pub const GB_GEN_ARITHMETIC: u32 = 0;
 pub const GB_GEN_ARITHMETIC_EXTENSION: u32 = 1;
@@ -354,6 +358,8 @@ extern "C" {
     fn gb_circuit_drop_retry(c: *mut gb_circuit) -> i32;
     fn gb_prove_salted(c: *mut gb_circuit, witness: *const c_void, flags: u32, public_inputs: *const u64, num_public_inputs: usize,
                        salts: *const c_void, proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> i32;
+    fn gb_random_elements(ctx: *mut gb_ctx, field: u32, seed: *const u8, nonce: *const u32, first_element: u64, count: u64, flags: u32,
+                          out: *mut c_void) -> i32;
     fn gb_verifier_create(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32, k_is: *const c_void,
                           constants_sigmas_cap: *const c_void, circuit_digest: *const c_void, out: *mut *mut gb_circuit) -> i32;
     fn gb_verifier_create_programs(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
@@ -504,6 +510,18 @@ pub enum Transform {
     Lde,
 }
 impl GpuContext {
+    /// Elements `first .. first + count` of the keyed stream (seed, nonce) as canonical words (`gb_random_elements`): ChaCha20
+    /// blocks under `seed` with counter e >> 2 and the three nonce words, each 128-bit quarter reduced mod p; computed on the device.
+    pub fn random_elements<W: Copy + Default>(&self, seed: &[u8; GB_SEED_SIZE], nonce: [u32; 3], first: u64, count: usize)
+                                              -> Result<Vec<W>, GpuError> {
+        let mut out = vec![W::default(); count.max(1)];
+        check(self.0, unsafe {
+            gb_random_elements(self.0, field_tag::<W>(), seed.as_ptr(), nonce.as_ptr(), first, count as u64, GB_INPUT_HOST,
+                               out.as_mut_ptr() as *mut c_void)
+        })?;
+        out.truncate(count);
+        Ok(out)
+    }
     fn poly_shape<W>(len: usize, num_polys: usize, ext: bool) -> Result<u32, GpuError> {
         let d = if !ext { 1 } else if std::mem::size_of::<W>() == 8 { 2 } else { 4 };
         if num_polys == 0 || len % (num_polys * d) != 0 || !(len / (num_polys * d)).is_power_of_two() {
@@ -936,6 +954,24 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         let st = unsafe {
             gb_prove_salted(self.handle, witness.as_ptr() as *const c_void, GB_INPUT_HOST, public_inputs.as_ptr(), public_inputs.len(),
                             salts.as_ptr() as *const c_void, buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
+        };
+        if st == GB_ERR_PERM_ARG_ZERO {
+            return Ok(ProveOutcome::PermArgZero);
+        }
+        check(self.ctx.0, st)?;
+        buf.truncate(len);
+        Ok(ProveOutcome::Proof(buf))
+    }
+    /// Zero-knowledge circuits, the salts from a seed (`GB_SALTS_FROM_SEED`): the library generates the salt columns on the device
+    /// from the 32 bytes - salt element [s][j][t] = element t of the stream (seed, (GB_STREAM_SALTS, s, j)) - and nothing but the
+    /// seed crosses the bus.  ONE SEED PER PROOF, from the operating system's generator: the library draws no entropy, and a seed
+    /// used for two different witnesses gives both proofs the same salts and voids the hiding of both.
+    pub fn prove_seeded(&self, witness: &[W], public_inputs: &[u64], seed: &[u8; GB_SEED_SIZE]) -> Result<ProveOutcome, GpuError> {
+        let mut buf = vec![0u8; 8 << 20];
+        let mut len = 0usize;
+        let st = unsafe {
+            gb_prove_salted(self.handle, witness.as_ptr() as *const c_void, GB_INPUT_HOST | GB_SALTS_FROM_SEED, public_inputs.as_ptr(),
+                            public_inputs.len(), seed.as_ptr() as *const c_void, buf.as_mut_ptr() as *mut c_void, buf.len(), &mut len)
         };
         if st == GB_ERR_PERM_ARG_ZERO {
             return Ok(ProveOutcome::PermArgZero);

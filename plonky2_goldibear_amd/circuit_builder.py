@@ -40,9 +40,10 @@ class CircuitConfig:
 
     def __init__(self, field=N.GB_GOLDILOCKS, num_wires=135, num_routed_wires=80, num_constants=2, num_challenges=2,
                  max_quotient_degree_factor=8, rate_bits=3, cap_height=4, proof_of_work_bits=16, num_query_rounds=28,
-                 arity_bits=4, final_poly_bits=5, security_bits=100, fri_reduction_strategy=None):
+                 arity_bits=4, final_poly_bits=5, security_bits=100, fri_reduction_strategy=None, zero_knowledge=False):
         """fri_reduction_strategy: None = FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (every stock
-        configuration); ("fixed", [bits..]) or ("min_size", max_arity_bits or None) as in fri/reduction_strategies.rs:11-25"""
+        configuration); ("fixed", [bits..]) or ("min_size", max_arity_bits or None) as in fri/reduction_strategies.rs:11-25.
+        zero_knowledge: build() adds the blinding rows of CircuitBuilder::blind and the proofs are salted (seed=)"""
         self.__dict__.update(locals())
         del self.__dict__["self"]
 
@@ -57,6 +58,16 @@ class CircuitConfig:
     def standard_recursion_config_gl(cls, **kw):
         """circuit_data.rs:102-116"""
         return cls(**kw)
+
+    @classmethod
+    def standard_recursion_zk_config_gl(cls, **kw):
+        """circuit_data.rs:175-180"""
+        return cls.standard_recursion_config_gl(**dict(kw, zero_knowledge=True))
+
+    @classmethod
+    def standard_recursion_zk_config_bb(cls, **kw):
+        """circuit_data.rs:181-186 (standard_recursion_config_bb is the narrow BabyBear config, :118-120)"""
+        return cls.recursion_config_bb_narrow(**dict(kw, zero_knowledge=True))
 
     @classmethod
     def recursion_config_bb_narrow(cls, **kw):
@@ -217,13 +228,15 @@ class _ConstantGenerator:
 class _RandomValueGenerator:
     deps = []
 
-    def __init__(self, target):
-        self.target = target
+    def __init__(self, target, blinding=False):
+        self.target, self.blinding = target, blinding   # blinding: a cell of CircuitBuilder.blind's rows (filled from a seed)
 
     def record(self, built):
         return None   # its target is an input: random values are the host's (determinism contract)
 
     def run(self, w, p):
+        if self.blinding and w.has(self.target):
+            return    # the value of the seed's stream is there already (BuiltCircuit._run_generators)
         w.set(self.target, w.random())
 
 
@@ -579,8 +592,8 @@ class _PartitionWitness:
 
 # --------------------------------------------------------------------------------------------- builder
 class CircuitBuilder:
-    """plonk/circuit_builder.rs:142-1409 (no lookups, no zero-knowledge blinding; base arithmetic goes through ArithmeticGate,
-    use_base_arithmetic_gate = true as in every stock configuration)."""
+    """plonk/circuit_builder.rs:142-1409 (no lookups; base arithmetic goes through ArithmeticGate, use_base_arithmetic_gate = true
+    as in every stock configuration).  Under a zero_knowledge config build() runs blind() before it pads."""
 
     def __init__(self, config):
         self.config, self.F = config, _Field(config.field)
@@ -1086,7 +1099,9 @@ class CircuitBuilder:
             self.connect(wire(gen.row, gen.wire_index), t)
             gen.constant = c
             self.generators.append(gen)
-        while len(self.gate_instances) & (len(self.gate_instances) - 1):   # blind_and_pad, zero_knowledge = false
+        if getattr(cfg, "zero_knowledge", False):                          # blind_and_pad (:924-932)
+            self.blind()
+        while len(self.gate_instances) & (len(self.gate_instances) - 1):
             self.add_gate(NoopGate())
         degree = len(self.gate_instances)
         degree_bits = degree.bit_length() - 1
@@ -1154,6 +1169,55 @@ class CircuitBuilder:
                             num_virtual_targets=self.virtual_target_index,
                             row_gates=[gates.index(g) for g, _ in self.gate_instances], generator_programs=generator_programs,
                             representative_map=representative_map)
+
+    # ---- zero-knowledge blinding (circuit_builder.rs:875-980)
+    def fri_reduction_arity_bits(self, degree_bits):
+        """self.fri_params(degree_bits).reduction_arity_bits (:855-859; hiding does not enter the list)"""
+        from . import fri_params
+        c = self.config
+        strategy = c.fri_reduction_strategy or ("constant", c.arity_bits, c.final_poly_bits)
+        return fri_params.reduction_arity_bits(strategy, degree_bits, c.rate_bits, c.cap_height, c.num_query_rounds)
+
+    def num_blinding_gates(self, degree_estimate):
+        """:879-898 -> (regular_poly_openings, z_openings): the polynomial values one opening reveals, for a degree estimate"""
+        D = self.F.ext_degree
+        arities = [1 << b for b in self.fri_reduction_arity_bits(degree_estimate.bit_length() - 1)]
+        total_fri_folding_points = sum(a - 1 for a in arities)
+        product = 1
+        for a in arities:
+            product *= a
+        final_poly_coeffs = degree_estimate // product
+        fri_openings = self.config.num_query_rounds * (1 + D * total_fri_folding_points + D * final_poly_coeffs)
+        return D + fri_openings, 2 * D + fri_openings   # zeta; zeta and g zeta
+
+    def blinding_counts(self):
+        """:903-922: the counts for the smallest power of two that holds the gates and their own blinding rows"""
+        num_gates = len(self.gate_instances)
+        degree_estimate = 1 << max(0, (num_gates - 1).bit_length())   # 1 << log2_ceil(num_gates)
+        while True:
+            regular_poly_openings, z_openings = self.num_blinding_gates(degree_estimate)
+            # one random element per opened value; Z takes two rows each, a copy between them
+            if num_gates + regular_poly_openings + 2 * z_openings <= degree_estimate:
+                return regular_poly_openings, z_openings
+            degree_estimate *= 2
+
+    def blind(self):
+        """:934-980: `regular` NoopGate rows with a random value on every wire, then `z` pairs of NoopGate rows with a random value
+        on every routed wire of the first and generate_copy to the same wire of the second (a CopyGenerator, as in the
+        reference: no copy constraint, so the sigma columns are those of the unblinded circuit's wiring)"""
+        regular_poly_openings, z_openings = self.blinding_counts()
+        cfg = self.config
+        for _ in range(regular_poly_openings):
+            row = self.add_gate(NoopGate())
+            for w in range(cfg.num_wires):
+                self.generators.append(_RandomValueGenerator(wire(row, w), blinding=True))
+        for _ in range(z_openings):
+            gate_1 = self.add_gate(NoopGate())
+            gate_2 = self.add_gate(NoopGate())
+            for w in range(cfg.num_routed_wires):
+                self.generators.append(_RandomValueGenerator(wire(gate_1, w), blinding=True))
+                self.generate_copy(wire(gate_1, w), wire(gate_2, w))
+        return regular_poly_openings, z_openings
 
     def _wiring_on_device(self, ctx, degree_bits, k_is):
         """the copy constraints as pairs of Target::index -> (sigma, representative map, find) from wiring.sigma_polys; `find`
@@ -1259,6 +1323,7 @@ class BuiltCircuit:
         self._generator_program_index = {tuple(pr.words): i for i, pr in enumerate(self.generator_programs)}
         self._inputs = None                 # set_generators: the targets whose values the host supplies per proof
         self._input_set = frozenset()
+        self._blinding_targets = self._blinding_split = None
         self.data = None
         if ctx is not None:
             from .prover import CircuitData
@@ -1269,14 +1334,34 @@ class BuiltCircuit:
                                     num_query_rounds=cfg.num_query_rounds, arity_bits=cfg.arity_bits,
                                     final_poly_bits=cfg.final_poly_bits, num_selectors=num_selectors, field=cfg.field,
                                     gates=gate_table, num_public_inputs=len(public_inputs),
+                                    zero_knowledge=bool(getattr(cfg, "zero_knowledge", False)),
                                     reduction_arity_bits=cfg.reduction_arity_bits(degree_bits), programs=programs)
 
-    def _run_generators(self, pw, rng=None):
-        """generate_partial_witness (iop/generator.rs:25-117) -> the partition witness: one value per copy class"""
+    @property
+    def blinding_targets(self):
+        """the random-value targets of the blinding rows (CircuitBuilder.blind), in creation order: with seed=, target i takes
+        element i of the stream (seed, (GB_STREAM_BLINDING, 0, 0))"""
+        if self._blinding_targets is None:
+            self._blinding_targets = [g.target for g in self.generators if isinstance(g, _RandomValueGenerator) and g.blinding]
+        return self._blinding_targets
+
+    def blinding_values(self, seed):
+        """the values of blinding_targets under `seed`: one call of random_elements on the circuit's context"""
+        if self.data is None:
+            raise ValueError("the circuit was built without a GPU context")
+        from .polynomial_batch import random_elements
+        return random_elements(self.data.ctx, self.config.field, seed, (N.GB_STREAM_BLINDING, 0, 0), 0, len(self.blinding_targets))
+
+    def _run_generators(self, pw, rng=None, seed=None):
+        """generate_partial_witness (iop/generator.rs:25-117) -> the partition witness: one value per copy class.  seed: the
+        blinding rows take their values from the seed's stream instead of `rng`"""
         p = self.F.p
         w = _PartitionWitness(self.find, p, rng or np.random.default_rng(0))
         for t, v in pw.values.items():
             w.set(t, v)
+        if seed is not None and self.blinding_targets:
+            for t, v in zip(self.blinding_targets, self.blinding_values(seed).tolist()):
+                w.set(t, v)
         pending = list(self.generators)
         while pending:
             rest = []
@@ -1290,10 +1375,10 @@ class BuiltCircuit:
             pending = rest
         return w
 
-    def generate_witness(self, pw, rng=None):
+    def generate_witness(self, pw, rng=None, seed=None):
         """generate_partial_witness + full_witness (iop/generator.rs:25-117, iop/witness.rs:359-371)
         -> (wire_values [num_wires][n], public input values)"""
-        w = self._run_generators(pw, rng)
+        w = self._run_generators(pw, rng, seed)
         # full_witness: every wire carries the value of its copy class; unset wires are zero
         wires = np.zeros((self.config.num_wires, 1 << self.degree_bits), dtype=self.F.dtype)
         for rep, v in w.v.items():
@@ -1330,28 +1415,30 @@ class BuiltCircuit:
     def public_input_targets(self):
         return np.array([self.target_index(t) for t in self.public_inputs], dtype=np.uint64)
 
-    def generate_partition_witness(self, pw, rng=None):
+    def generate_partition_witness(self, pw, rng=None, seed=None):
         """generate_partial_witness (iop/generator.rs:25-117) -> PartitionWitness.values as a dense array, one entry per target:
         the class's value at its representative, zero everywhere else (unwrap_or(ZERO)).  No expansion: full_witness() is
         gb_prove_partition's first step."""
-        w = self._run_generators(pw, rng)
+        w = self._run_generators(pw, rng, seed)
         values = np.zeros(self.num_targets, dtype=self.F.dtype)
         for rep, v in w.v.items():
             values[self.target_index(rep)] = v
         return values
 
-    def prove(self, pw, rng=None):
+    def prove(self, pw, rng=None, seed=None):
+        """seed (32 bytes; a zero-knowledge circuit needs one, and one per proof): the blinding rows' values and the salts of the
+        three commitments are the seed's streams (include/goldibear_gpu.h: GB_STREAM_BLINDING, GB_STREAM_SALTS)"""
         if self.data is None:
             raise ValueError("the circuit was built without a GPU context")
         if not self._partition_set:
             self.data.set_partition(self.representative_map, self.public_input_targets)
             self._partition_set = True
-        values = self.generate_partition_witness(pw, rng)
+        values = self.generate_partition_witness(pw, rng, seed)
         col_row = rep = None
         if self.random_wire:
             col_row = (self.random_wire[1], self.random_wire[0])
             rep = self.representative_map[self.target_index(wire(*self.random_wire))]
-        return self.data.prove_partition(values, representative=rep, random_wire=col_row, rng=rng)
+        return self.data.prove_partition(values, representative=rep, random_wire=col_row, rng=rng, seed=seed)
 
     # ---- prove() from the inputs alone: the generators run on the device (include/goldibear_gpu.h gb_circuit_set_generators)
     @property
@@ -1395,17 +1482,27 @@ class BuiltCircuit:
         self.data.set_generators(self.generator_records(), [self.target_index(t) for t in input_targets], self.constants_columns)
         self._input_targets = list(input_targets)
 
-    def input_values(self, pw, rng=None):
+    def input_values(self, pw, rng=None, seed=None):
         """the per-proof inputs in the order of set_generators' input_targets: the partial witness, and for the random-value
-        targets the values the mirror's RandomValueGenerators would draw from `rng`"""
+        targets the values the mirror's RandomValueGenerators would draw from `rng` - except, with seed=, the blinding rows':
+        those are the seed's stream (blinding_values), placed in one indexed assignment"""
         rng = rng or np.random.default_rng(0)
         extra = [t for t in pw.values if t not in self._input_set]
         if extra:
             raise ValueError("the partial witness sets %d targets that are no inputs of the schedule (first: %r): call "
                              "set_generators again with these targets" % (len(extra), extra[0]))
-        drawn = {t: int(rng.integers(0, self.F.p, dtype=np.uint64)) for t in self.random_targets}
+        blind = self._blinding_inputs()
+        drawn = {g.target: int(rng.integers(0, self.F.p, dtype=np.uint64)) for g in self.generators
+                 if isinstance(g, _RandomValueGenerator) and not g.blinding} if blind is not None else \
+                {t: int(rng.integers(0, self.F.p, dtype=np.uint64)) for t in self.random_targets}
         out = np.zeros(len(self._input_targets), dtype=self.F.dtype)
-        for i, t in enumerate(self._input_targets):
+        others = enumerate(self._input_targets)
+        if blind is not None:
+            positions, ordinals, others = blind
+            vals = self.blinding_values(seed) if seed is not None else \
+                rng.integers(0, self.F.p, size=len(self.blinding_targets), dtype=np.uint64).astype(self.F.dtype)
+            out[positions] = vals[ordinals]
+        for i, t in others:
             if t in pw.values:
                 out[i] = pw.values[t] % self.F.p
             elif t in drawn:
@@ -1414,21 +1511,34 @@ class BuiltCircuit:
                 raise ValueError("the partial witness has no value for input target %r of the schedule" % (t,))
         return out
 
-    def generate_partition_device(self, pw, rng=None):
+    def _blinding_inputs(self):
+        """(positions among the schedule's inputs, ordinals among blinding_targets, the (position, target) of every other input)
+        of the blinding targets that are inputs and that the partial witness does not set - None for a circuit without blinding
+        rows; computed once per set_generators"""
+        if not self.blinding_targets:
+            return None
+        if self._blinding_split is None:
+            ordinal = {t: k for k, t in enumerate(self.blinding_targets)}
+            hit = [(i, ordinal[t]) for i, t in enumerate(self._input_targets) if t in ordinal]
+            others = [(i, t) for i, t in enumerate(self._input_targets) if t not in ordinal]
+            self._blinding_split = (np.array([i for i, _ in hit], dtype=np.int64), np.array([k for _, k in hit], dtype=np.int64), others)
+        return self._blinding_split
+
+    def generate_partition_device(self, pw, rng=None, seed=None):
         """generate_partition_witness on the device -> PartitionWitness.values as a dense array, one entry per target"""
         if self._input_targets is None:
             self.set_generators(pw=pw)
-        got = self.data.generate_partition(self.input_values(pw, rng))
+        got = self.data.generate_partition(self.input_values(pw, rng, seed))
         values = np.zeros(self.num_targets, dtype=self.F.dtype)
         values[self.data.generator_classes().astype(np.int64)] = got
         return values
 
-    def prove_inputs(self, pw, rng=None):
+    def prove_inputs(self, pw, rng=None, seed=None):
         """prove() (plonk/prover.rs:136-226): the generators, full_witness() and the proof on the device, with the reference's
-        retry loop - after InvZeroPermArg the random wire's input is drawn again"""
+        retry loop - after InvZeroPermArg the random wire's input is drawn again.  seed: as for prove()"""
         if self._input_targets is None:
             self.set_generators(pw=pw)
-        values = self.input_values(pw, rng)
+        values = self.input_values(pw, rng, seed)
         data = self.data
         data.perm_arg_retries = 0
         for attempt in range(data.MAX_PERM_ARG_RETRIES):
@@ -1441,9 +1551,9 @@ class BuiltCircuit:
                 rng = rng or np.random.default_rng()
                 values[self._input_targets.index(t)] = int(rng.integers(0, self.F.p, dtype=np.uint64))
                 data.perm_arg_retries = attempt
-                retry = (self.random_wire[1], self.random_wire[0])
+                retry = (self.random_wire[1], self.random_wire[0]) if seed is None else None   # (salted: the full computation)
             try:
-                return data.prove_inputs_once(values, retry_wire=retry)
+                return data.prove_inputs_once(values, retry_wire=retry, seed=seed)
             except N.PermArgZeroError:
                 if not self.random_wire:
                     data.drop_retry()
@@ -1452,7 +1562,7 @@ class BuiltCircuit:
         raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
 
     # ---- does the witness these generators make satisfy the circuit?  (include/goldibear_gpu.h gb_check_partition / gb_check_inputs)
-    def check(self, pw, rng=None, max_violations=16):
+    def check(self, pw, rng=None, max_violations=16, seed=None):
         """the host generators as in prove(), the expansion and the check on the device -> (violations, result); the violations
         are native.Violation objects (describe(self) names the gate), an empty list means satisfied"""
         if self.data is None:
@@ -1460,14 +1570,14 @@ class BuiltCircuit:
         if not self._partition_set:
             self.data.set_partition(self.representative_map, self.public_input_targets)
             self._partition_set = True
-        return self.data.check_partition(self.generate_partition_witness(pw, rng), max_violations=max_violations)
+        return self.data.check_partition(self.generate_partition_witness(pw, rng, seed), max_violations=max_violations)
 
-    def check_inputs(self, pw, rng=None, max_violations=16):
+    def check_inputs(self, pw, rng=None, max_violations=16, seed=None):
         """the device generators as in prove_inputs(), then the check: what a generator program that disagrees with its gate
         program breaks, by row, gate and constraint"""
         if self._input_targets is None:
             self.set_generators(pw=pw)
-        return self.data.check_inputs(self.input_values(pw, rng), max_violations=max_violations)
+        return self.data.check_inputs(self.input_values(pw, rng, seed), max_violations=max_violations)
 
     # ---- the copy constraints from sigma alone (include/goldibear_gpu.h gb_circuit_decode_sigmas / gb_circuit_copy_classes)
     def decode_sigmas(self):
@@ -1491,6 +1601,7 @@ class BuiltCircuit:
     def _input_targets(self, targets):
         self._inputs = None if targets is None else list(targets)
         self._input_set = frozenset(self._inputs or ())
+        self._blinding_split = None
 
     def verify(self, proof):
         return self.data.verify(proof)

@@ -522,6 +522,10 @@ gb_status cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, typename F::T shift,
 // internal flag (not part of the C ABI): device input already in the field's device form (BabyBear: Montgomery)
 static constexpr uint32_t GB_INPUT_DEVICE_FORM = 0x100;
 static constexpr uint32_t GB_PUBLIC_INPUT_FLAGS = GB_INPUT_DEVICE | GB_INPUT_P3_REPR;   // what a caller may pass
+// ... and what the prove entry points with a `salts` argument take besides: the salts are a seed (prover_host.inc: prove())
+static constexpr uint32_t GB_PROVE_FLAGS = GB_PUBLIC_INPUT_FLAGS | GB_SALTS_FROM_SEED;
+// internal flag: `salts` of commit() is a canonical device block even where `cols` is host memory (the seeded salts of prove())
+static constexpr uint32_t GB_SALTS_DEVICE = 0x200;
 
 // A matrix of input columns as the caller holds it: one contiguous [ncols][n] block (`base`), or ncols separately allocated
 // columns (`ptrs`) - the reference's Vec<PolynomialValues<F>> (fri/oracle.rs:68-75) and MatrixWitness.wire_values: Vec<Vec<F>>
@@ -1026,7 +1030,7 @@ gb_status commit(gb_ctx* ctx, ColSrc cols, size_t ncols, uint32_t log_n, uint32_
             // salt columns arrive in LDE-point order (like lde_values' extra columns, oracle.rs:144-148)
             // and are stored, like everything else, in leaf order: leaf j <- point bitrev(j)
             const T* sdev = static_cast<const T*>(salts);
-            if (!dev_in) {
+            if (!dev_in && !(flags & GB_SALTS_DEVICE)) {
                 T* sh;
                 if ((s = scratch(0, salt_bytes, &sh))) return cleanup(s);
                 if (hipMemcpyAsync(sh, salts, salt_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1460,6 +1464,40 @@ gb_status gb_permute(gb_ctx* ctx, uint32_t field, const void* in, void* out, uin
 } GB_CATCH(ctx)
 
 }  // extern "C"
+
+// elements first_element .. first_element + count - 1 of the stream (seed, nonce) (random_stream.hpp), generated on the device
+template <class F>
+static gb_status random_elements_entry(gb_ctx* ctx, const gbk::rnd::Key& key, uint64_t first, uint64_t count, uint32_t flags, void* out) {
+    typedef typename F::T T;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    T* dst = static_cast<T*>(out);
+    const size_t bytes = count * sizeof(T);
+    if (!(flags & GB_INPUT_DEVICE)) {
+        if (gb_status s = ensure(ctx, ctx->scratch, bytes)) return s;
+        dst = static_cast<T*>(ctx->scratch.p);
+    }
+    if (!gbk::random_elements<F>(key, first, count, 1, dst, 0, ctx->stream)) return fail(ctx, GB_ERR_HIP, "launch of k_random_elements failed");
+    if (!(flags & GB_INPUT_DEVICE)) {
+        HIP_TRY(ctx, hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return GB_OK;
+}
+
+gb_status gb_random_elements(gb_ctx* ctx, uint32_t field, const uint8_t* seed, const uint32_t* nonce, uint64_t first_element,
+                             uint64_t count, uint32_t flags, void* out) try {
+    if (!ctx || !seed || !nonce || !out) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if (field != GB_GOLDILOCKS && field != GB_BABYBEAR) return fail(ctx, GB_ERR_INVALID, "unknown field tag");
+    if (flags & ~(uint32_t)GB_INPUT_DEVICE) return fail(ctx, GB_ERR_INVALID, "gb_random_elements: flags other than GB_INPUT_DEVICE");
+    if (!gbk::rnd::range_ok(first_element, count))
+        return fail(ctx, GB_ERR_INVALID, "gb_random_elements: the range ends past element 2^34 (the block counter has 32 bits)");
+    if ((flags & GB_INPUT_DEVICE) && (reinterpret_cast<uintptr_t>(out) & 15))
+        return fail(ctx, GB_ERR_INVALID, "gb_random_elements: the device destination is not 16-byte aligned");
+    if (!count) return GB_OK;
+    const gbk::rnd::Key key = gbk::rnd::make_key(seed, nonce);
+    return field == GB_GOLDILOCKS ? random_elements_entry<GlF>(ctx, key, first_element, count, flags, out)
+                                  : random_elements_entry<BbF>(ctx, key, first_element, count, flags, out);
+} GB_CATCH(ctx)
 
 #include "poly_host.inc"
 #include "prover_host.inc"

@@ -11,6 +11,7 @@
 #include "gate_set.hpp"
 #include "generator_ops.hpp"
 #include "challenge_slices.hpp"
+#include "random_stream.hpp"
 #include "sigma_decode.hpp"
 #include "wiring.hpp"
 
@@ -118,6 +119,10 @@ void bitrev_copy(const typename F::T* src, typename F::T* dst, u32 bits, size_t 
 // any word -> the residue below p, in place (GB_INPUT_P3_REPR: the words of the reference's field types from a host)
 template <class F>
 void reduce_words(typename F::T* p, size_t count, hipStream_t stream);
+// the keyed element stream (kernels_random.hip, random_stream.hpp): elements first .. first + count - 1 of the num_streams streams
+// (key.seed, (nonce[0], nonce[1], nonce[2] + y)), stream y to out + y * stream_stride, canonical words; false when a launch failed
+template <class F>
+bool random_elements(const rnd::Key& key, u64 first, u64 count, u32 num_streams, typename F::T* out, u64 stream_stride, hipStream_t stream);
 // PartitionWitness::full_witness (kernels_partition.hip, partition_expand.hpp): out[col][row] = staged[slots[row][col]] - slots
 // [2^log_n][num_wires] row-major, out [num_wires][2^log_n]; words are copied as they are
 template <class F>

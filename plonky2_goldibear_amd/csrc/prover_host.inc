@@ -1095,6 +1095,8 @@ template <class F>
 gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs,
                 const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
     typedef typename F::T T;
+    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // `salts` is 32 seed bytes on the host (checked non-null by the entries)
+    flags &= ~(uint32_t)GB_SALTS_FROM_SEED;
     typedef typename F::E E;
     typedef Host<F> HF;
     constexpr u32 D = F::D, H = F::H;
@@ -1134,9 +1136,27 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
     // zero-knowledge (config.zero_knowledge && PlonkOracle::*.blinding, prover.rs:267,334,382): the wires, Zs and quotient
     // leaves end in SALT_SIZE salt elements.  salts = [3][SALT_SIZE][N] canonical values in LDE-point order, in the same
     // memory space as the witness; the Zs / quotient commitments run on device data, so host salts are staged once.
+    // GB_SALTS_FROM_SEED: column j of commitment s is the stream (seed, (GB_STREAM_SALTS, s, j)), elements 0 .. N - 1, generated
+    // just before the commitment that consumes it into ONE block of SALT_SIZE x N elements the three commitments share - the
+    // stream orders commitment s's bitrev_copy out of the block before the generator of commitment s + 1 writes it.
     const T* salt_w = static_cast<const T*>(salts);
     const T *salt_z = nullptr, *salt_q = nullptr;
-    if (salts) {
+    gbk::rnd::Key salt_key{};
+    auto seeded_salts = [&](u32 commitment) -> gb_status {   // no-op without the flag
+        if (!seeded) return GB_OK;
+        salt_key.nonce[1] = commitment;
+        if (!gbk::random_elements<F>(salt_key, 0, N, GB_SALT_SIZE, const_cast<T*>(salt_w), N, st))
+            return fail(ctx, GB_ERR_HIP, "launch of k_random_elements failed");
+        return GB_OK;
+    };
+    const uint32_t wires_flags = flags | (seeded ? GB_SALTS_DEVICE : 0u);
+    if (seeded) {
+        const u32 nonce[3] = {gbk::rnd::STREAM_SALTS, 0, 0};
+        salt_key = gbk::rnd::make_key(static_cast<const uint8_t*>(salts), nonce);
+        T* block = tmp.get<T>((size_t)GB_SALT_SIZE * N);
+        if (!block) return fail(ctx, GB_ERR_OOM, "salt block");
+        salt_w = salt_z = salt_q = block;
+    } else if (salts) {
         const size_t per = (size_t)GB_SALT_SIZE * N;
         if (flags & GB_INPUT_DEVICE) {
             salt_z = salt_w + per;
@@ -1251,7 +1271,8 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             wit_vals = (T*)p;
         }
         Scope sc(ctx, "compute wires commitment");
-        if ((s = commit<F>(ctx, witness, nw, lg, r, capH, salt_w, flags, false, &wires, wit_vals, salts ? nullptr : &seg, &wit_mont_cols)))
+        if ((s = seeded_salts(0))) return s;
+        if ((s = commit<F>(ctx, witness, nw, lg, r, capH, salt_w, wires_flags, false, &wires, wit_vals, salts ? nullptr : &seg, &wit_mont_cols)))
             return (flags & GB_INPUT_DEVICE) ? s : finish_host_commit(ctx, s, nullptr);   // the witness is the caller's again
     }
     // the Z computation needs the routed wire VALUES on the device (device form) as well
@@ -1304,6 +1325,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             s = fail(ctx, GB_ERR_PERM_ARG_ZERO, "InvZeroPermArg (armed by gb_test_arm_perm_arg_failure)");
         }
         if (s) return failed(s);
+        if ((s = seeded_salts(1))) return s;
         if ((s = commit<F>(ctx, zs_vals, nzs, lg, r, capH, salt_z, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, false, &zs))) {
             if (defer) (void)hipMemsetAsync(c->perm_err, 0, 4, st);   // nobody will ask the deferred question: leave the word zero
             return s;
@@ -1324,6 +1346,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         Scope sc(ctx, "compute quotient polys");
         T* chunks = nullptr;
         if ((s = stage_quotient_polys<F>(c, tmp, wires, zs, pi_hash, betas_d, gammas_d, alphas, &chunks))) return s;
+        if ((s = seeded_salts(2))) return s;
         if ((s = commit<F>(ctx, chunks, nq, lg, r, capH, salt_q, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, true, &quot))) return s;
     }
     if ((s = read_cap<F>(quot, cap))) return s;
@@ -1915,7 +1938,10 @@ static gb_status prove_partition(Circuit<F>* c, const void* values, uint32_t fla
     }
     // the proof proper: the device-witness path of prove().  Host salts go to the device with the witness.
     const T* salts_dev = nullptr;
-    if (salts) {
+    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // the seed goes to prove() as it is
+    if (seeded) {
+        salts_dev = static_cast<const T*>(salts);
+    } else if (salts) {
         const size_t count = (size_t)3 * GB_SALT_SIZE * N;
         T* sd = tmp.get<T>(count);
         if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
@@ -1924,7 +1950,8 @@ static gb_status prove_partition(Circuit<F>* c, const void* values, uint32_t fla
         if (p3) p3_to_canonical_dev<F>(sd, count, st);
         salts_dev = sd;
     }
-    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE, pis.data(), pis.size(), salts_dev, proof_out, proof_cap, proof_len, hint);
+    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE | (seeded ? GB_SALTS_FROM_SEED : 0u), pis.data(), pis.size(), salts_dev, proof_out,
+                 proof_cap, proof_len, hint);
     if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
         c->part.matrix = matrix.p;
         c->part.matrix_bytes = matrix.bytes;
@@ -2091,7 +2118,10 @@ static gb_status prove_inputs(Circuit<F>* c, const void* input_values, uint32_t 
         if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
     }
     const T* salts_dev = nullptr;
-    if (salts) {
+    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // the seed goes to prove() as it is
+    if (seeded) {
+        salts_dev = static_cast<const T*>(salts);
+    } else if (salts) {
         const size_t count = (size_t)3 * GB_SALT_SIZE * N;
         T* sd = tmp.get<T>(count);
         if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
@@ -2100,7 +2130,8 @@ static gb_status prove_inputs(Circuit<F>* c, const void* input_values, uint32_t 
         if (p3) p3_to_canonical_dev<F>(sd, count, st);
         salts_dev = sd;
     }
-    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE, pis.data(), pis.size(), salts_dev, proof_out, proof_cap, proof_len, hint);
+    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE | (seeded ? GB_SALTS_FROM_SEED : 0u), pis.data(), pis.size(), salts_dev, proof_out,
+                 proof_cap, proof_len, hint);
     if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
         c->part.matrix = matrix.p;
         c->part.matrix_bytes = matrix.bytes;
@@ -2332,7 +2363,8 @@ static gb_status prove_entry(gb_circuit* c, ColSrc witness, uint32_t flags, cons
     if (!c) return fail(nullptr, GB_ERR_INVALID, "null circuit");
     gb_ctx* ctx = c->ctx;
     if (!witness || !proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
-    if (flags & ~GB_PUBLIC_INPUT_FLAGS) return fail(ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if (flags & ~GB_PROVE_FLAGS) return fail(ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
     if (witness.ptrs && !c->verify_only)
         for (u32 w = 0; w < c->cfg.num_wires; w++)
             if (!witness.ptrs[w]) return fail(ctx, GB_ERR_INVALID, "null wire column pointer");
@@ -2458,10 +2490,10 @@ gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative
     return GB_OK;
 } GB_CATCH_CIRCUIT(c)
 
-static gb_status partition_guard(gb_circuit* c, const void* values, uint32_t flags) {
+static gb_status partition_guard(gb_circuit* c, const void* values, uint32_t flags, uint32_t allowed = GB_PUBLIC_INPUT_FLAGS) {
     if (gb_status s = stage_guard(c)) return s;
     if (!values) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    if (flags & ~GB_PUBLIC_INPUT_FLAGS) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if (flags & ~allowed) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
     if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the partition witness is a host object: GB_INPUT_DEVICE does not apply");
     if (!c->part.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_partition has not been called on this circuit");
     return GB_OK;
@@ -2469,9 +2501,10 @@ static gb_status partition_guard(gb_circuit* c, const void* values, uint32_t fla
 
 static gb_status prove_partition_entry(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out,
                                        size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
-    if (gb_status s = partition_guard(c, values, flags)) return s;
+    if (gb_status s = partition_guard(c, values, flags, GB_PROVE_FLAGS)) return s;
     gb_ctx* ctx = c->ctx;
     if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
     if (c->cfg.zero_knowledge && !salts)
         return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
     if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
@@ -2635,9 +2668,10 @@ static gb_status schedule_guard(gb_circuit* c) {   // a schedule is set
     if (!c->part.set || !c->gens.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_generators has not been called on this circuit");
     return GB_OK;
 }
-static gb_status generators_guard(gb_circuit* c, const void* input_values, uint32_t flags) {   // and these are inputs for it
+static gb_status generators_guard(gb_circuit* c, const void* input_values, uint32_t flags,
+                                  uint32_t allowed = GB_PUBLIC_INPUT_FLAGS) {   // and these are inputs for it
     if (gb_status s = stage_guard(c)) return s;
-    if (flags & ~GB_PUBLIC_INPUT_FLAGS) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
+    if (flags & ~allowed) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
     if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the inputs are a host object: GB_INPUT_DEVICE does not apply");
     if (gb_status s = schedule_guard(c)) return s;
     if (!input_values && !c->gens.sched.input_cls.empty()) return fail(c->ctx, GB_ERR_INVALID, "null argument");
@@ -2676,9 +2710,10 @@ gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_
 
 static gb_status prove_inputs_entry(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
                                     size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
-    if (gb_status s = generators_guard(c, input_values, flags)) return s;
+    if (gb_status s = generators_guard(c, input_values, flags, GB_PROVE_FLAGS)) return s;
     gb_ctx* ctx = c->ctx;
     if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
     if (c->cfg.zero_knowledge && !salts)
         return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
     if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");

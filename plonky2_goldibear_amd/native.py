@@ -22,7 +22,10 @@ GB_VIOLATION_GATE, GB_VIOLATION_SELECTOR, GB_VIOLATION_COPY = 1, 2, 3
 GB_GOLDILOCKS, GB_BABYBEAR = 0, 1
 GB_INPUT_HOST, GB_INPUT_DEVICE = 0, 1
 GB_INPUT_P3_REPR = 2   # host elements are the reference's field types as they lie in memory (p3 words), not canonical values
+GB_SALTS_FROM_SEED = 4   # gb_prove_salted* / gb_prove_partition / gb_prove_inputs: `salts` is a host pointer to 32 seed bytes
 GB_SALT_SIZE = 4
+GB_SEED_SIZE = 32
+GB_STREAM_SALTS, GB_STREAM_BLINDING = 1, 2   # nonce[0] of the library's own streams (gb_random_elements)
 
 _vp, _u32, _u64, _sz, _i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int32
 _pvp = C.POINTER(C.c_void_p)
@@ -65,6 +68,7 @@ SIGNATURES = {
     "gb_verifier_create": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _pvp]),
     "gb_pow_grind": (_i32, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "gb_permute": (_i32, [_vp, _u32, _vp, _vp, _u64]),
+    "gb_random_elements": (_i32, [_vp, _u32, C.POINTER(C.c_uint8), C.POINTER(_u32), _u64, _u64, _u32, _vp]),
     "gb_circuit_create": (_i32, [_vp, _vp, _vp, _vp, _u32, _pvp]),
     "gb_circuit_create_gates": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _u32, _pvp]),
     "gb_circuit_create_cols": (_i32, [_vp, _vp, _cols, _vp, _u32, _pvp]),

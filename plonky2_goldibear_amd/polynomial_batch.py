@@ -127,6 +127,37 @@ def _dtype(field):
     return np.uint64 if field == N.GB_GOLDILOCKS else np.uint32
 
 
+def random_elements(ctx, field, seed, nonce, first, count, device=False):
+    """gb_random_elements: elements first .. first + count - 1 of the stream (seed[32], nonce[3]) - the ChaCha20 block of RFC 8439
+    under `seed` with counter e >> 2 and nonce words `nonce`, its 128-bit quarter e & 3 reduced mod p (include/goldibear_gpu.h) -
+    computed on the device -> a numpy array of canonical words, or with device=True a torch device tensor of the same bit patterns
+    (int64 / int32), ready as the device `salts` of PolynomialBatch.from_values"""
+    if field not in (N.GB_GOLDILOCKS, N.GB_BABYBEAR):
+        raise N.ShapeError(N.GB_ERR_INVALID, "unknown field tag")
+    raw = bytes(seed)
+    if len(raw) != N.GB_SEED_SIZE:
+        raise N.ShapeError(N.GB_ERR_INVALID, "seed must be %d bytes, got %d" % (N.GB_SEED_SIZE, len(raw)))
+    nonce = [int(x) for x in nonce]
+    if len(nonce) != 3 or any(not 0 <= x < 1 << 32 for x in nonce):
+        raise N.ShapeError(N.GB_ERR_INVALID, "nonce must be three 32-bit words")
+    first, count = int(first), int(count)
+    if not (0 <= first < 1 << 64 and 0 <= count < 1 << 40):   # (what ends past element 2^34 is the library's refusal)
+        raise N.ShapeError(N.GB_ERR_INVALID, "first / count out of range")
+    sbuf = (C.c_uint8 * N.GB_SEED_SIZE).from_buffer_copy(raw)
+    nbuf = (C.c_uint32 * 3)(*nonce)
+    lib = N.load()
+    if not device:
+        out = np.empty(max(count, 1), dtype=_dtype(field))[:count]
+        N.check(lib.gb_random_elements(ctx.handle, field, sbuf, nbuf, first, count, N.GB_INPUT_HOST, out.ctypes.data), ctx.handle)
+        return out
+    import torch
+    out = torch.empty(max(count, 1), dtype=torch.int64 if field == N.GB_GOLDILOCKS else torch.int32, device="cuda:%d" % ctx.device)[:count]
+    torch.cuda.current_stream(out.device).synchronize()
+    N.check(lib.gb_random_elements(ctx.handle, field, sbuf, nbuf, first, count, N.GB_INPUT_DEVICE, out.data_ptr()), ctx.handle)
+    N.check(lib.gb_ctx_synchronize(ctx.handle), ctx.handle)
+    return out
+
+
 def _as_input(x, field=N.GB_GOLDILOCKS):
     """numpy array (host) or torch CUDA tensor (device, same-width integer bit pattern) -> (ptr, shape, flags, keepalive)"""
     dt = _dtype(field)

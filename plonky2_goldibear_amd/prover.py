@@ -157,14 +157,28 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
 
     MAX_PERM_ARG_RETRIES = 3  # plonk/prover.rs:183
 
-    def prove(self, witness, public_inputs=(), random_wire=None, rng=None, salts=None, p3_repr=False):
+    @staticmethod
+    def _seed_bytes(seed, salts):
+        """the 32 seed bytes of GB_SALTS_FROM_SEED as a buffer ctypes can point to (None without a seed)"""
+        if seed is None:
+            return None
+        if salts is not None:
+            raise N.ShapeError(N.GB_ERR_INVALID, "seed= and salts= are exclusive: the seed is what the salts are generated from")
+        raw = bytes(seed)
+        if len(raw) != N.GB_SEED_SIZE:
+            raise N.ShapeError(N.GB_ERR_INVALID, "seed must be %d bytes, got %d" % (N.GB_SEED_SIZE, len(raw)))
+        return C.create_string_buffer(raw, N.GB_SEED_SIZE)
+
+    def prove(self, witness, public_inputs=(), random_wire=None, rng=None, salts=None, p3_repr=False, seed=None):
         """prove_with_partition_witness (plonk/prover.rs:160-226): the retry loop around the proof proper.  When the
         permutation argument hits a zero denominator (ProverError::InvZeroPermArg - with a 31-bit field and 2^20 rows
         about one proof in five) the reference overwrites `random_wire` (circuit_builder.rs:1073-1075: the last wire of the
         PublicInputGate row, given here as (column, row)) with a fresh F::rand() and tries again, at most 3 attempts.
         `witness` is modified in place in that case, like the reference's `witness.wire_values`.  `witness`: the [num_wires][n]
         matrix, or MatrixWitness.wire_values as the reference holds it - a list of num_wires separately allocated columns
-        (gb_prove_cols).  p3_repr: host elements are the reference's in-memory words (GB_INPUT_P3_REPR)."""
+        (gb_prove_cols).  p3_repr: host elements are the reference's in-memory words (GB_INPUT_P3_REPR).  seed: 32 bytes the
+        library generates a zero-knowledge circuit's salts from, on the device (GB_SALTS_FROM_SEED) - one seed per proof."""
+        self._seed_bytes(seed, salts)
         self.perm_arg_retries = 0
         for attempt in range(self.MAX_PERM_ARG_RETRIES):
             if attempt > 0:
@@ -195,8 +209,8 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
             try:
                 # the second and third attempts differ from the failed one in the random wire only: gb_prove_retry rebuilds just
                 # that column of the wires commitment where the library kept the rest (no salts)
-                retry = (col, row) if attempt > 0 and salts is None else None
-                return self.prove_once(witness, public_inputs, salts, retry_wire=retry, p3_repr=p3_repr)
+                retry = (col, row) if attempt > 0 and salts is None and seed is None else None
+                return self.prove_once(witness, public_inputs, salts, retry_wire=retry, p3_repr=p3_repr, seed=seed)
             except N.PermArgZeroError:
                 if random_wire is None:   # no retry will follow: do not keep the failed attempt's commitment on the device
                     self.drop_retry()
@@ -214,10 +228,13 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         done, keeping what gb_prove_retry builds on - the only way to drive the retry path of a 64-bit field"""
         N.check(self._lib.gb_test_arm_perm_arg_failure(self.handle), self.ctx.handle)
 
-    def prove_once(self, witness, public_inputs=(), salts=None, retry_wire=None, p3_repr=False):
+    def prove_once(self, witness, public_inputs=(), salts=None, retry_wire=None, p3_repr=False, seed=None):
         """internal_prove_with_partition_witness (plonk/prover.rs:228-447); raises PermArgZeroError.  A circuit created with
         zero_knowledge=True takes `salts`: [3][4][N] canonical elements (the F::rand_vec columns of the wires / Zs / quotient
-        commitments, fri/oracle.rs:144-148), in the same memory space as the witness."""
+        commitments, fri/oracle.rs:144-148), in the same memory space as the witness - or `seed`: 32 bytes (host) from which the
+        library generates those columns on the device (GB_SALTS_FROM_SEED: element [s][j][t] = element t of the stream
+        (seed, (GB_STREAM_SALTS, s, j)) of random_elements)."""
+        sbuf = self._seed_bytes(seed, salts)
         cols = is_column_list(witness)
         ptr, shape, flags, keep = _as_columns(witness, self.field) if cols else _as_input(witness, self.field)
         lib, sfx = self._lib, "_cols" if cols else ""
@@ -231,7 +248,11 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
             self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
         n = C.c_size_t()
         pis_ptr = pis.ctypes.data if pis.size else None
-        if salts is None and retry_wire is not None:   # (wire, row): the one element re-drawn since the attempt that failed
+        if sbuf is not None:
+            st = getattr(lib, "gb_prove_salted" + sfx)(self.handle, ptr, flags | N.GB_SALTS_FROM_SEED, pis_ptr, pis.size,
+                                                       C.cast(sbuf, C.c_void_p), self._proof_buf.ctypes.data, self._proof_buf.size,
+                                                       C.byref(n))
+        elif salts is None and retry_wire is not None:   # (wire, row): the one element re-drawn since the attempt that failed
             st = getattr(lib, "gb_prove_retry" + sfx)(self.handle, ptr, flags, int(retry_wire[0]), int(retry_wire[1]), pis_ptr, pis.size,
                                                       self._proof_buf.ctypes.data, self._proof_buf.size, C.byref(n))
         elif salts is None:
@@ -266,14 +287,19 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
             raise N.ShapeError(N.GB_ERR_INVALID, "values must have one entry per target of the map given to set_partition")
         return v, (N.GB_INPUT_P3_REPR if p3_repr else N.GB_INPUT_HOST)
 
-    def prove_partition_once(self, values, salts=None, retry_wire=None, p3_repr=False):
-        """internal_prove_with_partition_witness from PartitionWitness.values (None as zero): full_witness() runs on the device"""
+    def prove_partition_once(self, values, salts=None, retry_wire=None, p3_repr=False, seed=None):
+        """internal_prove_with_partition_witness from PartitionWitness.values (None as zero): full_witness() runs on the device.
+        salts / seed as for prove_once (both host)."""
+        sbuf = self._seed_bytes(seed, salts)
         v, flags = self._partition_values(values, p3_repr)
         if self._proof_buf is None:
             self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
         n = C.c_size_t()
         out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
-        if salts is None and retry_wire is not None:
+        if sbuf is not None:
+            st = self._lib.gb_prove_partition(self.handle, v.ctypes.data, flags | N.GB_SALTS_FROM_SEED, C.cast(sbuf, C.c_void_p), out, cap,
+                                              C.byref(n))
+        elif salts is None and retry_wire is not None:
             st = self._lib.gb_prove_partition_retry(self.handle, v.ctypes.data, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap,
                                                     C.byref(n))
         else:
@@ -287,10 +313,11 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         N.check(st, self.ctx.handle)
         return self._proof_buf[: n.value].tobytes()
 
-    def prove_partition(self, values, representative=None, random_wire=None, rng=None, salts=None, p3_repr=False):
+    def prove_partition(self, values, representative=None, random_wire=None, rng=None, salts=None, p3_repr=False, seed=None):
         """prove_with_partition_witness (plonk/prover.rs:160-226) on the reference's own witness object: the retry loop of prove()
         over gb_prove_partition / gb_prove_partition_retry.  random_wire = (column, row) as for prove(); `representative` is the
         entry of `values` that holds it (representative_map[row * num_wires + column]), re-drawn in place after InvZeroPermArg."""
+        self._seed_bytes(seed, salts)
         self.perm_arg_retries = 0
         for attempt in range(self.MAX_PERM_ARG_RETRIES):
             if attempt > 0:
@@ -305,8 +332,8 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
                 values[int(representative)] = val
                 self.perm_arg_retries = attempt
             try:
-                retry = random_wire if attempt > 0 and salts is None else None
-                return self.prove_partition_once(values, salts, retry_wire=retry, p3_repr=p3_repr)
+                retry = random_wire if attempt > 0 and salts is None and seed is None else None
+                return self.prove_partition_once(values, salts, retry_wire=retry, p3_repr=p3_repr, seed=seed)
             except N.PermArgZeroError:
                 if random_wire is None:
                     self.drop_retry()
@@ -387,15 +414,19 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         N.check(self._lib.gb_ctx_synchronize(self.ctx.handle), self.ctx.handle)
         return out.cpu().numpy().view(self._dt)[:self.generators_info()["num_classes"]]
 
-    def prove_inputs_once(self, input_values, salts=None, retry_wire=None, p3_repr=False):
-        """prove() (plonk/prover.rs:136-158) from the inputs: the generators, full_witness() and the proof on the device"""
+    def prove_inputs_once(self, input_values, salts=None, retry_wire=None, p3_repr=False, seed=None):
+        """prove() (plonk/prover.rs:136-158) from the inputs: the generators, full_witness() and the proof on the device.
+        salts / seed as for prove_once (both host)."""
+        sbuf = self._seed_bytes(seed, salts)
         v, flags = self._input_values(input_values, p3_repr)
         if self._proof_buf is None:
             self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
         n = C.c_size_t()
         out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
         vp = v.ctypes.data if v.size else None
-        if salts is None and retry_wire is not None:
+        if sbuf is not None:
+            st = self._lib.gb_prove_inputs(self.handle, vp, flags | N.GB_SALTS_FROM_SEED, C.cast(sbuf, C.c_void_p), out, cap, C.byref(n))
+        elif salts is None and retry_wire is not None:
             st = self._lib.gb_prove_inputs_retry(self.handle, vp, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap, C.byref(n))
         else:
             sa = None
