@@ -93,7 +93,9 @@ gb_status gb_ctx_stream(gb_ctx* ctx, void** stream_out);
  *   "retry_verify"   1: gb_prove_retry first compares the caller's whole matrix with the copy the failed attempt kept and
  *                    returns GB_ERR_INVALID if they differ in more than witness[wire][row] (one read-back of the witness)
  *   "check_witness"  1: every gb_prove* that does the full computation checks its witness first (gb_check_witness, below) and
- *                    returns GB_ERR_UNSATISFIED instead of proof bytes that cannot verify; default 0: gb_prove* runs nothing new */
+ *                    returns GB_ERR_UNSATISFIED instead of proof bytes that cannot verify; default 0: gb_prove* runs nothing new
+ *   "verify_chunk_bytes"  gb_verify_batch: the most bytes (query rounds and per-proof records) staged and uploaded per chunk,
+ *                    4096 .. 2^30; default 8388608 (8 MiB; two page-locked slots of this size).  A chunk holds at least one proof */
 gb_status gb_ctx_set_option(gb_ctx* ctx, const char* key, int64_t value);
 
 /* ---- host memory ---------------------------------------------------------------------------
@@ -762,6 +764,47 @@ gb_status gb_wiring_sigmas(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, ui
  * malformed bytes. */
 #define GB_ERR_VERIFY 19
 gb_status gb_verify(gb_circuit* c, const void* proof, size_t proof_len);
+/* gb_verify of many proofs of ONE circuit at once, with the query rounds - the Merkle paths and the folding checks, ~96 % of a
+ * verification - checked on the device of `ctx`; the transcript, the vanishing identity and the proof of work stay on the host,
+ * split over the context's "copy_threads".  For every i, results[i].status is what gb_verify(c, proofs[i], proof_lens[i])
+ * returns and gb_verify_check_text(results[i].check) is the text it leaves in gb_last_error; of several failing checks the one
+ * gb_verify reaches first is named (parse errors, the vanishing identity, the proof of work, then per query round in order: the
+ * initial paths by oracle, each layer's consistency check and then its path, the final polynomial).
+ *   c       any handle gb_verify accepts, either field - a gb_verifier_create* object made with a NULL context included
+ *   ctx     the device; NULL, or a circuit that belongs to another context: GB_ERR_INVALID
+ *   flags   0 (anything else: GB_ERR_INVALID).  Compressed proofs are not taken: decompress or use gb_verify_compressed
+ *   results gb_verify_result[num_proofs], host
+ * Returns GB_OK: every proof verified; GB_ERR_VERIFY: the call completed, at least one proof did not verify (results says which -
+ * GB_ERR_INVALID proofs included); anything else: the call did not complete and results is unspecified.  num_proofs == 0: GB_OK.
+ * A proof whose query section does not have the circuit's shape (a Merkle path length byte that differs) is checked on the host;
+ * no device offset is derived from proof content.  The staged bytes per chunk are bounded by the context option
+ * "verify_chunk_bytes" (gb_ctx_set_option: 4096 .. 2^30, default 8388608 = 8 MiB per staging slot, two slots); a chunk holds at
+ * least one proof.  While a chunk's kernels run the host stage of the next chunk proceeds.
+ * Timing scopes: "verify batch: host stage" (the span on the stream during which the host stage of a chunk ran), "verify batch:
+ * upload", "verify batch: paths", "verify batch: queries". */
+#define GB_VCHECK_NONE 0
+#define GB_VCHECK_TRUNCATED 1          /* GB_ERR_INVALID: "proof bytes are truncated" */
+#define GB_VCHECK_NON_CANONICAL 2      /* GB_ERR_INVALID: a word >= p */
+#define GB_VCHECK_PI_IMPLAUSIBLE 3     /* GB_ERR_INVALID */
+#define GB_VCHECK_PI_COUNT 4           /* GB_ERR_INVALID: validate_proof_with_pis_shape */
+#define GB_VCHECK_TRAILING 5           /* GB_ERR_INVALID: "trailing bytes in proof" */
+#define GB_VCHECK_VANISHING 6          /* GB_ERR_VERIFY from here on, but for the two path lengths */
+#define GB_VCHECK_POW 7
+#define GB_VCHECK_INITIAL_PATH_LEN 8   /* GB_ERR_INVALID; query_round, index = oracle */
+#define GB_VCHECK_INITIAL_PATH 9       /* query_round, index = oracle */
+#define GB_VCHECK_CONSISTENCY 10       /* query_round, index = layer */
+#define GB_VCHECK_LAYER_PATH_LEN 11    /* GB_ERR_INVALID; query_round, index = layer */
+#define GB_VCHECK_LAYER_PATH 12        /* query_round, index = layer */
+#define GB_VCHECK_FINAL_POLY 13        /* query_round */
+typedef struct gb_verify_result {
+    uint32_t status;       /* GB_OK, GB_ERR_VERIFY or GB_ERR_INVALID: what gb_verify returns for this proof */
+    uint32_t check;        /* GB_VCHECK_*: the check gb_verify would name; 0 when status == GB_OK */
+    uint32_t query_round;  /* for the FRI query checks, else UINT32_MAX */
+    uint32_t index;        /* oracle index (initial paths) or layer index (consistency, layer path), else UINT32_MAX */
+} gb_verify_result;
+gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
+                          uint32_t flags, void* results /* gb_verify_result[num_proofs] */);
+const char* gb_verify_check_text(uint32_t check); /* "" for GB_VCHECK_NONE and for a value that is no check */
 /* Compressed proofs, on the host like the reference's (hash/path_compression.rs, fri/proof.rs:137-384, plonk/proof.rs:96-260):
  * gb_proof_compress = ProofWithPublicInputs::compress -> CompressedProofWithPublicInputs bytes (util/serialization/mod.rs:2168-2256:
  * Merkle paths of one tree share their siblings, a repeated query index is stored once, the FRI evaluation the verifier can infer

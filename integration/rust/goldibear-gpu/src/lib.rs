@@ -232,6 +232,23 @@ pub struct gb_challenger_state {
     pub output_len: u32,
 }
 
+/// One proof's outcome of `gb_verify_batch`: `status` is what `gb_verify` returns for it, `check` the `GB_VCHECK_*` it names.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct gb_verify_result {
+    pub status: u32,
+    pub check: u32,
+    pub query_round: u32,
+    pub index: u32,
+}
+
+impl gb_verify_result {
+    /// the text `gb_verify` leaves in `gb_last_error` for this result's check ("" when the proof verified)
+    pub fn text(&self) -> String {
+        unsafe { CStr::from_ptr(gb_verify_check_text(self.check)) }.to_string_lossy().into_owned()
+    }
+}
+
 /// How the words of a host matrix encode field elements (`flags` of the entry points that take matrices).
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
 pub enum Repr {
@@ -333,6 +350,9 @@ extern "C" {
     fn gb_prove(c: *mut gb_circuit, witness: *const c_void, flags: u32, public_inputs: *const u64, num_public_inputs: usize,
                 proof_out: *mut c_void, proof_cap: usize, proof_len: *mut usize) -> i32;
     fn gb_verify(c: *mut gb_circuit, proof: *const c_void, proof_len: usize) -> i32;
+    fn gb_verify_batch(ctx: *mut gb_ctx, c: *mut gb_circuit, proofs: *const *const c_void, proof_lens: *const usize, num_proofs: u32,
+                       flags: u32, results: *mut c_void) -> i32;
+    fn gb_verify_check_text(check: u32) -> *const c_char;
     fn gb_circuit_constants_sigmas_commitment(c: *mut gb_circuit, out: *mut *mut gb_batch) -> i32;
     fn gb_zs_partial_products(c: *mut gb_circuit, witness: *const c_void, flags: u32, betas: *const c_void, gammas: *const c_void,
                               values_out: *mut c_void) -> i32;
@@ -1392,6 +1412,21 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         let mut h = ptr::null_mut();
         check(self.ctx.0, unsafe { gb_circuit_constants_sigmas_commitment(self.handle, &mut h) })?;
         Ok(h)
+    }
+    /// `verify` of many proofs of this circuit at once, the query rounds on the device: one `gb_verify_result` per proof (its
+    /// `status` is what `verify` would answer); Err only when the call itself did not complete
+    pub fn verify_batch(&self, proofs: &[&[u8]]) -> Result<Vec<gb_verify_result>, GpuError> {
+        let ptrs: Vec<*const c_void> = proofs.iter().map(|p| p.as_ptr() as *const c_void).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut res = vec![gb_verify_result::default(); proofs.len()];
+        let st = unsafe {
+            gb_verify_batch(self.ctx.0, self.handle, ptrs.as_ptr(), lens.as_ptr(), proofs.len() as u32, 0,
+                            res.as_mut_ptr() as *mut c_void)
+        };
+        if st != GB_ERR_VERIFY {
+            check(self.ctx.0, st)?;
+        }
+        Ok(res)
     }
     /// `CircuitData::verify` for the gate sets the library evaluates, on the host: Ok(true), Ok(false) when a check fails
     pub fn verify(&self, proof: &[u8]) -> Result<bool, GpuError> {

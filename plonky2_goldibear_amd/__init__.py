@@ -9,7 +9,7 @@ wiring      copy constraints -> sigma columns and representative map on the devi
 """
 from .native import GB_BABYBEAR, GB_GOLDILOCKS, GoldibearError, ShapeError  # noqa: F401
 from .native import PermArgZeroError, TooManyPermArgFailuresError, VerifyError  # noqa: F401
-from .native import UnsatisfiedError, Violation  # noqa: F401
+from .native import UnsatisfiedError, VerifyResult, Violation  # noqa: F401
 from .polynomial_batch import GpuContext, MerkleTree, PolynomialBatch, random_elements  # noqa: F401
 from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  # noqa: F401
 from .prover import CircuitData, SigmaInfo, VerifierCircuitData  # noqa: F401

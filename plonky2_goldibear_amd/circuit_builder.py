@@ -1605,3 +1605,7 @@ class BuiltCircuit:
 
     def verify(self, proof):
         return self.data.verify(proof)
+
+    def verify_batch(self, proofs):
+        """CircuitData.verify_batch: one native.VerifyResult per proof, the query rounds checked on the device"""
+        return self.data.verify_batch(proofs)

@@ -28,6 +28,7 @@
 #include "kernels.hpp"
 #include "poseidon2_bb_host.hpp"
 #include "poseidon_gl_host.hpp"
+#include "verify_query.hpp"
 
 using gbk::BbF;
 using gbk::GlF;
@@ -103,6 +104,12 @@ struct gb_ctx {
     int copy_threads = 4;                                   // "copy_threads": -1 = no staging ring (hipMemcpyAsync straight from pageable memory)
     bool retry_verify = false;                              // "retry_verify": gb_prove_retry compares the whole matrix with the kept copy
     bool check_witness = false;                             // "check_witness": gb_prove* check their device witness before the wires commitment
+    size_t verify_chunk_bytes = (size_t)8 << 20;            // "verify_chunk_bytes": gb_verify_batch stages and uploads at most this much per chunk
+    // gb_verify_batch (verify_batch_host.inc): two page-locked staging slots and their device twins, grow-only, and the failure keys
+    char *vstage_host[2] = {nullptr, nullptr}, *vstage_dev[2] = {nullptr, nullptr};
+    size_t vstage_bytes = 0;
+    hipEvent_t vstage_read[2] = {nullptr, nullptr};         // recorded behind the uploads out of a slot
+    DeviceBuf vkeys;
 };
 static void drop_all_retry_state(gb_ctx* ctx);              // prover_host.inc
 static void drop_all_check_state(gb_ctx* ctx);              // prover_host.inc: what gb_check_witness keeps with the circuits
@@ -1150,6 +1157,12 @@ gb_status gb_ctx_destroy(gb_ctx* ctx) try {
     for (auto& kv : ctx->pool) hipFree(kv.second);
     if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
     delete ctx->stager;   // joins the copy threads, frees the page-locked ring
+    for (int s = 0; s < 2; s++) {
+        if (ctx->vstage_host[s]) (void)hipHostFree(ctx->vstage_host[s]);
+        if (ctx->vstage_dev[s]) (void)hipFree(ctx->vstage_dev[s]);
+        if (ctx->vstage_read[s]) (void)hipEventDestroy(ctx->vstage_read[s]);
+    }
+    if (ctx->vkeys.p) (void)hipFree(ctx->vkeys.p);
     if (ctx->xfer_up) (void)hipHostFree(ctx->xfer_up);
     if (ctx->xfer_down) (void)hipHostFree(ctx->xfer_down);
     hipStreamDestroy(ctx->stream);
@@ -1329,6 +1342,9 @@ gb_status gb_ctx_set_option(gb_ctx* ctx, const char* key, int64_t value) try {
         ctx->retry_verify = value != 0;
     } else if (k == "check_witness") {
         ctx->check_witness = value != 0;
+    } else if (k == "verify_chunk_bytes") {
+        if (value < 4096 || value > ((int64_t)1 << 30)) return fail(ctx, GB_ERR_INVALID, "verify_chunk_bytes must be 4096 .. 2^30");
+        ctx->verify_chunk_bytes = (size_t)value;
     } else {
         return fail(ctx, GB_ERR_INVALID, "unknown option: " + k);
     }
@@ -1504,3 +1520,4 @@ gb_status gb_random_elements(gb_ctx* ctx, uint32_t field, const uint8_t* seed, c
 #include "wiring_host.inc"
 #include "verifier_host.inc"
 #include "compress_host.inc"
+#include "verify_batch_host.inc"

@@ -480,4 +480,32 @@ struct QueryIdx {
 template <class F>
 void query_gather(const QueryJobs<F>& jobs, u32 njobs, const u64* idx_host, const u64* idx_dev, u32 nidx, typename F::T* out, hipStream_t st);
 
+// ---- gb_verify_batch (kernels_verify.hip): the query rounds of a chunk of proofs of one circuit.
+// `rounds` holds the proofs' query sections as they stand in the proof bytes, proof after proof, nqr rounds of round_bytes each
+// (words canonical, at any byte offset); every offset below comes from the circuit's shape, none from a proof.  `records` holds
+// one record of rec_bytes per proof:
+//   E section: fri_alpha, red_open[2], alpha_shift[2], points[2], betas[num_layers], final_poly[final_len]   (device form)
+//   at rec_x_off:    u64 x_indices[nqr]
+//   at rec_caps_off: T wires_cap, zs_cap, quot_cap, layer_caps[num_layers], each H << cap_height canonical words
+// A failing check writes min(key) into keys[proof], key = vq::fail_key(query round, position in the round) (verify_query.hpp).
+static constexpr u32 VERIFY_ORACLES = 4, VERIFY_MAX_LAYERS = 32, VERIFY_MAX_TREES = VERIFY_ORACLES + VERIFY_MAX_LAYERS;
+struct VerifyTree {
+    u32 row_off, num_words;   // the opened row (or coset) inside a query round: byte offset, canonical words
+    u32 path_off, path_len;   // its siblings: byte offset (behind the length byte), count
+    u32 shift;                // leaf index = x_index >> shift
+    u32 cap_word;             // word offset of the tree's cap in the record's caps; ~0u: the circuit's own cap
+};
+struct VerifyLayout {
+    u32 num_proofs, nqr, lgN, num_layers, final_len, round_bytes, rec_bytes, rec_x_off, rec_caps_off;
+    u32 batch_sizes[2];                  // every polynomial of the four oracles at zeta; the Zs at g zeta
+    u32 widths[VERIFY_ORACLES];          // polynomials per oracle (a salted row is longer: the salts are hashed, never combined)
+    u32 arity_bits[VERIFY_MAX_LAYERS];
+    VerifyTree trees[VERIFY_MAX_TREES];  // the four oracles, then the layers
+};
+template <class F>
+void verify_paths(const VerifyLayout& L, const unsigned char* rounds, const unsigned char* records, const typename F::T* circuit_cap,
+                  u64* keys, hipStream_t st);
+template <class F>
+void verify_queries(const VerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st);
+
 }  // namespace gbk

@@ -13,11 +13,40 @@ namespace {
 struct VerifyFail {
     gb_status code;
     std::string msg;
+    // what gb_verify_batch reports beside the status (gb_verify_result): the GB_VCHECK_* of the checks gb_verify runs, the
+    // query round and the oracle / layer of the FRI query checks
+    u32 check = GB_VCHECK_NONE, query_round = UINT32_MAX, index = UINT32_MAX;
 };
-#define GB_VCHECK(cond, text)                                \
-    do {                                                     \
-        if (!(cond)) throw VerifyFail{GB_ERR_VERIFY, text};  \
-    } while (0)
+// The text gb_verify leaves in gb_last_error for each of its checks (gb_verify_check_text) and the status it returns
+inline const char* vcheck_text(u32 check) {
+    switch (check) {
+    case GB_VCHECK_TRUNCATED: return "proof bytes are truncated";
+    case GB_VCHECK_NON_CANONICAL: return "non-canonical field element in the proof";
+    case GB_VCHECK_PI_IMPLAUSIBLE: return "implausible public input count";
+    case GB_VCHECK_PI_COUNT: return "Number of public inputs doesn't match circuit data.";
+    case GB_VCHECK_TRAILING: return "trailing bytes in proof";
+    case GB_VCHECK_VANISHING: return "vanishing polynomial identity failed at zeta (plonk/verifier.rs:87-95)";
+    case GB_VCHECK_POW: return "Invalid proof of work witness. (fri/verifier.rs:51-65)";
+    case GB_VCHECK_INITIAL_PATH_LEN: return "Merkle path of the wrong length";
+    case GB_VCHECK_INITIAL_PATH: return "initial Merkle path does not lead to the cap";
+    case GB_VCHECK_CONSISTENCY: return "FRI consistency check failed (fri/verifier.rs:213-216)";
+    case GB_VCHECK_LAYER_PATH_LEN: return "FRI layer Merkle path of the wrong length";
+    case GB_VCHECK_LAYER_PATH: return "FRI layer Merkle path does not lead to the cap";
+    case GB_VCHECK_FINAL_POLY: return "Final polynomial evaluation is invalid. (fri/verifier.rs:240-247)";
+    default: return "";
+    }
+}
+inline gb_status vcheck_status(u32 check) {
+    switch (check) {
+    case GB_VCHECK_NONE: return GB_OK;
+    case GB_VCHECK_VANISHING: case GB_VCHECK_POW: case GB_VCHECK_INITIAL_PATH: case GB_VCHECK_CONSISTENCY: case GB_VCHECK_LAYER_PATH:
+    case GB_VCHECK_FINAL_POLY: return GB_ERR_VERIFY;
+    default: return GB_ERR_INVALID;
+    }
+}
+[[noreturn]] inline void vfail(u32 check, u32 query_round = UINT32_MAX, u32 index = UINT32_MAX) {
+    throw VerifyFail{vcheck_status(check), vcheck_text(check), check, query_round, index};
+}
 
 template <class F>
 struct ProofReader {
@@ -26,7 +55,7 @@ struct ProofReader {
     const uint8_t* p;
     size_t len, off = 0;
     void need(size_t n) {
-        if (off + n > len) throw VerifyFail{GB_ERR_INVALID, "proof bytes are truncated"};
+        if (off + n > len) vfail(GB_VCHECK_TRUNCATED);
     }
     uint8_t u8() { need(1); return p[off++]; }
     u64 usize() { need(8); u64 v; std::memcpy(&v, p + off, 8); off += 8; return v; }
@@ -36,7 +65,7 @@ struct ProofReader {
         std::memcpy(&v, p + off, sizeof(T));
         off += sizeof(T);
         const u64 order = F::ORDER_BITS == 64 ? 0xFFFFFFFF00000001ULL : 2013265921ULL;
-        if ((u64)v >= order) throw VerifyFail{GB_ERR_INVALID, "non-canonical field element in the proof"};
+        if ((u64)v >= order) vfail(GB_VCHECK_NON_CANONICAL);
         return v;
     }
     void canon_vec(std::vector<T>& out, size_t n) { out.resize(n); for (auto& x : out) x = field_canonical(); }
@@ -63,6 +92,10 @@ template <class F>
 struct HostHash;
 template <>
 struct HostHash<GlF> {
+    u64 s[12] = {};   // the hasher policy of verify_query.hpp: one sponge state, canonical words
+    void set_canonical(int i, u64 v) { s[i] = v; }
+    void permute() { poseidon_gl_host::permute(s); }
+    u64 out(int i) const { return s[i]; }
     static void two_to_one(const u64* l, const u64* r, u64* out) {  // hash/hashing.rs:76-96
         u64 st[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
         poseidon_gl_host::permute(st);
@@ -71,6 +104,10 @@ struct HostHash<GlF> {
 };
 template <>
 struct HostHash<BbF> {
+    u32 s[16] = {};
+    void set_canonical(int i, u32 v) { s[i] = v; }
+    void permute() { poseidon2_bb_host::permute(s); }
+    u32 out(int i) const { return s[i]; }
     static void two_to_one(const u32* l, const u32* r, u32* out) {
         u32 st[16];
         std::memcpy(st, l, 8 * sizeof(u32));
@@ -80,41 +117,18 @@ struct HostHash<BbF> {
     }
 };
 
-// hash/merkle_proofs.rs:54-76 (leaf and siblings canonical)
+// hash/merkle_proofs.rs:54-76 (leaf and siblings canonical): verify_query.hpp's walk over the host permutation
 template <class F>
 bool merkle_verify(const std::vector<typename F::T>& leaf, u64 index, const typename F::T* cap, const std::vector<typename F::T>& siblings) {
-    typedef typename F::T T;
-    constexpr u32 H = F::H;
-    T cur[H];
-    if (leaf.size() <= H) {  // hash_or_noop (plonk/config.rs:70-84)
-        for (u32 i = 0; i < H; i++) cur[i] = i < leaf.size() ? leaf[i] : 0;
-    } else {
-        Host<F>::hash_no_pad(leaf.data(), leaf.size(), cur);
-    }
-    const size_t layers = siblings.size() / H;
-    for (size_t i = 0; i < layers; i++) {
-        T nxt[H];
-        const T* sib = siblings.data() + i * H;
-        if (index & 1) HostHash<F>::two_to_one(sib, cur, nxt);
-        else HostHash<F>::two_to_one(cur, sib, nxt);
-        std::memcpy(cur, nxt, sizeof cur);
-        index >>= 1;
-    }
-    return std::memcmp(cur, cap + index * H, sizeof cur) == 0;
+    HostHash<F> h;
+    return gbk::vq::merkle_path_ok<F>(h, reinterpret_cast<const unsigned char*>(leaf.data()), (u32)leaf.size(), index,
+                                      reinterpret_cast<const unsigned char*>(siblings.data()), (u32)(siblings.size() / F::H), cap);
 }
 
-inline u64 rev_bits64(u64 x, u32 bits) {
-    u64 r = 0;
-    for (u32 i = 0; i < bits; i++) r |= ((x >> i) & 1) << (bits - 1 - i);
-    return r;
-}
+inline u64 rev_bits64(u64 x, u32 bits) { return gbk::vq::rev_bits(x, bits); }
 
 template <class F>
-bool eeq(const typename F::E& a, const typename F::E& b) {
-    for (u32 k = 0; k < F::D; k++)
-        if (F::coord(a, k) != F::coord(b, k)) return false;
-    return true;
-}
+bool eeq(const typename F::E& a, const typename F::E& b) { return gbk::vq::eeq<F>(a, b); }
 
 // Shape of a proof for one circuit (what the (de)serialisers need from CommonCircuitData)
 template <class F>
@@ -218,12 +232,12 @@ void parse_proof(const Circuit<F>* c, const ProofShape<F>& sh, const uint8_t* by
     parse_caps_and_openings(rd, sh, p);
     parse_fri_queries(rd, sh.row_widths, 4, c->arity_bits, sh.nqr, sh.final_len, p);
     const u64 npis = rd.usize();
-    if (npis > (1u << 20)) throw VerifyFail{GB_ERR_INVALID, "implausible public input count"};
+    if (npis > (1u << 20)) vfail(GB_VCHECK_PI_IMPLAUSIBLE);
     // validate_proof_with_pis_shape (plonk/validate_shape.rs:22-25): hash_no_pad does not pad, so a proof re-serialised with
     // zero public inputs appended or stripped keeps its transcript - only the count tells it from the honest one
-    if (npis != c->cfg.num_public_inputs) throw VerifyFail{GB_ERR_INVALID, "Number of public inputs doesn't match circuit data."};
+    if (npis != c->cfg.num_public_inputs) vfail(GB_VCHECK_PI_COUNT);
     rd.canon_vec(p.pis, (size_t)npis);
-    if (rd.off != len) throw VerifyFail{GB_ERR_INVALID, "trailing bytes in proof"};
+    if (rd.off != len) vfail(GB_VCHECK_TRAILING);
 }
 
 // plonk/get_challenges.rs:26-101 (fri/challenges.rs:24-68 for the FRI part); field challenges in device form
@@ -329,6 +343,8 @@ struct FriQueryMath {
     const FriInstance<F> inst;
     const E fri_alpha;
     std::vector<E> red_open, alpha_shift;   // per batch: reduce(openings) (PrecomputedReducedOpenings), alpha^(size of the batch)
+    std::vector<E> points;                  // per batch, and its size: the flat form verify_query.hpp takes
+    std::vector<u32> sizes;
     T wN;
     // openings[b]: the claimed values of batch b's polynomials at its point, in the batch's order
     FriQueryMath(FriInstance<F> in, const std::vector<std::vector<E>>& openings, E alpha) : inst(std::move(in)), fri_alpha(alpha) {
@@ -337,46 +353,25 @@ struct FriQueryMath {
             for (size_t i = openings[b].size(); i-- > 0;) acc = F::eadd(F::emul(fri_alpha, acc), openings[b][i]);
             red_open.push_back(acc);
             alpha_shift.push_back(gbk::epow<F>(fri_alpha, inst.batches[b].polys.size()));
+            points.push_back(inst.batches[b].point);
+            sizes.push_back((u32)inst.batches[b].polys.size());
         }
         wN = F::two_adic_generator(inst.lgN);
     }
     FriQueryMath(const ProofShape<F>& s, const ParsedProof<F>& p, const Challenges<F>& c)
         : FriQueryMath(plonk_fri_instance<F>(s, c.zeta), plonk_fri_openings<F>(p), c.fri_alpha) {}
-    T subgroup_x(u64 x_index) const { return F::mul(F::generator(), F::pow(wN, rev_bits64(x_index, inst.lgN))); }
+    T subgroup_x(u64 x_index) const { return gbk::vq::subgroup_x<F>(inst.lgN, x_index); }
     // fri_combine_initial: rows[o] = the opened leaf of oracle o (salts, if any, at the end and never indexed)
     E combine_initial(const std::vector<T>* rows, T x) const {
-        E sum = F::ezero();
-        for (size_t b = 0; b < inst.batches.size(); b++) {
-            const typename FriInstance<F>::Batch& bt = inst.batches[b];
-            E acc = F::ezero();
-            for (size_t i = bt.polys.size(); i-- > 0;)
-                acc = F::eadd(F::emul(fri_alpha, acc), F::efrom(F::enc(rows[bt.polys[i].first][bt.polys[i].second])));
-            const E term = F::emul(F::esub(acc, red_open[b]), F::einv(F::esub(F::efrom(x), bt.point)));
-            sum = F::eadd(F::emul(alpha_shift[b], sum), term);   // alpha.shift(sum) + numerator / denominator
-        }
-        return sum;
+        return gbk::vq::combine_initial<F>((u32)sizes.size(), sizes.data(), points.data(), red_open.data(), alpha_shift.data(), fri_alpha, x,
+                                           [&](u32 b, u32 i) {
+                                               const std::pair<u32, u32>& pl = inst.batches[b].polys[i];
+                                               return rows[pl.first][pl.second];
+                                           });
     }
     // compute_evaluation: interpolate the coset's values (bit-reversed order) at beta
     static E compute_evaluation(T x, u64 within, u32 ab, const std::vector<E>& evals, E beta) {
-        const u32 arity = 1u << ab;
-        const E one = F::efrom(F::one());
-        const T g = F::two_adic_generator(ab);
-        const T coset_start = F::mul(x, F::pow(g, arity - rev_bits64(within, ab)));
-        std::vector<T> xs(arity);
-        T xp = coset_start;
-        for (u32 i = 0; i < arity; i++) { xs[i] = xp; xp = F::mul(xp, g); }
-        E res = F::ezero();
-        for (u32 i = 0; i < arity; i++) {
-            E num = one;
-            T den = F::one();
-            for (u32 j = 0; j < arity; j++)
-                if (j != i) {
-                    num = F::emul(num, F::esub(beta, F::efrom(xs[j])));
-                    den = F::mul(den, F::sub(xs[i], xs[j]));
-                }
-            res = F::eadd(res, F::emul(evals[rev_bits64(i, ab)], F::escale(num, F::inv(den))));
-        }
-        return res;
+        return gbk::vq::compute_evaluation<F>(x, within, ab, beta, [&](u32 k) { return evals[k]; });
     }
     static std::vector<E> to_ext(const std::vector<T>& canon) {
         std::vector<E> out(canon.size() / F::D);
@@ -389,55 +384,60 @@ struct FriQueryMath {
     }
 };
 
-// verify_fri_proof (fri/verifier.rs:67-250) after the transcript: proof of work, then per query round the initial Merkle paths,
-// fri_combine_initial and the folding checks down to the final polynomial.  initial_caps[o]: the cap of oracle o.
+// verify_fri_proof (fri/verifier.rs:67-250) after the transcript, in the two pieces gb_verify_batch needs apart: the proof of
+// work, then per query round the initial Merkle paths, fri_combine_initial and the folding checks down to the final polynomial
+// (verify_query.hpp).  initial_caps[o]: the cap of oracle o.
 template <class F>
-void verify_fri_parsed(const FriQueryMath<F>& fri, const typename F::T* const* initial_caps, const std::vector<uint32_t>& arity_bits,
-                       u32 proof_of_work_bits, const ParsedProof<F>& pp, const Challenges<F>& chal) {
+void check_pow(u32 proof_of_work_bits, const Challenges<F>& chal) {
+    const u32 min_lz = proof_of_work_bits + (64 - F::ORDER_BITS);
+    const u32 lz = chal.pow_response ? (u32)__builtin_clzll(chal.pow_response) : 64;
+    if (lz < min_lz) vfail(GB_VCHECK_POW);
+}
+template <class F>
+void verify_fri_queries(const FriQueryMath<F>& fri, const typename F::T* const* initial_caps, const std::vector<uint32_t>& arity_bits,
+                        const ParsedProof<F>& pp, const Challenges<F>& chal) {
     typedef typename F::T T;
     typedef typename F::E E;
     constexpr u32 H = F::H;
+    namespace vq = gbk::vq;
     const FriInstance<F>& in = fri.inst;
-    const u32 nlayers = (u32)arity_bits.size();
-    {
-        const u32 min_lz = proof_of_work_bits + (64 - F::ORDER_BITS);
-        const u32 lz = chal.pow_response ? (u32)__builtin_clzll(chal.pow_response) : 64;
-        GB_VCHECK(lz >= min_lz, "Invalid proof of work witness. (fri/verifier.rs:51-65)");
-    }
+    const u32 nlayers = (u32)arity_bits.size(), noracles = (u32)in.widths.size();
     for (size_t qi = 0; qi < pp.queries.size(); qi++) {
         const typename ParsedProof<F>::Query& q = pp.queries[qi];
         const u64 x_index = chal.x_indices[qi];
-        for (size_t o = 0; o < in.widths.size(); o++) {
+        for (u32 o = 0; o < noracles; o++) {
             // the path length is part of the statement (hash/merkle_proofs.rs:62-75 indexes the cap with what is left of the index)
-            if (q.paths[o].size() != (size_t)H * (in.lgN - in.capH)) throw VerifyFail{GB_ERR_INVALID, "Merkle path of the wrong length"};
-            GB_VCHECK(merkle_verify<F>(q.rows[o], x_index, initial_caps[o], q.paths[o]), "initial Merkle path does not lead to the cap");
+            if (q.paths[o].size() != (size_t)H * (in.lgN - in.capH)) vfail(GB_VCHECK_INITIAL_PATH_LEN, (u32)qi, o);
+            if (!merkle_verify<F>(q.rows[o], x_index, initial_caps[o], q.paths[o])) vfail(GB_VCHECK_INITIAL_PATH, (u32)qi, o);
         }
-        T subgroup_x = fri.subgroup_x(x_index);
-        E old_eval = fri.combine_initial(q.rows.data(), subgroup_x);
-        u64 xi = x_index;
+        const T subgroup_x = fri.subgroup_x(x_index);
+        const E old_eval = fri.combine_initial(q.rows.data(), subgroup_x);
         u32 height = in.lgN;
-        for (u32 li = 0; li < nlayers; li++) {
-            const u32 ab = arity_bits[li], arity = 1u << ab;
-            const u64 coset_index = xi >> ab, within = xi & (arity - 1);
-            const std::vector<E> evals = FriQueryMath<F>::to_ext(q.step_rows[li]);
-            GB_VCHECK(eeq<F>(evals[within], old_eval), "FRI consistency check failed (fri/verifier.rs:213-216)");
-            old_eval = FriQueryMath<F>::compute_evaluation(subgroup_x, within, ab, evals, chal.fri_betas[li]);
-            height -= ab;
-            if (height < in.capH || q.step_paths[li].size() != (size_t)H * (height - in.capH))
-                throw VerifyFail{GB_ERR_INVALID, "FRI layer Merkle path of the wrong length"};
-            GB_VCHECK(merkle_verify<F>(q.step_rows[li], coset_index, pp.layer_caps[li].data(), q.step_paths[li]),
-                      "FRI layer Merkle path does not lead to the cap");
-            subgroup_x = F::pow(subgroup_x, (u64)1 << ab);
-            xi = coset_index;
-        }
-        E acc = F::ezero();
-        for (size_t i = pp.final_poly.size(); i-- > 0;) acc = F::eadd(F::escale(acc, subgroup_x), pp.final_poly[i]);
-        GB_VCHECK(eeq<F>(acc, old_eval), "Final polynomial evaluation is invalid. (fri/verifier.rs:240-247)");
+        const u32 pos = vq::fold_checks<F>(
+            noracles, nlayers, arity_bits.data(), x_index, subgroup_x, old_eval, (u32)pp.final_poly.size(),
+            [&](u32 li) { return reinterpret_cast<const unsigned char*>(q.step_rows[li].data()); },
+            [&](u32 li) { return chal.fri_betas[li]; }, [&](u32 i) { return pp.final_poly[i]; },
+            [&](u32 li, u64 coset_index) {
+                height -= arity_bits[li];
+                if (height < in.capH || q.step_paths[li].size() != (size_t)H * (height - in.capH)) vfail(GB_VCHECK_LAYER_PATH_LEN, (u32)qi, li);
+                return merkle_verify<F>(q.step_rows[li], coset_index, pp.layer_caps[li].data(), q.step_paths[li]);
+            });
+        if (pos == ~0u) continue;
+        if (pos == vq::pos_final(noracles, nlayers)) vfail(GB_VCHECK_FINAL_POLY, (u32)qi);
+        const u32 li = (pos - noracles) / 2;
+        vfail((pos - noracles) & 1 ? GB_VCHECK_LAYER_PATH : GB_VCHECK_CONSISTENCY, (u32)qi, li);
     }
 }
-
 template <class F>
-void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>& pp) {
+void verify_fri_parsed(const FriQueryMath<F>& fri, const typename F::T* const* initial_caps, const std::vector<uint32_t>& arity_bits,
+                       u32 proof_of_work_bits, const ParsedProof<F>& pp, const Challenges<F>& chal) {
+    check_pow<F>(proof_of_work_bits, chal);
+    verify_fri_queries<F>(fri, initial_caps, arity_bits, pp, chal);
+}
+
+// vanishing(zeta) == Z_H(zeta) * quotient(zeta)  (plonk/verifier.rs:60-95, vanishing_poly.rs:40-170)
+template <class F>
+void check_vanishing(const Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>& pp, const Challenges<F>& chal) {
     typedef typename F::T T;
     typedef typename F::E E;
     constexpr u32 H = F::H;
@@ -445,15 +445,12 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
     const u32 lg = sh.lg, nch = sh.nch, nr = sh.nr, qdf = sh.qdf, nchunks = sh.nchunks, num_prods = sh.num_prods;
     const u64 n = sh.n;
     const E one = F::efrom(F::one());
-    Challenges<F> chal;
-    get_challenges(c, sh, pp, chal);
     const std::vector<E>&o_const = pp.o_const, &o_sig = pp.o_sig, &o_w = pp.o_w, &o_z = pp.o_z, &o_zn = pp.o_zn, &o_pp = pp.o_pp,
                         &o_q = pp.o_q;
     const std::vector<T>&betas = chal.betas, &gammas = chal.gammas, &alphas = chal.alphas;
     const E zeta = chal.zeta;
     const T* pi_hash = chal.pi_hash;
 
-    // ---- vanishing(zeta) == Z_H(zeta) * quotient(zeta)  (plonk/verifier.rs:60-95, vanishing_poly.rs:40-170)
     {
         E zn = zeta;
         for (u32 i = 0; i < lg; i++) zn = F::emul(zn, zn);
@@ -513,9 +510,18 @@ void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>&
             for (size_t t = terms.size(); t-- > 0;) van = F::eadd(terms[t], F::escale(van, alphas[i]));
             E acc = F::ezero();
             for (u32 j = qdf; j-- > 0;) acc = F::eadd(F::emul(acc, zn), o_q[(size_t)i * qdf + j]);
-            GB_VCHECK(eeq<F>(van, F::emul(z_h, acc)), "vanishing polynomial identity failed at zeta (plonk/verifier.rs:87-95)");
+            if (!eeq<F>(van, F::emul(z_h, acc))) vfail(GB_VCHECK_VANISHING);
         }
     }
+}
+
+template <class F>
+void verify_parsed(Circuit<F>* c, const ProofShape<F>& sh, const ParsedProof<F>& pp) {
+    typedef typename F::T T;
+    const gb_circuit_config& cfg = c->cfg;
+    Challenges<F> chal;
+    get_challenges(c, sh, pp, chal);
+    check_vanishing<F>(c, sh, pp, chal);
 
     // ---- FRI (fri/verifier.rs:67-250) on the PLONK instance
     const FriQueryMath<F> fri(sh, pp, chal);

@@ -1,0 +1,299 @@
+// gb_verify_batch: gb_verify of many proofs of one circuit, the query rounds on the device (included at the end of api.hip, after
+// verifier_host.inc, whose pieces it shares: parse_proof, get_challenges, check_vanishing, check_pow, FriQueryMath and - for a
+// proof whose query section is not of the circuit's shape - verify_fri_queries itself).
+//
+// Per chunk of proofs: the HOST STAGE runs per proof, independent, over the context's copy threads - everything gb_verify does in
+// front of the query rounds, then the proof's query bytes (as they stand) and its record (kernels.hpp: VerifyLayout) into a
+// page-locked slot; a proof that fails here, or that the host checks whole, takes no place in the slot.  Then one upload and the
+// two kernels of kernels_verify.hip on the context's stream.  There are two slots, so the host stage of chunk k+1 runs while the
+// kernels of chunk k do.  The failure keys of every chunk are read back once, at the end.
+
+namespace {
+
+template <class F>
+struct BatchPlan {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    ProofShape<F> sh;
+    gbk::VerifyLayout L{};
+    size_t head_bytes = 0, query_bytes = 0, tail_fixed_bytes = 0, per_proof_bytes = 0;
+    explicit BatchPlan(const Circuit<F>* c) : sh(c) {
+        constexpr size_t TS = sizeof(T);
+        constexpr u32 D = F::D, H = F::H;
+        const u32 nl = sh.nlayers;
+        L.nqr = sh.nqr; L.lgN = sh.lgN; L.num_layers = nl; L.final_len = (u32)sh.final_len;
+        size_t batch0 = 0;
+        for (int o = 0; o < 4; o++) { L.widths[o] = (u32)sh.widths[o]; batch0 += sh.widths[o]; }
+        L.batch_sizes[0] = (u32)batch0;
+        L.batch_sizes[1] = sh.nch;
+        // one query round (util/serialization/mod.rs:1679-1695): per oracle the row and its path behind a length byte, then per
+        // layer the coset and its path likewise
+        size_t off = 0;
+        u32 t = 0, shift = 0;
+        for (int o = 0; o < 4; o++, t++) {
+            gbk::VerifyTree& tr = L.trees[t];
+            tr.row_off = (u32)off; tr.num_words = (u32)sh.row_widths[o];
+            off += sh.row_widths[o] * TS + 1;
+            tr.path_off = (u32)off; tr.path_len = sh.lgN - sh.capH;
+            off += (size_t)tr.path_len * H * TS;
+            tr.shift = 0;
+            tr.cap_word = o == 0 ? ~0u : (u32)((o - 1) * sh.cap_elems);
+        }
+        for (u32 li = 0; li < nl; li++, t++) {
+            const u32 ab = c->arity_bits[li];
+            shift += ab;
+            gbk::VerifyTree& tr = L.trees[t];
+            L.arity_bits[li] = ab;
+            tr.row_off = (u32)off; tr.num_words = D << ab;
+            off += ((size_t)D << ab) * TS + 1;
+            tr.path_off = (u32)off; tr.path_len = sh.lgN - shift - sh.capH;   // >= 0: check_fri_reduction_arity_bits
+            off += (size_t)tr.path_len * H * TS;
+            tr.shift = shift;
+            tr.cap_word = (u32)((3 + li) * sh.cap_elems);
+        }
+        L.round_bytes = (u32)off;
+        query_bytes = off * sh.nqr;
+        const size_t openings = sh.nconst + sh.nr + sh.nw + 2 * (size_t)sh.nch + (size_t)sh.nch * sh.num_prods + sh.nq;
+        head_bytes = ((3 + nl) * sh.cap_elems + D * openings) * TS;
+        tail_fixed_bytes = (D * sh.final_len + 1) * TS + 8;   // final_poly, pow_witness, the public-input count
+        const size_t ext_bytes = (7 + nl + sh.final_len) * sizeof(E);
+        L.rec_x_off = (u32)ext_bytes;
+        L.rec_caps_off = (u32)(ext_bytes + 8 * (size_t)sh.nqr);
+        L.rec_bytes = (u32)((L.rec_caps_off + (3 + nl) * sh.cap_elems * TS + 15) & ~(size_t)15);
+        per_proof_bytes = query_bytes + L.rec_bytes;
+    }
+};
+
+inline gb_verify_result vresult(const VerifyFail& f) { return gb_verify_result{(uint32_t)f.code, f.check, f.query_round, f.index}; }
+
+// The host stage of one proof.  true: its query rounds and record stand at rounds_dst / rec_dst for the device; false: *res is final.
+template <class F>
+bool verify_host_stage(Circuit<F>* c, const BatchPlan<F>& plan, const uint8_t* bytes, size_t len, gb_verify_result* res,
+                       unsigned char* rounds_dst, unsigned char* rec_dst) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 H = F::H;
+    const ProofShape<F>& sh = plan.sh;
+    const gbk::VerifyLayout& L = plan.L;
+    *res = gb_verify_result{GB_OK, GB_VCHECK_NONE, UINT32_MAX, UINT32_MAX};
+    try {
+        ParsedProof<F> pp;
+        parse_proof(c, sh, bytes, len, pp);
+        Challenges<F> chal;
+        get_challenges(c, sh, pp, chal);
+        check_vanishing<F>(c, sh, pp, chal);
+        const FriQueryMath<F> fri(sh, pp, chal);
+        check_pow<F>(c->cfg.proof_of_work_bits, chal);
+        // the regular shape: every path as long as the circuit says, so that the query rounds stand at the circuit's offsets
+        bool regular = len == plan.head_bytes + plan.query_bytes + plan.tail_fixed_bytes + pp.pis.size() * sizeof(T);
+        for (const auto& q : pp.queries) {
+            for (u32 o = 0; o < 4 && regular; o++) regular = q.paths[o].size() == (size_t)H * L.trees[o].path_len;
+            for (u32 li = 0; li < L.num_layers && regular; li++) regular = q.step_paths[li].size() == (size_t)H * L.trees[4 + li].path_len;
+        }
+        if (!regular) {   // the host's own walk: GB_ERR_INVALID and GB_ERR_VERIFY in gb_verify's order by construction
+            const T* initial_caps[4] = {c->cap_host.data(), pp.wires_cap.data(), pp.zs_cap.data(), pp.quot_cap.data()};
+            verify_fri_queries<F>(fri, initial_caps, c->arity_bits, pp, chal);
+            return false;
+        }
+        std::memcpy(rounds_dst, bytes + plan.head_bytes, plan.query_bytes);
+        E* e = reinterpret_cast<E*>(rec_dst);
+        e[0] = chal.fri_alpha;
+        for (u32 b = 0; b < 2; b++) { e[1 + b] = fri.red_open[b]; e[3 + b] = fri.alpha_shift[b]; e[5 + b] = fri.points[b]; }
+        for (u32 li = 0; li < L.num_layers; li++) e[7 + li] = chal.fri_betas[li];
+        for (u32 i = 0; i < L.final_len; i++) e[7 + L.num_layers + i] = pp.final_poly[i];
+        std::memcpy(rec_dst + L.rec_x_off, chal.x_indices.data(), 8 * (size_t)L.nqr);
+        T* caps = reinterpret_cast<T*>(rec_dst + L.rec_caps_off);
+        const size_t ce = sh.cap_elems;
+        std::memcpy(caps, pp.wires_cap.data(), ce * sizeof(T));
+        std::memcpy(caps + ce, pp.zs_cap.data(), ce * sizeof(T));
+        std::memcpy(caps + 2 * ce, pp.quot_cap.data(), ce * sizeof(T));
+        for (u32 li = 0; li < L.num_layers; li++) std::memcpy(caps + (3 + li) * ce, pp.layer_caps[li].data(), ce * sizeof(T));
+        return true;
+    } catch (const VerifyFail& f) {
+        *res = vresult(f);
+        return false;
+    }
+}
+
+// the key a proof's checks left on the device -> its result
+inline gb_verify_result vresult_of_key(u64 key, u32 num_layers) {
+    if (key == gbk::vq::KEY_NONE) return gb_verify_result{GB_OK, GB_VCHECK_NONE, UINT32_MAX, UINT32_MAX};
+    const u32 qr = (u32)(key >> gbk::vq::POS_BITS), pos = (u32)(key & ((1u << gbk::vq::POS_BITS) - 1));
+    if (pos < 4) return gb_verify_result{GB_ERR_VERIFY, GB_VCHECK_INITIAL_PATH, qr, pos};
+    if (pos == gbk::vq::pos_final(4, num_layers)) return gb_verify_result{GB_ERR_VERIFY, GB_VCHECK_FINAL_POLY, qr, UINT32_MAX};
+    return gb_verify_result{GB_ERR_VERIFY, (pos - 4) & 1 ? (uint32_t)GB_VCHECK_LAYER_PATH : (uint32_t)GB_VCHECK_CONSISTENCY, qr, (pos - 4) / 2};
+}
+
+gb_status verify_stage_ready(gb_ctx* ctx, size_t slot_bytes, size_t key_bytes) {
+    if (ctx->vstage_bytes < slot_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (int s = 0; s < 2; s++) {
+            if (ctx->vstage_host[s]) (void)hipHostFree(ctx->vstage_host[s]);
+            if (ctx->vstage_dev[s]) (void)hipFree(ctx->vstage_dev[s]);
+            ctx->vstage_host[s] = nullptr; ctx->vstage_dev[s] = nullptr;
+        }
+        ctx->vstage_bytes = 0;
+        for (int s = 0; s < 2; s++) {
+            void* h = nullptr;
+            if (hipHostMalloc(&h, slot_bytes, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, GB_ERR_OOM, "hipHostMalloc of the batch verifier's staging slot failed (lower \"verify_chunk_bytes\")");
+            }
+            ctx->vstage_host[s] = static_cast<char*>(h);
+            void* d = nullptr;
+            if (hipMalloc(&d, slot_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, GB_ERR_OOM, "hipMalloc of the batch verifier's chunk buffer failed");
+            }
+            ctx->vstage_dev[s] = static_cast<char*>(d);
+            if (!ctx->vstage_read[s]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->vstage_read[s], hipEventDisableTiming));
+        }
+        ctx->vstage_bytes = slot_bytes;
+    }
+    return ensure(ctx, ctx->vkeys, key_bytes);
+}
+
+template <class F>
+gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proofs, const size_t* lens, u32 num_proofs, gb_verify_result* results) {
+    typedef typename F::T T;
+    const BatchPlan<F> plan(c);
+    gbk::VerifyLayout L = plan.L;
+    const size_t cap_bytes = ((plan.sh.cap_elems * sizeof(T)) + 15) & ~(size_t)15;
+    // proofs per chunk: what "verify_chunk_bytes" holds, at least one; rounds * proofs stays a 32-bit count in the kernels
+    size_t per_chunk = std::max<size_t>(1, ctx->verify_chunk_bytes / plan.per_proof_bytes);
+    per_chunk = std::min<size_t>(per_chunk, std::min<size_t>(num_proofs, (size_t)0x7FFFFFFF / std::max<u32>(1, L.nqr)));
+    // a slot: the circuit's cap, the proofs' query rounds back to back (of any byte length), then - aligned again - their records
+    const size_t rounds_region = (per_chunk * plan.query_bytes + 15) & ~(size_t)15;
+    const size_t slot_bytes = cap_bytes + rounds_region + per_chunk * (size_t)L.rec_bytes;
+    if (gb_status s = verify_stage_ready(ctx, slot_bytes, 8 * (size_t)num_proofs)) return s;
+    u64* keys_dev = static_cast<u64*>(ctx->vkeys.p);
+    HIP_TRY(ctx, hipMemsetAsync(keys_dev, 0xFF, 8 * (size_t)num_proofs, ctx->stream));
+    std::vector<u32> slot_proof(num_proofs, 0);   // device slot (chunk base + place in the chunk) -> proof
+    const unsigned nthreads = (unsigned)std::max(1, std::min<int>(ctx->copy_threads, (int)per_chunk));
+    u32 chunk_no = 0;
+    for (size_t base = 0; base < num_proofs; base += per_chunk, chunk_no++) {
+        const size_t count = std::min<size_t>(per_chunk, num_proofs - base);
+        const int s = (int)(chunk_no & 1);
+        if (chunk_no >= 2) HIP_TRY(ctx, hipEventSynchronize(ctx->vstage_read[s]));   // the slot's last upload has left it
+        char* host = ctx->vstage_host[s];
+        char* dev = ctx->vstage_dev[s];
+        unsigned char* h_rounds = reinterpret_cast<unsigned char*>(host) + cap_bytes;
+        unsigned char* h_recs = h_rounds + rounds_region;
+        std::atomic<size_t> next{0};
+        std::exception_ptr thrown;
+        std::mutex thrown_lock;
+        std::vector<unsigned char> act(count, 0);   // place i of the slot holds a proof for the device
+        std::vector<u32> owner(count);
+        size_t lo = 0, hi = count;
+        {
+            Scope sc(ctx, "verify batch: host stage");
+            auto work = [&]() {
+                try {
+                    for (size_t i; (i = next.fetch_add(1)) < count;) {   // proof base + i stages into place i
+                        const size_t pi = base + i;
+                        act[i] = verify_host_stage<F>(c, plan, static_cast<const uint8_t*>(proofs[pi]), lens[pi], &results[pi],
+                                                      h_rounds + i * plan.query_bytes, h_recs + i * L.rec_bytes);
+                    }
+                } catch (...) {   // (std::bad_alloc: the call fails as a whole)
+                    std::lock_guard<std::mutex> g(thrown_lock);
+                    if (!thrown) thrown = std::current_exception();
+                    next.store(count);
+                }
+            };
+            std::vector<std::thread> pool;
+            for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work);
+            work();
+            for (auto& th : pool) th.join();
+            if (thrown) std::rethrow_exception(thrown);
+            // the places of proofs that ended on the host are filled from the end of the slot
+            for (size_t i = 0; i < count; i++) owner[i] = (u32)(base + i);
+            while (true) {
+                while (lo < hi && act[lo]) lo++;
+                while (hi > lo && !act[hi - 1]) hi--;
+                if (lo >= hi) break;
+                std::memcpy(h_rounds + lo * plan.query_bytes, h_rounds + (hi - 1) * plan.query_bytes, plan.query_bytes);
+                std::memcpy(h_recs + lo * L.rec_bytes, h_recs + (hi - 1) * L.rec_bytes, L.rec_bytes);
+                owner[lo] = owner[hi - 1];
+                act[lo] = 1;
+                act[hi - 1] = 0;
+            }
+            for (size_t i = 0; i < count; i++) slot_proof[base + i] = i < lo ? owner[i] : UINT32_MAX;
+        }
+        const u32 active = (u32)lo;
+        if (!active) continue;
+        L.num_proofs = active;
+        unsigned char* d_rounds = reinterpret_cast<unsigned char*>(dev) + cap_bytes;
+        unsigned char* d_recs = d_rounds + rounds_region;
+        {
+            Scope sc(ctx, "verify batch: upload");
+            std::memcpy(host, c->cap_host.data(), plan.sh.cap_elems * sizeof(T));   // the circuit's cap rides in front of every chunk
+            HIP_TRY(ctx, hipMemcpyAsync(dev, host, cap_bytes + (size_t)active * plan.query_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(d_recs, h_recs, (size_t)active * L.rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ctx->vstage_read[s], ctx->stream));
+        }
+        {
+            Scope sc(ctx, "verify batch: paths");
+            gbk::verify_paths<F>(L, d_rounds, d_recs, reinterpret_cast<const T*>(dev), keys_dev + base, ctx->stream);
+        }
+        {
+            Scope sc(ctx, "verify batch: queries");
+            gbk::verify_queries<F>(L, d_rounds, d_recs, keys_dev + base, ctx->stream);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    std::vector<u64> keys(num_proofs);
+    if (gb_status s = read_back(ctx, keys.data(), keys_dev, 8 * (size_t)num_proofs)) return s;
+    for (size_t slot = 0; slot < num_proofs; slot++)
+        if (slot_proof[slot] != UINT32_MAX) results[slot_proof[slot]] = vresult_of_key(keys[slot], L.num_layers);
+    return GB_OK;
+}
+
+// GB_CATCH of an entry point that returns text instead of a status: the empty string
+struct TextEntryPoint {};
+const char* unwound(TextEntryPoint, const char*) noexcept { return ""; }
+
+}  // namespace
+
+extern "C" {
+
+gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
+                          uint32_t flags, void* results) try {
+    if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null ctx");
+    if (!c) return fail(ctx, GB_ERR_INVALID, "null circuit");
+    if (c->ctx && c->ctx != ctx) return fail(ctx, GB_ERR_INVALID, "the circuit belongs to a different context");
+    if (flags != 0) return fail(ctx, GB_ERR_INVALID, "gb_verify_batch: flags must be 0");
+    if (num_proofs == 0) return GB_OK;
+    if (!proofs || !proof_lens || !results) return fail(ctx, GB_ERR_INVALID, "null argument");
+    for (uint32_t i = 0; i < num_proofs; i++)
+        if (!proofs[i]) return fail(ctx, GB_ERR_INVALID, "null proof");
+    if (c->arity_pending) {
+        (void)need_arity_list(c);   // (writes the message where gb_verify leaves it)
+        return fail(ctx, GB_ERR_INVALID, "no FRI reduction list for this circuit - hand its list over with gb_circuit_set_fri_reduction_arity_bits");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gb_verify_result* res = static_cast<gb_verify_result*>(results);
+    gb_status s;
+    try {
+        s = c->field == GB_GOLDILOCKS ? verify_batch_impl<GlF>(ctx, static_cast<Circuit<GlF>*>(c), proofs, proof_lens, num_proofs, res)
+                                      : verify_batch_impl<BbF>(ctx, static_cast<Circuit<BbF>*>(c), proofs, proof_lens, num_proofs, res);
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);   // earlier chunks may still read the staging slots
+        throw;
+    }
+    if (s != GB_OK) {
+        (void)hipStreamSynchronize(ctx->stream);   // nothing of the call may still read the staging slots
+        return s;
+    }
+    uint32_t bad = 0, first = 0;
+    for (uint32_t i = num_proofs; i-- > 0;)
+        if (res[i].status != GB_OK) { bad++; first = i; }
+    if (!bad) return GB_OK;
+    return fail(ctx, GB_ERR_VERIFY, std::to_string(bad) + " of " + std::to_string(num_proofs) + " proofs did not verify; the first is proof " +
+                                        std::to_string(first) + ": " + vcheck_text(res[first].check));
+} GB_CATCH(ctx)
+
+const char* gb_verify_check_text(uint32_t check) try {
+    return vcheck_text(check);
+} GB_CATCH(TextEntryPoint{})
+
+}  // extern "C"

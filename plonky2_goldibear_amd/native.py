@@ -19,6 +19,10 @@ GB_OK, GB_ERR_INVALID, GB_ERR_HIP, GB_ERR_OOM, GB_ERR_UNSUPPORTED = 0, 1, 2, 3, 
 GB_ERR_PERM_ARG_ZERO, GB_ERR_OPENING_IN_SUBGROUP, GB_ERR_BUFFER_TOO_SMALL, GB_ERR_VERIFY = 16, 17, 18, 19
 GB_ERR_UNSATISFIED = 20   # gb_check_*, and gb_prove* under the option "check_witness": the witness does not satisfy the circuit
 GB_VIOLATION_GATE, GB_VIOLATION_SELECTOR, GB_VIOLATION_COPY = 1, 2, 3
+# gb_verify_result.check: the check gb_verify names (gb_verify_batch)
+(GB_VCHECK_NONE, GB_VCHECK_TRUNCATED, GB_VCHECK_NON_CANONICAL, GB_VCHECK_PI_IMPLAUSIBLE, GB_VCHECK_PI_COUNT, GB_VCHECK_TRAILING,
+ GB_VCHECK_VANISHING, GB_VCHECK_POW, GB_VCHECK_INITIAL_PATH_LEN, GB_VCHECK_INITIAL_PATH, GB_VCHECK_CONSISTENCY,
+ GB_VCHECK_LAYER_PATH_LEN, GB_VCHECK_LAYER_PATH, GB_VCHECK_FINAL_POLY) = range(14)
 GB_GOLDILOCKS, GB_BABYBEAR = 0, 1
 GB_INPUT_HOST, GB_INPUT_DEVICE = 0, 1
 GB_INPUT_P3_REPR = 2   # host elements are the reference's field types as they lie in memory (p3 words), not canonical values
@@ -62,6 +66,8 @@ SIGNATURES = {
     "gb_batch_device_ptrs": (_i32, [_vp, _pvp, _pvp, _pvp]),
     "gb_batch_eval_ext": (_i32, [_vp, _vp, _vp]),
     "gb_verify": (_i32, [_vp, _vp, _sz]),
+    "gb_verify_batch": (_i32, [_vp, _vp, _cols, C.POINTER(_sz), _u32, _u32, _vp]),
+    "gb_verify_check_text": (C.c_char_p, [_u32]),
     "gb_proof_compress": (_i32, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_proof_decompress": (_i32, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_verify_compressed": (_i32, [_vp, _vp, _sz]),
@@ -204,6 +210,50 @@ class gb_violation(C.Structure):
 class gb_check_result(C.Structure):
     _fields_ = [("num_gate_violations", _u64), ("num_selector_violations", _u64), ("num_copy_violations", _u64),
                 ("copies_checked", _u32), ("num_listed", _u32)]
+
+
+class gb_verify_result(C.Structure):
+    _fields_ = [("status", _u32), ("check", _u32), ("query_round", _u32), ("index", _u32)]
+
+
+class VerifyResult:
+    """one gb_verify_result of gb_verify_batch: `status` is what gb_verify returns for the proof, `text` what it leaves in
+    gb_last_error; query_round / index are None where the check has none"""
+    __slots__ = ("ok", "status", "check", "text", "query_round", "index")
+
+    def __init__(self, status, check, text, query_round, index):
+        self.ok, self.status, self.check, self.text = status == GB_OK, int(status), int(check), text
+        self.query_round = None if query_round == 0xFFFFFFFF else int(query_round)
+        self.index = None if index == 0xFFFFFFFF else int(index)
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "VerifyResult(ok=%r, status=%d, check=%d, text=%r, query_round=%r, index=%r)" % (
+            self.ok, self.status, self.check, self.text, self.query_round, self.index)
+
+
+def verify_batch(ctx_handle, circuit_handle, proofs):
+    """gb_verify_batch on a list of proof byte strings -> [VerifyResult]; a failing proof is reported, not raised - malformed
+    arguments (and HIP / memory errors) still raise"""
+    import numpy as np
+    lib = load()
+    bufs = [np.frombuffer(bytes(p), dtype=np.uint8) for p in proofs]
+    n = len(bufs)
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    # (an empty proof still needs a non-NULL pointer: it is a truncated proof, not a missing argument)
+    empty = np.zeros(1, dtype=np.uint8)
+    for i, b in enumerate(bufs):
+        if not b.size:
+            ptrs[i] = empty.ctypes.data
+    lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+    res = (gb_verify_result * max(n, 1))()
+    st = lib.gb_verify_batch(ctx_handle, circuit_handle, ptrs, lens, n, 0, C.cast(res, C.c_void_p))
+    if st not in (GB_OK, GB_ERR_VERIFY):
+        check(st, ctx_handle)
+    return [VerifyResult(r.status, r.check, (lib.gb_verify_check_text(r.check) or b"").decode(), r.query_round, r.index)
+            for r in res[:n]]
 
 
 class gb_sigma_info(C.Structure):

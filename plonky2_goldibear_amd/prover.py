@@ -595,6 +595,11 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         N.check(self._lib.gb_verify(self.handle, buf.ctypes.data, buf.size), self.ctx.handle)
         return True
 
+    def verify_batch(self, proofs):
+        """verify() of many proofs of this circuit at once, the query rounds on the device (gb_verify_batch): a list of
+        native.VerifyResult, one per proof - status and text are verify()'s; a failing proof is reported, not raised."""
+        return N.verify_batch(self.ctx.handle, self.handle, proofs)
+
     def free(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self._lib.gb_circuit_free(self.handle)
@@ -649,6 +654,11 @@ class VerifierCircuitData(_ProofBytesOps, _FriParamsOps):
         buf = np.frombuffer(bytes(proof_bytes), dtype=np.uint8)
         N.check(self._lib.gb_verify(self.handle, buf.ctypes.data, buf.size))
         return True
+
+    def verify_batch(self, ctx, proofs):
+        """verify() of many proofs at once on the device of `ctx` (a GpuContext; the object itself has none): a list of
+        native.VerifyResult, one per proof - a failing proof is reported, not raised."""
+        return N.verify_batch(getattr(ctx, "handle", None), self.handle, proofs)
 
     def free(self):
         if getattr(self, "handle", None):
