@@ -31,6 +31,7 @@ import numpy as np
 
 from . import native as N
 from .dummy_circuit import BB_P, P as GL_P, bb_mul, bb_powers, gl_mul, gl_powers
+from .prover import prove_with_retries
 
 GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_ARITHMETIC, GATE_POSEIDON, GATE_POSEIDON2_BABYBEAR = 0, 1, 2, 3, 4, 5  # gb_gate.kind
 
@@ -1539,27 +1540,16 @@ class BuiltCircuit:
         if self._input_targets is None:
             self.set_generators(pw=pw)
         values = self.input_values(pw, rng, seed)
-        data = self.data
-        data.perm_arg_retries = 0
-        for attempt in range(data.MAX_PERM_ARG_RETRIES):
-            retry = None
-            if attempt > 0:
-                t = wire(*self.random_wire) if self.random_wire else None
-                if t not in self._input_targets:
-                    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "Permutation argument division by zero but the "
-                                                        "random wire is no input to randomize")
-                rng = rng or np.random.default_rng()
-                values[self._input_targets.index(t)] = int(rng.integers(0, self.F.p, dtype=np.uint64))
-                data.perm_arg_retries = attempt
-                retry = (self.random_wire[1], self.random_wire[0]) if seed is None else None   # (salted: the full computation)
-            try:
-                return data.prove_inputs_once(values, retry_wire=retry, seed=seed)
-            except N.PermArgZeroError:
-                if not self.random_wire:
-                    data.drop_retry()
-                continue
-        data.drop_retry()
-        raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+        rw = self.random_wire or None
+        t = wire(*rw) if rw else None
+
+        def redraw(val):
+            values[self._input_targets.index(t)] = val
+
+        return prove_with_retries(self.data, redraw if t in self._input_set else None,
+                                  lambda hint: self.data.prove_inputs_once(values, retry_wire=hint, seed=seed),
+                                  (rw[1], rw[0]) if rw else None, rng=rng, salted=seed is not None,   # (salted: the full computation)
+                                  nothing_to_redraw="Permutation argument division by zero but the random wire is no input to randomize")
 
     # ---- does the witness these generators make satisfy the circuit?  (include/goldibear_gpu.h gb_check_partition / gb_check_inputs)
     def check(self, pw, rng=None, max_violations=16, seed=None):

@@ -1,5 +1,5 @@
 // gb_check_witness / gb_check_partition / gb_check_inputs (include/goldibear_gpu.h): does this witness satisfy this circuit, and
-// where not?  Included at the end of prover_host.inc.  The kernels are kernels_check.hip's, the row logic
+// where not?  Included at the end of prover_host.inc, behind the witness fronts (witness_host.inc).  The kernels are kernels_check.hip's, the row logic
 // witness_check.hpp's; this file prepares a circuit on its first check (the selector and constant columns as values on H, a row
 // list per gate), runs one launch per gate that has rows and the copy pass, reads the counts back first and the per-entry results
 // only where a count is not zero, and puts the violations in the order the header gives.  The copy classes are the partition's
@@ -99,7 +99,7 @@ gb_status check_matrix(Circuit<F>* c, TmpAlloc& tmp, const typename F::T* wit, c
     gb_ctx* ctx = c->ctx;
     const gb_circuit_config& cfg = c->cfg;
     const u32 nw = cfg.num_wires, nsel = cfg.num_selectors, ng = c->gates.num_gates, nl = ng + 1;
-    const size_t n = (size_t)1 << cfg.degree_bits;
+    const size_t n = Counts(cfg).n;
     const u64 cells = (u64)n * nw;
     hipStream_t st = ctx->stream;
     gb_status s;
@@ -276,38 +276,17 @@ gb_status check_before_commit(Circuit<F>* c, ColSrc witness, uint32_t flags, con
     return check_witness_matrix<F>(c, witness, flags, public_inputs, num_public_inputs, nullptr, 1, nullptr);
 }
 
+// gb_check_partition / gb_check_inputs: the matrix as the prove fronts make it (witness_host.inc), then the check
 template <class F>
-gb_status check_partition(Circuit<F>* c, const void* values, uint32_t flags, gb_violation* out, size_t capacity, gb_check_result* result) {
+gb_status check_source(Circuit<F>* c, WitnessSource src, uint32_t flags, gb_violation* out, size_t capacity, gb_check_result* result) {
     typedef typename F::T T;
     gb_ctx* ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    gb_status s;
-    std::vector<uint64_t> pis;
-    if ((s = partition_public_inputs<F>(c, values, (flags & GB_INPUT_P3_REPR) != 0, &pis))) return s;
-    TmpAlloc tmp(ctx);
-    T* matrix = tmp.get<T>((size_t)c->cfg.num_wires << c->cfg.degree_bits);
-    if (!matrix) return fail(ctx, GB_ERR_OOM, "partition witness matrix");
-    if ((s = expand_partition_stage<F>(c, tmp, values, flags, matrix))) return s;
-    return check_matrix<F>(c, tmp, matrix, pis.data(), pis.size(), out, capacity, result);
-}
-
-template <class F>
-gb_status check_inputs(Circuit<F>* c, const void* input_values, uint32_t flags, gb_violation* out, size_t capacity, gb_check_result* result) {
-    typedef typename F::T T;
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    gb_status s;
     std::vector<uint64_t> pis;
     TmpAlloc tmp(ctx);
     T* matrix = tmp.get<T>((size_t)c->cfg.num_wires << c->cfg.degree_bits);
-    T* values_dev = tmp.get<T>(c->gens.sched.num_classes);
-    if (!matrix || !values_dev) return fail(ctx, GB_ERR_OOM, "witness matrix");
-    if ((s = generate_stage<F>(c, tmp, input_values, flags, values_dev, &pis))) return s;
-    {
-        Scope sc(ctx, "compute full witness");
-        gbk::expand_partition<F>(c->part.slots_dev, values_dev, matrix, c->cfg.degree_bits, c->cfg.num_wires, ctx->stream);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
-    }
+    if (!matrix) return fail(ctx, GB_ERR_OOM, src.inputs ? "witness matrix" : "partition witness matrix");
+    if (gb_status s = witness_to_device<F>(c, tmp, src, flags, matrix, &pis)) return s;
     return check_matrix<F>(c, tmp, matrix, pis.data(), pis.size(), out, capacity, result);
 }
 
@@ -327,9 +306,9 @@ gb_status gb_check_witness(gb_circuit* c, const void* witness, uint32_t flags, c
     gb_violation* out = static_cast<gb_violation*>(violations_out);
     gb_check_result* res = static_cast<gb_check_result*>(result);
     c->drop_retry();   // for gb_prove_retry a check is another call in between: what follows it is the full computation
-    return c->field == GB_GOLDILOCKS
-               ? check_witness_matrix<GlF>(static_cast<Circuit<GlF>*>(c), ColSrc(witness), flags, public_inputs, num_public_inputs, out, capacity, res)
-               : check_witness_matrix<BbF>(static_cast<Circuit<BbF>*>(c), ColSrc(witness), flags, public_inputs, num_public_inputs, out, capacity, res);
+    return by_field(c, [&](auto* cf) {
+        return check_witness_matrix(cf, ColSrc(witness), flags, public_inputs, num_public_inputs, out, capacity, res);
+    });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_check_partition(gb_circuit* c, const void* values, uint32_t flags, void* violations_out, size_t capacity, void* result) try {
@@ -338,8 +317,7 @@ gb_status gb_check_partition(gb_circuit* c, const void* values, uint32_t flags, 
     gb_violation* out = static_cast<gb_violation*>(violations_out);
     gb_check_result* res = static_cast<gb_check_result*>(result);
     c->drop_retry();   // for gb_prove_retry a check is another call in between: what follows it is the full computation
-    return c->field == GB_GOLDILOCKS ? check_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, out, capacity, res)
-                                     : check_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, out, capacity, res);
+    return by_field(c, [&](auto* cf) { return check_source(cf, WitnessSource{values, false}, flags, out, capacity, res); });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_check_inputs(gb_circuit* c, const void* input_values, uint32_t flags, void* violations_out, size_t capacity, void* result) try {
@@ -348,8 +326,7 @@ gb_status gb_check_inputs(gb_circuit* c, const void* input_values, uint32_t flag
     gb_violation* out = static_cast<gb_violation*>(violations_out);
     gb_check_result* res = static_cast<gb_check_result*>(result);
     c->drop_retry();   // for gb_prove_retry a check is another call in between: what follows it is the full computation
-    return c->field == GB_GOLDILOCKS ? check_inputs<GlF>(static_cast<Circuit<GlF>*>(c), input_values, flags, out, capacity, res)
-                                     : check_inputs<BbF>(static_cast<Circuit<BbF>*>(c), input_values, flags, out, capacity, res);
+    return by_field(c, [&](auto* cf) { return check_source(cf, WitnessSource{input_values, true}, flags, out, capacity, res); });
 } GB_CATCH_CIRCUIT(c)
 
 }  // extern "C"

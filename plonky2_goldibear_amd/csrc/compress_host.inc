@@ -307,16 +307,13 @@ extern "C" {
 
 gb_status gb_proof_compress(gb_circuit* c, const void* proof, size_t proof_len, void* out, size_t out_cap, size_t* out_len) try {
     return run_bytes(c, proof, out, out_cap, out_len, [&] {
-        return c->field == GB_GOLDILOCKS ? compress_impl<GlF>(static_cast<Circuit<GlF>*>(c), static_cast<const uint8_t*>(proof), proof_len)
-                                         : compress_impl<BbF>(static_cast<Circuit<BbF>*>(c), static_cast<const uint8_t*>(proof), proof_len);
+        return by_field(c, [&](auto* cf) { return compress_impl(cf, static_cast<const uint8_t*>(proof), proof_len); });
     });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_proof_decompress(gb_circuit* c, const void* compressed, size_t compressed_len, void* out, size_t out_cap, size_t* out_len) try {
     return run_bytes(c, compressed, out, out_cap, out_len, [&] {
-        return c->field == GB_GOLDILOCKS
-                   ? decompress_impl<GlF>(static_cast<Circuit<GlF>*>(c), static_cast<const uint8_t*>(compressed), compressed_len)
-                   : decompress_impl<BbF>(static_cast<Circuit<BbF>*>(c), static_cast<const uint8_t*>(compressed), compressed_len);
+        return by_field(c, [&](auto* cf) { return decompress_impl(cf, static_cast<const uint8_t*>(compressed), compressed_len); });
     });
 } GB_CATCH_CIRCUIT(c)
 
@@ -326,13 +323,10 @@ gb_status gb_verify_compressed(gb_circuit* c, const void* compressed, size_t com
     if (gb_status s = need_arity_list(c)) return s;
     try {
         // CompressedProofWithPublicInputs::verify (plonk/proof.rs:238-265): decompress, then verify_with_challenges
-        if (c->field == GB_GOLDILOCKS) {
-            const auto bytes = decompress_impl<GlF>(static_cast<Circuit<GlF>*>(c), static_cast<const uint8_t*>(compressed), compressed_len);
-            verify_impl<GlF>(static_cast<Circuit<GlF>*>(c), bytes.data(), bytes.size());
-        } else {
-            const auto bytes = decompress_impl<BbF>(static_cast<Circuit<BbF>*>(c), static_cast<const uint8_t*>(compressed), compressed_len);
-            verify_impl<BbF>(static_cast<Circuit<BbF>*>(c), bytes.data(), bytes.size());
-        }
+        by_field(c, [&](auto* cf) {
+            const auto bytes = decompress_impl(cf, static_cast<const uint8_t*>(compressed), compressed_len);
+            verify_impl(cf, bytes.data(), bytes.size());
+        });
     } catch (const VerifyFail& f) {
         return fail(c->ctx, f.code, f.msg);
     } catch (const std::out_of_range&) {

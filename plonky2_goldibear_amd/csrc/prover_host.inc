@@ -29,20 +29,26 @@ struct gb_circuit {
     // is Fixed / MinSize and its list comes through gb_circuit_set_fri_reduction_arity_bits - until then nothing that needs it runs
     bool arity_pending = false;
     bool test_fail_next_perm_arg = false;   // armed by gb_test_arm_perm_arg_failure (include/goldibear_gpu_test_hooks.h), one shot
-    // What a gb_prove that ended in GB_ERR_PERM_ARG_ZERO leaves for gb_prove_retry (prove_with_partition_witness's retry loop,
+    // What a gb_prove* that ended in GB_ERR_PERM_ARG_ZERO leaves for its retry (prove_with_partition_witness's retry loop,
     // plonk/prover.rs:183-226, re-draws ONE wire): the wires commitment, the device-form witness and the leaf sponges' state in
-    // front of the last column segment.  Held until the next gb_prove* / gb_circuit_free on this circuit.
+    // front of the last column segment; from a witness front (witness_host.inc) also the canonical matrix that commitment was made
+    // from - the "device witness" gb_prove_partition_retry / gb_prove_inputs_retry re-draw one cell of - and, from gb_prove_inputs,
+    // the generated public inputs.  One state with one owner: nothing else remembers an attempt.  Held until the next gb_prove* /
+    // gb_circuit_free on this circuit (drop_retry).
     struct RetryKeep {
         gb_batch* wires = nullptr;
         void* wit_vals = nullptr;
         size_t wit_bytes = 0;
         size_t wit_mont_cols = 0;   // BabyBear: columns below this are in Montgomery form in wit_vals, the rest canonical (commit())
         SegKeep seg;
+        void* matrix = nullptr;     // [num_wires][n] canonical words, a pool block
+        size_t matrix_bytes = 0;
+        bool by_inputs = false;     // kept by gb_prove_inputs, with these public inputs (a partition attempt's matrix has none:
+        std::vector<uint64_t> pis;  // gb_prove_inputs_retry does not build on it, gb_prove_partition_retry builds on either)
     } retry;
     // gb_circuit_set_partition: ProverOnlyCircuitData.representative_map as the slot map of partition_map.hpp - the ascending
     // representatives and the public inputs' on the host, a u32 slot per wire cell on the device - and what gb_prove_partition
-    // works with: page-locked staging for the compacted values, and the expanded canonical matrix of an attempt that ended in
-    // InvZeroPermArg (the "device witness" gb_prove_partition_retry re-draws one cell of; released with the retry state).
+    // works with: page-locked staging for the compacted values.
     struct Partition {
         bool set = false;
         std::vector<uint32_t> reps, pi_reps;
@@ -53,8 +59,6 @@ struct gb_circuit {
         void* staged_host = nullptr;
         size_t staged_host_bytes = 0;
         hipEvent_t staged_read = nullptr;   // recorded behind the upload out of staged_host
-        void* matrix = nullptr;
-        size_t matrix_bytes = 0;
         bool is_shared_slot(uint32_t k) const { return (shared[k >> 6] >> (k & 63)) & 1; }
     } part;
     // gb_circuit_set_generators: the schedule of generator_schedule.hpp - its launches, levels and input classes on the host, the
@@ -68,8 +72,6 @@ struct gb_circuit {
         gbk::gen::DeviceSchedule device{nullptr, nullptr, nullptr};   // of device_schedule(): the arrays above and the program tables
         std::vector<std::pair<uint64_t, uint32_t>> input_index;   // (target, index into input_targets), ascending
         std::vector<uint8_t> input_fast;    // the input may be re-drawn inside a kept matrix (gb_prove_inputs_retry)
-        std::vector<uint64_t> kept_pis;     // the public inputs of the attempt that left part.matrix == kept_for behind
-        const void* kept_for = nullptr;
     } gens;
     // gb_circuit_set_generator_programs: the checked programs on the host (the schedule reads the headers) and their tables on the
     // device, literals in the field's device form.  A schedule is built on them: replacing them drops it.
@@ -128,11 +130,8 @@ struct gb_circuit {
         if (retry.wires) gb_batch_free(retry.wires);
         if (ctx && retry.wit_vals) pool_free(ctx, retry.wit_vals, retry.wit_bytes);
         if (ctx && retry.seg.state) pool_free(ctx, retry.seg.state, retry.seg.bytes);
+        if (ctx && retry.matrix) pool_free(ctx, retry.matrix, retry.matrix_bytes);
         retry = RetryKeep{};
-        if (ctx && part.matrix) pool_free(ctx, part.matrix, part.matrix_bytes);
-        part.matrix = nullptr;
-        part.matrix_bytes = 0;
-        gens.kept_for = nullptr;
     }
     void drop_partition() {   // (the caller has waited for the stream)
         drop_generator_programs();
@@ -340,6 +339,16 @@ static inline u32 quotient_degree_bits(const gb_circuit_config& cfg) {
     return qb;
 }
 
+// what the stages derive from a circuit's config (prover.rs:305-376: partial products per challenge, quotient chunks)
+struct Counts {
+    u32 lg, nchunks, num_prods;
+    size_t n, N, nzs, nq;
+    explicit Counts(const gb_circuit_config& cfg)
+        : lg(cfg.degree_bits), nchunks((cfg.num_routed_wires + cfg.max_quotient_degree_factor - 1) / cfg.max_quotient_degree_factor),
+          num_prods(nchunks - 1), n((size_t)1 << lg), N(n << cfg.rate_bits), nzs((size_t)cfg.num_challenges * nchunks),
+          nq((size_t)cfg.num_challenges * cfg.max_quotient_degree_factor) {}
+};
+
 template <class F>
 struct Circuit : gb_circuit {
     typedef typename F::T T;
@@ -367,6 +376,18 @@ struct Circuit : gb_circuit {
         if (digest_out) std::memcpy(digest_out, digest, sizeof digest);
     }
 };
+
+// One call for either field (the tag is GB_GOLDILOCKS or GB_BABYBEAR: the entries check it).  fn is a generic lambda: by tag it
+// gets the traits as a value, `[&](auto f) { typedef decltype(f) F; ... }`; by circuit it gets the circuit as its Circuit<F>*, and
+// the templates it calls deduce F from that
+template <class Fn>
+auto by_field(uint32_t field, Fn&& fn) -> decltype(fn(GlF{})) {
+    return field == GB_GOLDILOCKS ? fn(GlF{}) : fn(BbF{});
+}
+template <class Fn>
+auto by_field(gb_circuit* c, Fn&& fn) -> decltype(fn(static_cast<Circuit<GlF>*>(c))) {
+    return c->field == GB_GOLDILOCKS ? fn(static_cast<Circuit<GlF>*>(c)) : fn(static_cast<Circuit<BbF>*>(c));
+}
 
 struct TmpAlloc {  // pooled temporaries released together
     gb_ctx* ctx;
@@ -653,8 +674,9 @@ gb_status stage_zs_partial_products(Circuit<F>* c, TmpAlloc& tmp, const typename
     gb_ctx* ctx = c->ctx;
     const gb_circuit_config& cfg = c->cfg;
     const u32 lg = cfg.degree_bits, nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
-    const u32 nchunks = (nr + qdf - 1) / qdf, num_prods = nchunks - 1;
-    const size_t n = (size_t)1 << lg, nzs = (size_t)nch * (1 + num_prods);
+    const Counts cnt(cfg);
+    const u32 nchunks = cnt.nchunks;
+    const size_t n = cnt.n, nzs = cnt.nzs;
     hipStream_t st = ctx->stream;
     gbk::ZsParams<F> zp{lg, nr, nch, qdf, nchunks, gbk::PowTab<F>{c->wn_lo, c->wn_hi, 12}, {}, {}};
     std::copy(betas_d.begin(), betas_d.end(), zp.betas);
@@ -683,9 +705,10 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     gb_ctx* ctx = c->ctx;
     const gb_circuit_config& cfg = c->cfg;
     const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, nr = cfg.num_routed_wires;
-    const u32 qdf = cfg.max_quotient_degree_factor, nchunks = (nr + qdf - 1) / qdf;
+    const Counts cnt(cfg);
+    const u32 qdf = cfg.max_quotient_degree_factor, nchunks = cnt.nchunks;
     const u32 qb = quotient_degree_bits(cfg);   // the quotient domain: n 2^qb points = the first 2^qb coset blocks of the LDEs
-    const size_t n = (size_t)1 << lg, nq = (size_t)nch * qdf;
+    const size_t n = cnt.n, nq = cnt.nq;
     hipStream_t st = ctx->stream;
     gb_status s;
     const u32 t0 = nch + nch * nchunks, nterms = t0 + c->num_gate_constraints;
@@ -1043,11 +1066,9 @@ gb_status stage_prove_openings(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     typedef typename F::E E;
     gb_ctx* ctx = c->ctx;
     const gb_circuit_config& cfg = c->cfg;
-    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height;
-    const size_t n = (size_t)1 << lg;
-    const u32 nr = cfg.num_routed_wires, nw = cfg.num_wires, qdf = cfg.max_quotient_degree_factor;
-    const u32 nchunks = (nr + qdf - 1) / qdf, num_prods = nchunks - 1;
-    const size_t ncs = c->cs->ncols, nzs = (size_t)nch * (1 + num_prods), nq = (size_t)nch * qdf;
+    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height, nw = cfg.num_wires;
+    const Counts cnt(cfg);
+    const size_t n = cnt.n, ncs = c->cs->ncols, nzs = cnt.nzs, nq = cnt.nq;
     hipStream_t st = ctx->stream;
     gb_status s;
     auto get_ext = get_ext_challenge<F>;
@@ -1091,24 +1112,258 @@ struct RetryHint {   // gb_prove_retry: the one wire that differs from the witne
 // option "check_witness" (check_host.inc): GB_ERR_UNSATISFIED where the witness breaks a gate or a copy constraint
 template <class F>
 gb_status check_before_commit(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs);
+
+// prover.rs:399-404: an opening point inside the subgroup would divide by zero in prove_openings
+template <class F>
+gb_status check_opening_point(gb_ctx* ctx, typename F::E zeta, u32 degree_bits) {
+    for (u32 i = 0; i < degree_bits; i++) zeta = F::emul(zeta, zeta);
+    if (gbk::eis_one<F>(zeta)) return fail(ctx, GB_ERR_OPENING_IN_SUBGROUP, "Opening point is in the subgroup.");
+    return GB_OK;
+}
+
+// The routed wire VALUES [num_routed][n] on the device in device form, as the Z computation reads them (only these columns:
+// prover.rs:497-505): the caller's device matrix where canonical words are the device form, else a pooled copy, converted
+template <class F>
+gb_status routed_wires_device_form(Circuit<F>* c, TmpAlloc& tmp, ColSrc witness, uint32_t flags, const typename F::T** out) {
+    typedef typename F::T T;
+    typedef Host<F> HF;
+    gb_ctx* ctx = c->ctx;
+    const bool dev = (flags & GB_INPUT_DEVICE) != 0;
+    if (HF::device_form_is_canonical && dev && witness.base) {
+        *out = static_cast<const T*>(witness.base);
+        return GB_OK;
+    }
+    const u32 nr = c->cfg.num_routed_wires;
+    const size_t n = (size_t)1 << c->cfg.degree_bits;
+    T* copy = tmp.get<T>((size_t)nr * n);
+    if (!copy) return fail(ctx, GB_ERR_OOM, "witness copy");
+    if (!copy_columns(witness, nr, n * sizeof(T), copy, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream))
+        return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
+    if (flags & GB_INPUT_P3_REPR) gbk::reduce_words<F>(copy, (size_t)nr * n, ctx->stream);
+    else HF::to_device_form(copy, copy, (size_t)nr * n, ctx->stream);
+    *out = copy;
+    return GB_OK;
+}
+
+// zero-knowledge (config.zero_knowledge && PlonkOracle::*.blinding, prover.rs:267,334,382): the wires, Zs and quotient
+// leaves end in SALT_SIZE salt elements.  salts = [3][SALT_SIZE][N] canonical values in LDE-point order, in the same
+// memory space as the witness; the Zs / quotient commitments run on device data, so host salts are staged once.
+// GB_SALTS_FROM_SEED: `salts` is 32 seed bytes on the host (checked non-null by the entries); column j of commitment s is the
+// stream (seed, (GB_STREAM_SALTS, s, j)), elements 0 .. N - 1, generated just before the commitment that consumes it into ONE
+// block of SALT_SIZE x N elements the three commitments share - the stream orders commitment s's bitrev_copy out of the block
+// before the generator of commitment s + 1 writes it.
+template <class F>
+struct SaltPlan {
+    typedef typename F::T T;
+    const T *w = nullptr, *z = nullptr, *q = nullptr;   // of the wires / Zs / quotient commitment; null: no salts
+    bool seeded = false;
+    gbk::rnd::Key key{};
+    size_t N = 0;
+    gb_status init(gb_ctx* ctx, TmpAlloc& tmp, const void* salts, bool from_seed, uint32_t flags, size_t lde_size) {
+        seeded = from_seed;
+        N = lde_size;
+        w = static_cast<const T*>(salts);
+        const size_t per = (size_t)GB_SALT_SIZE * N;
+        if (seeded) {
+            const u32 nonce[3] = {gbk::rnd::STREAM_SALTS, 0, 0};
+            key = gbk::rnd::make_key(static_cast<const uint8_t*>(salts), nonce);
+            T* block = tmp.get<T>(per);
+            if (!block) return fail(ctx, GB_ERR_OOM, "salt block");
+            w = z = q = block;
+        } else if (salts && (flags & GB_INPUT_DEVICE)) {
+            z = w + per;
+            q = w + 2 * per;
+        } else if (salts) {
+            T* stage = tmp.get<T>(2 * per);
+            if (!stage) return fail(ctx, GB_ERR_OOM, "salt staging");
+            HIP_TRY(ctx, hipMemcpyAsync(stage, w + per, 2 * per * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            if (flags & GB_INPUT_P3_REPR) p3_to_canonical_dev<F>(stage, 2 * per, ctx->stream);   // the Zs / quotient commits take device salts: canonical
+            z = stage;
+            q = stage + per;
+        }
+        return GB_OK;
+    }
+    gb_status generate(gb_ctx* ctx, u32 commitment) {   // the seeded block for this commitment; no-op without the flag
+        if (!seeded) return GB_OK;
+        key.nonce[1] = commitment;
+        if (!gbk::random_elements<F>(key, 0, N, GB_SALT_SIZE, const_cast<T*>(w), N, ctx->stream))
+            return fail(ctx, GB_ERR_HIP, "launch of k_random_elements failed");
+        return GB_OK;
+    }
+};
+
+// gb_prove_retry, the retry of an attempt that failed on this circuit with one wire re-drawn: everything of that attempt's wires
+// commitment is still right except the column of that wire - its coefficients, its LDE - and what the leaf sponges absorbed from
+// it on.  The kept state moves into the caller's guarded variables first: from there on it is that call's to release or to keep.
+template <class F>
+gb_status recommit_retry_column(Circuit<F>* c, TmpAlloc& tmp, ColSrc witness, uint32_t flags, const RetryHint& hint, gb_batch** wires_out,
+                                typename F::T** wit_vals_out, SegKeep* seg_out, size_t* wit_mont_cols_out) {
+    typedef typename F::T T;
+    typedef Host<F> HF;
+    constexpr u32 H = F::H;
+    gb_ctx* ctx = c->ctx;
+    const gb_circuit_config& cfg = c->cfg;
+    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, capH = cfg.cap_height, nw = cfg.num_wires;
+    const size_t n = (size_t)1 << lg, N = n << r, col_bytes = n * sizeof(T), wit_bytes = (size_t)nw * col_bytes;
+    const bool dev_witness = (flags & GB_INPUT_DEVICE) != 0;
+    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;   // host words of the reference's field types (commit() rejects it for device input)
+    hipStream_t st = ctx->stream;
+    gb_status s;
+    Scope sc(ctx, "compute wires commitment");
+    gb_batch* const wires = *wires_out = c->retry.wires;
+    T*& wit_vals = *wit_vals_out = (T*)c->retry.wit_vals;
+    const SegKeep seg = *seg_out = c->retry.seg;
+    const size_t wit_mont_cols = *wit_mont_cols_out = c->retry.wit_mont_cols;
+    c->retry.wires = nullptr; c->retry.wit_vals = nullptr; c->retry.seg = SegKeep{};   // owned by the call from here on
+    c->drop_retry();                                          // (a witness front's matrix, had it not taken it: not this witness)
+    const T* col_src;                                         // the wire's column of the new witness, device form
+    bool canonical_col = false;                               // ... or canonical, where commit() left the kept copy so
+    if (dev_witness) {                                        // the caller's device matrix holds it: copy, convert
+        if (wit_vals) { pool_free(ctx, wit_vals, wit_bytes); wit_vals = nullptr; }   // (a host attempt's copy: not this one's)
+        T* colbuf = tmp.get<T>(n);
+        if (!colbuf) return fail(ctx, GB_ERR_OOM, "witness column");
+        HIP_TRY(ctx, hipMemcpyAsync(colbuf, witness.col(hint.wire, col_bytes), col_bytes, hipMemcpyDeviceToDevice, st));
+        HF::to_device_form(colbuf, colbuf, n, st);
+        col_src = colbuf;
+    } else {                                                  // host matrix: the kept device copy, one element re-written
+        if (ctx->retry_verify) {   // option "retry_verify": is the caller's matrix the kept one but for that element?  (a debugging
+                                   // aid: one column at a time through a host buffer of n elements)
+            std::unique_ptr<T[]> back(new (std::nothrow) T[n]);
+            if (!back) return fail(ctx, GB_ERR_OOM, "host allocation failed");
+            for (u32 w = 0; w < nw; w++) {
+                HIP_TRY(ctx, hipMemcpyAsync(back.get(), wit_vals + (size_t)w * n, col_bytes, hipMemcpyDeviceToHost, st));
+                HIP_TRY(ctx, hipStreamSynchronize(st));
+                const T* hw = reinterpret_cast<const T*>(witness.col(w, col_bytes));
+                for (size_t i = 0; i < n; i++) {
+                    if (w == hint.wire && i == hint.row) continue;
+                    const T canon = p3 ? (T)HF::p3_to_canonical(hw[i]) : hw[i];
+                    if (back[i] != (w < wit_mont_cols ? F::enc(canon) : canon))   // the caller's guards release wires / wit_vals / seg
+                        return fail(ctx, GB_ERR_INVALID, "gb_prove_retry: the witness differs from the failed attempt's in more than witness[wire][row]");
+                }
+            }
+        }
+        T v = reinterpret_cast<const T*>(witness.col(hint.wire, col_bytes))[hint.row];
+        if (p3) v = (T)HF::p3_to_canonical(v);
+        if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
+        canonical_col = !HF::device_form_is_canonical && hint.wire >= wit_mont_cols;   // that column of the kept copy is as uploaded
+        const T vd = canonical_col ? v : F::enc(v);
+        T* cell = wit_vals + (size_t)hint.wire * n + hint.row;
+        if (sizeof(T) == 8) {
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)vd, 1, st));
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)((u32*)cell + 1), (int)(u32)((u64)vd >> 32), 1, st));
+        } else {
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)vd, 1, st));
+        }
+        col_src = wit_vals + (size_t)hint.wire * n;
+    }
+    const typename HF::Tables* tabs;
+    const typename HF::Cosets* cos;
+    if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
+    if ((s = cosets_for<F>(ctx, lg, r, F::generator(), false, &cos))) return s;
+    if ((s = ensure(ctx, ctx->scratch, 2 * n * sizeof(T)))) return s;
+    T* coeffs_col = (T*)wires->coeffs + (size_t)hint.wire * n;
+    T* lde_col = (T*)wires->lde + (size_t)hint.wire * N;
+    {
+        Scope si(ctx, "IFFT");
+        if (canonical_col) {
+            if (!HF::intt_canonical(const_cast<T*>(col_src), coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st))
+                return fail(ctx, GB_ERR_INVALID, "internal: canonical-input transform not available for this size");
+        } else {
+            gbk::intt_columns<F>(col_src, coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st);
+        }
+    }
+    { Scope sf(ctx, "FFT + blinding"); gbk::lde_columns<F>(coeffs_col, lde_col, 1, *tabs, *cos, st); }
+    {
+        Scope sm(ctx, "build Merkle tree");
+        T* lv = (T*)wires->levels;
+        { Scope sl(ctx, "hash leaves"); HF::merkle_leaves_segment((const T*)wires->lde, N, seg.start, nw, (T*)seg.state, true, 0, lv, st); }
+        for (u32 k = 0; k < lg + r - capH; k++)
+            HF::merkle_level(lv + H * level_offset(N, k), lv + H * level_offset(N, k + 1), N >> (k + 1), st);
+    }
+    return GB_OK;
+}
+
+// The opening set at zeta and g zeta (plonk/proof.rs:346-387), then the front of the proof bytes - the three caps and the
+// OpeningSet (serialization/mod.rs:2103-2118, 1514-1529) - and observe_openings (plonk/proof.rs:388-440)
+template <class F>
+gb_status open_and_serialize(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb_batch* zs, gb_batch* quot, typename F::E zeta,
+                             const typename F::T* const caps[3], typename Host<F>::Challenger& ch, Bytes& ob) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 D = F::D, H = F::H;
+    gb_ctx* ctx = c->ctx;
+    const gb_circuit_config& cfg = c->cfg;
+    const Counts cnt(cfg);
+    const u32 nch = cfg.num_challenges, nw = cfg.num_wires;
+    const size_t n = cnt.n, ncs = c->cs->ncols, nzs = cnt.nzs, nq = cnt.nq, cap_elems = (size_t)H << cfg.cap_height;
+    hipStream_t st = ctx->stream;
+    const E zeta_next = F::escale(zeta, F::two_adic_generator(cnt.lg));
+    // o_* hold D canonical words per opened polynomial
+    std::vector<T> o_cs(D * ncs), o_w(D * nw), o_z(D * nzs), o_zn(D * nzs), o_q(D * nq);
+    {
+        Scope sc(ctx, "construct the opening set");
+        gbk::ExtPowTab<F> zt, znt;
+        {
+            const E pts[2] = {zeta, zeta_next};
+            const size_t ns[2] = {n, n};
+            gbk::ExtPowTab<F>* tabs2[2] = {&zt, &znt};
+            if (gb_status s = make_ext_powtabs<F>(ctx, tmp, 2, pts, ns, tabs2)) return s;
+        }
+        E* ztab = tmp.get<E>(n);
+        E* zntab = tmp.get<E>(n);
+        const size_t nchk = (n + 4095) / 4096;
+        const size_t nout = ncs + nw + 2 * nzs + nq;
+        E* partial = tmp.get<E>(nchk * nout);
+        E* outs = tmp.get<E>(nout);
+        if (!ztab || !zntab || !partial || !outs) return fail(ctx, GB_ERR_OOM, "openings workspace");
+        gbk::ext_pow_tables<F>(gbk::ExtPowTables<F>{{zt, znt}, {ztab, zntab}}, 2, n, st);
+        const gbk::EvalJobs<F> ej{{{(const T*)c->cs->coeffs, ztab, (u32)ncs}, {(const T*)wires->coeffs, ztab, nw}, {(const T*)zs->coeffs, ztab, (u32)nzs},
+                                   {(const T*)zs->coeffs, zntab, (u32)nzs}, {(const T*)quot->coeffs, ztab, (u32)nq}}};
+        gbk::eval_columns<F>(ej, 5, n, partial, outs, st);
+        std::vector<E> host(nout);
+        if (gb_status rs = read_back(ctx, host.data(), outs, nout * sizeof(E))) return rs;
+        const E* h = host.data();
+        auto take = [&](std::vector<T>& dst, size_t count) {
+            for (size_t i = 0; i < count; i++, h++)
+                for (u32 k = 0; k < D; k++) dst[D * i + k] = (T)F::dec(F::coord(*h, k));
+        };
+        take(o_cs, ncs); take(o_w, nw); take(o_z, nzs); take(o_zn, nzs); take(o_q, nq);
+    }
+    const size_t es = sizeof(T);
+    for (u32 i = 0; i < 3; i++) ob.put(caps[i], cap_elems * es);            // wires, Zs, quotient
+    const size_t nconst = cfg.num_selectors + cfg.num_constants;
+    ob.put(o_cs.data(), D * nconst * es);                                   // constants
+    ob.put(o_cs.data() + D * nconst, D * (ncs - nconst) * es);             // plonk_sigmas
+    ob.put(o_w.data(), o_w.size() * es);                                    // wires
+    ob.put(o_z.data(), D * nch * es);                                       // plonk_zs
+    ob.put(o_zn.data(), D * nch * es);                                      // plonk_zs_next
+    ob.put(o_z.data() + D * nch, D * (nzs - nch) * es);                     // partial_products
+    ob.put(o_q.data(), o_q.size() * es);                                    // quotient_polys
+    // observe_openings: zeta batch then zeta_next batch
+    ch.observe(o_cs.data(), o_cs.size());
+    ch.observe(o_w.data(), o_w.size());
+    ch.observe(o_z.data(), D * nch);
+    ch.observe(o_z.data() + D * nch, D * (nzs - nch));
+    ch.observe(o_q.data(), o_q.size());
+    ch.observe(o_zn.data(), D * nch);
+    return GB_OK;
+}
+
 template <class F>
 gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs,
                 const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
     typedef typename F::T T;
-    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // `salts` is 32 seed bytes on the host (checked non-null by the entries)
-    flags &= ~(uint32_t)GB_SALTS_FROM_SEED;
     typedef typename F::E E;
     typedef Host<F> HF;
-    constexpr u32 D = F::D, H = F::H;
+    constexpr u32 H = F::H;
+    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;
+    flags &= ~(uint32_t)GB_SALTS_FROM_SEED;
     gb_ctx* ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const gb_circuit_config& cfg = c->cfg;
-    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height;
-    const size_t n = (size_t)1 << lg, N = n << r;
-    const u32 nr = cfg.num_routed_wires, nw = cfg.num_wires, qdf = cfg.max_quotient_degree_factor;
-    const u32 nchunks = (nr + qdf - 1) / qdf, num_prods = nchunks - 1;
-    const size_t ncs = c->cs->ncols, nzs = (size_t)nch * (1 + num_prods), nq = (size_t)nch * qdf;
-    const size_t cap_elems = (size_t)H << capH;
+    const Counts cnt(cfg);
+    const u32 lg = cfg.degree_bits, r = cfg.rate_bits, nch = cfg.num_challenges, capH = cfg.cap_height, nw = cfg.num_wires;
+    const size_t n = cnt.n, N = cnt.N, cap_elems = (size_t)H << capH;
     hipStream_t st = ctx->stream;
     TmpAlloc tmp(ctx);
     gb_status s;
@@ -1122,54 +1377,14 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         for (size_t i = 0; i < canon.size(); i++) v[i] = F::enc(canon[i]);
         return v;
     };
-    auto get_ext = [](typename HF::Challenger& ch) {  // get_extension_challenge: D base challenges -> device form
-        E e = F::ezero();
-        for (u32 k = 0; k < D; k++) F::set_coord(e, k, F::enc(ch.get()));
-        return e;
-    };
 
     std::vector<T> pis(num_public_inputs);
     for (size_t i = 0; i < num_public_inputs; i++) pis[i] = (T)public_inputs[i];
     T pi_hash[H];
     HF::hash_no_pad(pis.data(), pis.size(), pi_hash);  // prover.rs:244
+    SaltPlan<F> salt;
+    if ((s = salt.init(ctx, tmp, salts, seeded, flags, N))) return s;
 
-    // zero-knowledge (config.zero_knowledge && PlonkOracle::*.blinding, prover.rs:267,334,382): the wires, Zs and quotient
-    // leaves end in SALT_SIZE salt elements.  salts = [3][SALT_SIZE][N] canonical values in LDE-point order, in the same
-    // memory space as the witness; the Zs / quotient commitments run on device data, so host salts are staged once.
-    // GB_SALTS_FROM_SEED: column j of commitment s is the stream (seed, (GB_STREAM_SALTS, s, j)), elements 0 .. N - 1, generated
-    // just before the commitment that consumes it into ONE block of SALT_SIZE x N elements the three commitments share - the
-    // stream orders commitment s's bitrev_copy out of the block before the generator of commitment s + 1 writes it.
-    const T* salt_w = static_cast<const T*>(salts);
-    const T *salt_z = nullptr, *salt_q = nullptr;
-    gbk::rnd::Key salt_key{};
-    auto seeded_salts = [&](u32 commitment) -> gb_status {   // no-op without the flag
-        if (!seeded) return GB_OK;
-        salt_key.nonce[1] = commitment;
-        if (!gbk::random_elements<F>(salt_key, 0, N, GB_SALT_SIZE, const_cast<T*>(salt_w), N, st))
-            return fail(ctx, GB_ERR_HIP, "launch of k_random_elements failed");
-        return GB_OK;
-    };
-    const uint32_t wires_flags = flags | (seeded ? GB_SALTS_DEVICE : 0u);
-    if (seeded) {
-        const u32 nonce[3] = {gbk::rnd::STREAM_SALTS, 0, 0};
-        salt_key = gbk::rnd::make_key(static_cast<const uint8_t*>(salts), nonce);
-        T* block = tmp.get<T>((size_t)GB_SALT_SIZE * N);
-        if (!block) return fail(ctx, GB_ERR_OOM, "salt block");
-        salt_w = salt_z = salt_q = block;
-    } else if (salts) {
-        const size_t per = (size_t)GB_SALT_SIZE * N;
-        if (flags & GB_INPUT_DEVICE) {
-            salt_z = salt_w + per;
-            salt_q = salt_w + 2 * per;
-        } else {
-            T* stage = tmp.get<T>(2 * per);
-            if (!stage) return fail(ctx, GB_ERR_OOM, "salt staging");
-            HIP_TRY(ctx, hipMemcpyAsync(stage, salt_w + per, 2 * per * sizeof(T), hipMemcpyHostToDevice, st));
-            if (flags & GB_INPUT_P3_REPR) p3_to_canonical_dev<F>(stage, 2 * per, st);   // the Zs / quotient commits take device salts: canonical
-            salt_z = stage;
-            salt_q = stage + per;
-        }
-    }
     // ---- wires commitment (prover.rs:261-272)
     // A host witness crosses PCIe once: commit() uploads it in column chunks into `wit_vals` (device form), overlapped with the
     // inverse NTTs, and the permutation argument below reads the routed columns from there.
@@ -1177,7 +1392,7 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
     // (c->retry): they are pool blocks of their own, released by the guard unless they are kept.
     T* wit_vals = nullptr;
     const size_t wit_bytes = (size_t)nw * n * sizeof(T);
-    size_t wit_mont_cols = nr;   // leading columns of wit_vals in device form: what the Z computation reads (commit() may convert more)
+    size_t wit_mont_cols = cfg.num_routed_wires;   // leading columns of wit_vals in device form: what the Z computation reads (commit() may convert more)
     SegKeep seg;
     struct KeepGuard {
         gb_ctx* ctx; T** wit; size_t wit_bytes; SegKeep* seg;
@@ -1186,110 +1401,27 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             if (seg->state) pool_free(ctx, seg->state, seg->bytes);
         }
     } keep_guard{ctx, &wit_vals, wit_bytes, &seg};
-    // the retry of an attempt that failed on this circuit, one wire re-drawn: everything of that attempt's wires commitment is
-    // still right except the column of that wire - its coefficients, its LDE - and what the leaf sponges absorbed from it on
     const bool dev_witness = (flags & GB_INPUT_DEVICE) != 0;
-    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;   // host words of the reference's field types (commit() rejects it for device input)
-    const size_t col_bytes = n * sizeof(T);
     const bool incremental = hint && c->retry.wires && c->retry.seg.state && !salts && (dev_witness || c->retry.wit_vals) &&
                              hint->wire < nw && hint->wire >= c->retry.seg.start && hint->row < n;
     if (incremental) {
-        Scope sc(ctx, "compute wires commitment");
-        wires = c->retry.wires; wit_vals = (T*)c->retry.wit_vals; seg = c->retry.seg;
-        wit_mont_cols = c->retry.wit_mont_cols;
-        c->retry = gb_circuit::RetryKeep{};                       // owned by this call from here on
-        const T* col_src;                                         // the wire's column of the new witness, device form
-        bool canonical_col = false;                               // ... or canonical, where commit() left the kept copy so
-        if (dev_witness) {                                        // the caller's device matrix holds it: copy, convert
-            if (wit_vals) { pool_free(ctx, wit_vals, wit_bytes); wit_vals = nullptr; }   // (a host attempt's copy: not this one's)
-            T* colbuf = tmp.get<T>(n);
-            if (!colbuf) return fail(ctx, GB_ERR_OOM, "witness column");
-            HIP_TRY(ctx, hipMemcpyAsync(colbuf, witness.col(hint->wire, col_bytes), col_bytes, hipMemcpyDeviceToDevice, st));
-            HF::to_device_form(colbuf, colbuf, n, st);
-            col_src = colbuf;
-        } else {                                                  // host matrix: the kept device copy, one element re-written
-            if (ctx->retry_verify) {   // option "retry_verify": is the caller's matrix the kept one but for that element?  (a debugging
-                                       // aid: one column at a time through a host buffer of n elements)
-                std::unique_ptr<T[]> back(new (std::nothrow) T[n]);
-                if (!back) return fail(ctx, GB_ERR_OOM, "host allocation failed");
-                for (u32 w = 0; w < nw; w++) {
-                    HIP_TRY(ctx, hipMemcpyAsync(back.get(), wit_vals + (size_t)w * n, col_bytes, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(ctx, hipStreamSynchronize(st));
-                    const T* hw = reinterpret_cast<const T*>(witness.col(w, col_bytes));
-                    for (size_t i = 0; i < n; i++) {
-                        if (w == hint->wire && i == hint->row) continue;
-                        const T canon = p3 ? (T)HF::p3_to_canonical(hw[i]) : hw[i];
-                        if (back[i] != (w < wit_mont_cols ? F::enc(canon) : canon))   // the guards of this call release wires / wit_vals / seg
-                            return fail(ctx, GB_ERR_INVALID, "gb_prove_retry: the witness differs from the failed attempt's in more than witness[wire][row]");
-                    }
-                }
-            }
-            T v = reinterpret_cast<const T*>(witness.col(hint->wire, col_bytes))[hint->row];
-            if (p3) v = (T)HF::p3_to_canonical(v);
-            if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
-            canonical_col = !HF::device_form_is_canonical && hint->wire >= wit_mont_cols;   // that column of the kept copy is as uploaded
-            const T vd = canonical_col ? v : F::enc(v);
-            T* cell = wit_vals + (size_t)hint->wire * n + hint->row;
-            if (sizeof(T) == 8) {
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)vd, 1, st));
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)((u32*)cell + 1), (int)(u32)((u64)vd >> 32), 1, st));
-            } else {
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)vd, 1, st));
-            }
-            col_src = wit_vals + (size_t)hint->wire * n;
-        }
-        const typename HF::Tables* tabs;
-        const typename HF::Cosets* cos;
-        if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
-        if ((s = cosets_for<F>(ctx, lg, r, F::generator(), false, &cos))) return s;
-        if ((s = ensure(ctx, ctx->scratch, 2 * n * sizeof(T)))) return s;
-        T* coeffs_col = (T*)wires->coeffs + (size_t)hint->wire * n;
-        T* lde_col = (T*)wires->lde + (size_t)hint->wire * N;
-        {
-            Scope si(ctx, "IFFT");
-            if (canonical_col) {
-                if (!HF::intt_canonical(const_cast<T*>(col_src), coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st))
-                    return fail(ctx, GB_ERR_INVALID, "internal: canonical-input transform not available for this size");
-            } else {
-                gbk::intt_columns<F>(col_src, coeffs_col, (T*)ctx->scratch.p, 1, *tabs, st);
-            }
-        }
-        { Scope sf(ctx, "FFT + blinding"); gbk::lde_columns<F>(coeffs_col, lde_col, 1, *tabs, *cos, st); }
-        {
-            Scope sm(ctx, "build Merkle tree");
-            T* lv = (T*)wires->levels;
-            { Scope sl(ctx, "hash leaves"); HF::merkle_leaves_segment((const T*)wires->lde, N, seg.start, nw, (T*)seg.state, true, 0, lv, st); }
-            for (u32 k = 0; k < lg + r - capH; k++)
-                HF::merkle_level(lv + H * level_offset(N, k), lv + H * level_offset(N, k + 1), N >> (k + 1), st);
-        }
+        if ((s = recommit_retry_column<F>(c, tmp, witness, flags, *hint, &wires, &wit_vals, &seg, &wit_mont_cols))) return s;
     } else {
         c->drop_retry();
         if (ctx->check_witness && (s = check_before_commit<F>(c, witness, flags, public_inputs, num_public_inputs))) return s;
-        if (!(flags & GB_INPUT_DEVICE) && lg >= 12) {
+        if (!dev_witness && lg >= 12) {
             void* p = nullptr;
             if (pool_alloc(ctx, wit_bytes, &p) != hipSuccess) return fail(ctx, GB_ERR_OOM, "witness staging");
             wit_vals = (T*)p;
         }
         Scope sc(ctx, "compute wires commitment");
-        if ((s = seeded_salts(0))) return s;
-        if ((s = commit<F>(ctx, witness, nw, lg, r, capH, salt_w, wires_flags, false, &wires, wit_vals, salts ? nullptr : &seg, &wit_mont_cols)))
-            return (flags & GB_INPUT_DEVICE) ? s : finish_host_commit(ctx, s, nullptr);   // the witness is the caller's again
+        if ((s = salt.generate(ctx, 0))) return s;
+        if ((s = commit<F>(ctx, witness, nw, lg, r, capH, salt.w, flags | (seeded ? GB_SALTS_DEVICE : 0u), false, &wires, wit_vals,
+                           salts ? nullptr : &seg, &wit_mont_cols)))
+            return dev_witness ? s : finish_host_commit(ctx, s, nullptr);   // the witness is the caller's again
     }
-    // the Z computation needs the routed wire VALUES on the device (device form) as well
-    const T* wit_dev = nullptr;
-    if (wit_vals) {
-        wit_dev = wit_vals;
-    } else if (HF::device_form_is_canonical && (flags & GB_INPUT_DEVICE) && witness.base) {
-        wit_dev = static_cast<const T*>(witness.base);
-    } else {
-        T* wit_copy = tmp.get<T>((size_t)nr * n);
-        if (!wit_copy) return fail(ctx, GB_ERR_OOM, "witness copy");
-        if (!copy_columns(witness, nr, col_bytes, wit_copy, (flags & GB_INPUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
-            return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
-        if (p3) gbk::reduce_words<F>(wit_copy, (size_t)nr * n, st);
-        else HF::to_device_form(wit_copy, wit_copy, (size_t)nr * n, st);
-        wit_dev = wit_copy;
-    }
+    const T* wit_dev = wit_vals;   // the Z computation needs the routed wire VALUES on the device (device form) as well
+    if (!wit_dev && (s = routed_wires_device_form<F>(c, tmp, witness, flags, &wit_dev))) return s;
     std::vector<T> cap;
     typename HF::Challenger ch;
     ch.observe(c->digest, H);
@@ -1325,8 +1457,8 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
             s = fail(ctx, GB_ERR_PERM_ARG_ZERO, "InvZeroPermArg (armed by gb_test_arm_perm_arg_failure)");
         }
         if (s) return failed(s);
-        if ((s = seeded_salts(1))) return s;
-        if ((s = commit<F>(ctx, zs_vals, nzs, lg, r, capH, salt_z, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, false, &zs))) {
+        if ((s = salt.generate(ctx, 1))) return s;
+        if ((s = commit<F>(ctx, zs_vals, cnt.nzs, lg, r, capH, salt.z, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, false, &zs))) {
             if (defer) (void)hipMemsetAsync(c->perm_err, 0, 4, st);   // nobody will ask the deferred question: leave the word zero
             return s;
         }
@@ -1346,76 +1478,21 @@ gb_status prove(Circuit<F>* c, ColSrc witness, uint32_t flags, const uint64_t* p
         Scope sc(ctx, "compute quotient polys");
         T* chunks = nullptr;
         if ((s = stage_quotient_polys<F>(c, tmp, wires, zs, pi_hash, betas_d, gammas_d, alphas, &chunks))) return s;
-        if ((s = seeded_salts(2))) return s;
-        if ((s = commit<F>(ctx, chunks, nq, lg, r, capH, salt_q, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, true, &quot))) return s;
+        if ((s = salt.generate(ctx, 2))) return s;
+        if ((s = commit<F>(ctx, chunks, cnt.nq, lg, r, capH, salt.q, GB_INPUT_DEVICE | GB_INPUT_DEVICE_FORM, true, &quot))) return s;
     }
     if ((s = read_cap<F>(quot, cap))) return s;
     ch.observe(cap.data(), cap.size());
-    const E zeta = get_ext(ch);
-    {
-        E zn = zeta;
-        for (u32 i = 0; i < lg; i++) zn = F::emul(zn, zn);
-        if (gbk::eis_one<F>(zn)) return fail(ctx, GB_ERR_OPENING_IN_SUBGROUP, "Opening point is in the subgroup.");
-    }
-    const E zeta_next = F::escale(zeta, F::two_adic_generator(lg));
+    const E zeta = get_ext_challenge<F>(ch);
+    if ((s = check_opening_point<F>(ctx, zeta, lg))) return s;
 
-    // ---- openings (plonk/proof.rs:346-387); o_* hold D canonical words per opened polynomial
-    std::vector<T> o_cs(D * ncs), o_w(D * nw), o_z(D * nzs), o_zn(D * nzs), o_q(D * nq);
-    gbk::ExtPowTab<F> zt, znt;
-    {
-        Scope sc(ctx, "construct the opening set");
-        {
-            const E pts[2] = {zeta, zeta_next};
-            const size_t ns[2] = {n, n};
-            gbk::ExtPowTab<F>* tabs2[2] = {&zt, &znt};
-            if ((s = make_ext_powtabs<F>(ctx, tmp, 2, pts, ns, tabs2))) return s;
-        }
-        E* ztab = tmp.get<E>(n);
-        E* zntab = tmp.get<E>(n);
-        const size_t nchk = (n + 4095) / 4096;
-        const size_t nout = ncs + nw + 2 * nzs + nq;
-        E* partial = tmp.get<E>(nchk * nout);
-        E* outs = tmp.get<E>(nout);
-        if (!ztab || !zntab || !partial || !outs) return fail(ctx, GB_ERR_OOM, "openings workspace");
-        gbk::ext_pow_tables<F>(gbk::ExtPowTables<F>{{zt, znt}, {ztab, zntab}}, 2, n, st);
-        const gbk::EvalJobs<F> ej{{{(const T*)c->cs->coeffs, ztab, (u32)ncs}, {(const T*)wires->coeffs, ztab, nw}, {(const T*)zs->coeffs, ztab, (u32)nzs},
-                                   {(const T*)zs->coeffs, zntab, (u32)nzs}, {(const T*)quot->coeffs, ztab, (u32)nq}}};
-        gbk::eval_columns<F>(ej, 5, n, partial, outs, st);
-        std::vector<E> host(nout);
-        if (gb_status rs = read_back(ctx, host.data(), outs, nout * sizeof(E))) return rs;
-        const E* h = host.data();
-        auto take = [&](std::vector<T>& dst, size_t count) {
-            for (size_t i = 0; i < count; i++, h++)
-                for (u32 k = 0; k < D; k++) dst[D * i + k] = (T)F::dec(F::coord(*h, k));
-        };
-        take(o_cs, ncs); take(o_w, nw); take(o_z, nzs); take(o_zn, nzs); take(o_q, nq);
-    }
-    // proof bytes: caps + OpeningSet (serialization/mod.rs:2103-2118, 1514-1529)
+    // ---- openings (plonk/proof.rs:346-440), then prove_openings (fri/oracle.rs:187-246) -> FriProof bytes
     Bytes ob(proof_out, proof_cap);
-    const size_t es = sizeof(T);
-    ob.put(cap_wires.data(), cap_elems * es);
-    ob.put(cap_zs.data(), cap_elems * es);
-    ob.put(cap.data(), cap_elems * es);       // the quotient's, read for zeta above
-    const size_t nconst = cfg.num_selectors + cfg.num_constants;
-    ob.put(o_cs.data(), D * nconst * es);                                   // constants
-    ob.put(o_cs.data() + D * nconst, D * (ncs - nconst) * es);             // plonk_sigmas
-    ob.put(o_w.data(), o_w.size() * es);                                    // wires
-    ob.put(o_z.data(), D * nch * es);                                       // plonk_zs
-    ob.put(o_zn.data(), D * nch * es);                                      // plonk_zs_next
-    ob.put(o_z.data() + D * nch, D * (nzs - nch) * es);                     // partial_products
-    ob.put(o_q.data(), o_q.size() * es);                                    // quotient_polys
-    // observe_openings (plonk/proof.rs:388-440): zeta batch then zeta_next batch
-    ch.observe(o_cs.data(), o_cs.size());
-    ch.observe(o_w.data(), o_w.size());
-    ch.observe(o_z.data(), D * nch);
-    ch.observe(o_z.data() + D * nch, D * (nzs - nch));
-    ch.observe(o_q.data(), o_q.size());
-    ch.observe(o_zn.data(), D * nch);
-
-    // ---- prove_openings (fri/oracle.rs:187-246) -> FriProof bytes
+    const T* const caps[3] = {cap_wires.data(), cap_zs.data(), cap.data()};   // (the quotient's, read for zeta above)
+    if ((s = open_and_serialize<F>(c, tmp, wires, zs, quot, zeta, caps, ch, ob))) return s;
     if ((s = stage_prove_openings<F>(c, tmp, wires, zs, quot, zeta, ch, ob))) return s;
     ob.u64v(num_public_inputs);  // ProofWithPublicInputs (serialization/mod.rs:2134-2151)
-    ob.put(pis.data(), pis.size() * es);
+    ob.put(pis.data(), pis.size() * sizeof(T));
     *proof_len = ob.len;
     if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
     if (!proof_out || ob.len > proof_cap) return fail(ctx, GB_ERR_BUFFER_TOO_SMALL, "proof buffer too small");
@@ -1465,24 +1542,15 @@ static gb_status abi_zs_partial_products(Circuit<F>* c, ColSrc witness, uint32_t
     gb_ctx* ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const gb_circuit_config& cfg = c->cfg;
-    const u32 nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
-    const size_t n = (size_t)1 << cfg.degree_bits, nzs = (size_t)nch * ((nr + qdf - 1) / qdf);
+    const Counts cnt(cfg);
+    const u32 nch = cfg.num_challenges;
+    const size_t n = cnt.n, nzs = cnt.nzs;
     hipStream_t st = ctx->stream;
     TmpAlloc tmp(ctx);
     const bool dev = flags & GB_INPUT_DEVICE, p3 = flags & GB_INPUT_P3_REPR;
     if (p3 && dev) return fail(ctx, GB_ERR_INVALID, "GB_INPUT_P3_REPR describes host memory; device inputs are canonical");
     const T* wit_dev;
-    if (HF::device_form_is_canonical && dev && witness.base) {
-        wit_dev = static_cast<const T*>(witness.base);
-    } else {  // only the routed columns are read (prover.rs:497-505)
-        T* copy = tmp.get<T>((size_t)nr * n);
-        if (!copy) return fail(ctx, GB_ERR_OOM, "witness copy");
-        if (!copy_columns(witness, nr, n * sizeof(T), copy, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st))
-            return fail(ctx, GB_ERR_HIP, "copy of the routed wires failed");
-        if (p3) gbk::reduce_words<F>(copy, (size_t)nr * n, st);
-        else HF::to_device_form(copy, copy, (size_t)nr * n, st);
-        wit_dev = copy;
-    }
+    if (gb_status s = routed_wires_device_form<F>(c, tmp, witness, flags, &wit_dev)) return s;
     std::vector<T> bd(nch), gd(nch);
     for (u32 k = 0; k < nch; k++) {
         const T b = static_cast<const T*>(betas)[k], g = static_cast<const T*>(gammas)[k];
@@ -1519,8 +1587,9 @@ static gb_status abi_quotient_polys(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     gb_ctx* ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const gb_circuit_config& cfg = c->cfg;
-    const u32 nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
-    const size_t n = (size_t)1 << cfg.degree_bits, nzs = (size_t)nch * ((nr + qdf - 1) / qdf), nq = (size_t)nch * qdf;
+    const Counts cnt(cfg);
+    const u32 nch = cfg.num_challenges;
+    const size_t n = cnt.n, nzs = cnt.nzs, nq = cnt.nq;
     if (gb_status s = check_stage_batch<F>(c, wires, cfg.num_wires, "wires")) return s;
     if (gb_status s = check_stage_batch<F>(c, zs, nzs, "zs_partial_products")) return s;
     hipStream_t st = ctx->stream;
@@ -1585,8 +1654,8 @@ static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs
     gb_ctx* ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const gb_circuit_config& cfg = c->cfg;
-    const u32 nch = cfg.num_challenges, nr = cfg.num_routed_wires, qdf = cfg.max_quotient_degree_factor;
-    const size_t nzs = (size_t)nch * ((nr + qdf - 1) / qdf), nq = (size_t)nch * qdf;
+    const Counts cnt(cfg);
+    const size_t nzs = cnt.nzs, nq = cnt.nq;
     if (gb_status s = check_stage_batch<F>(c, wires, cfg.num_wires, "wires")) return s;
     if (gb_status s = check_stage_batch<F>(c, zs, nzs, "zs_partial_products")) return s;
     if (gb_status s = check_stage_batch<F>(c, quot, nq, "quotient")) return s;
@@ -1598,11 +1667,7 @@ static gb_status abi_prove_openings(Circuit<F>* c, gb_batch* wires, gb_batch* zs
         if ((u64)z >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical zeta");
         F::set_coord(zeta, k, F::enc(z));
     }
-    {   // prover.rs:399-404: an opening point inside the subgroup would divide by zero in prove_openings
-        E zn = zeta;
-        for (u32 i = 0; i < cfg.degree_bits; i++) zn = F::emul(zn, zn);
-        if (gbk::eis_one<F>(zn)) return fail(ctx, GB_ERR_OPENING_IN_SUBGROUP, "Opening point is in the subgroup.");
-    }
+    if (gb_status s = check_opening_point<F>(ctx, zeta, cfg.degree_bits)) return s;
     TmpAlloc tmp(ctx);
     Bytes ob(out, out_cap);
     if (gb_status s = stage_prove_openings<F>(c, tmp, wires, zs, quot, zeta, ch, ob)) return s;
@@ -1799,357 +1864,6 @@ static gb_status verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, cons
     return GB_OK;
 }
 
-// ---------------------------------------------------------------------------------------------- the partition witness
-// prove_with_partition_witness's first timed step, "compute full witness" = partition_witness.full_witness() (plonk/prover.rs:
-// 160-183, iop/witness.rs:359-371), from the reference's own object: `values` holds PartitionWitness.values (None as zero), one
-// entry per target.  Compaction staged[k] = values[reps[k]] (reps ascending: one streaming pass, canonicalised and range-checked as
-// it goes, by the context's copy threads into page-locked memory), upload of the K staged elements, k_expand_partition.  The
-// upload is not overlapped with the transforms the way the chunks of a host matrix are (DESIGN.md section 8).
-template <class F>
-static bool partition_value(const void* values, uint64_t target, bool p3, typename F::T* out) {
-    typedef typename F::T T;
-    T v = static_cast<const T*>(values)[target];
-    if (p3) v = (T)Host<F>::p3_to_canonical(F::reduce_word(v));
-    *out = v;
-    return (u64)v < F::ORDER;
-}
-
-template <class F>
-static gb_status partition_public_inputs(Circuit<F>* c, const void* values, bool p3, std::vector<uint64_t>* pis) {
-    pis->resize(c->part.pi_reps.size());
-    for (size_t i = 0; i < pis->size(); i++) {
-        typename F::T v;
-        if (!partition_value<F>(values, c->part.pi_reps[i], p3, &v)) return fail(c->ctx, GB_ERR_INVALID, "non-canonical witness element");
-        (*pis)[i] = (uint64_t)v;
-    }
-    return GB_OK;
-}
-
-// values -> matrix_dev [num_wires][n], canonical words, on the context's stream
-template <class F>
-static gb_status expand_partition_stage(Circuit<F>* c, TmpAlloc& tmp, const void* values, uint32_t flags, typename F::T* matrix_dev) {
-    typedef typename F::T T;
-    gb_ctx* ctx = c->ctx;
-    gb_circuit::Partition& part = c->part;
-    hipStream_t st = ctx->stream;
-    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
-    const size_t K = part.reps.size(), bytes = K * sizeof(T);
-    Scope sc(ctx, "compute full witness");
-    if (part.staged_host_bytes < bytes) {
-        if (part.staged_host) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            (void)hipHostFree(part.staged_host);
-            part.staged_host = nullptr;
-            part.staged_host_bytes = 0;
-        }
-        HIP_TRY(ctx, hipHostMalloc(&part.staged_host, bytes, hipHostMallocDefault));
-        part.staged_host_bytes = bytes;
-    }
-    if (!part.staged_read) HIP_TRY(ctx, hipEventCreateWithFlags(&part.staged_read, hipEventDisableTiming));
-    else HIP_TRY(ctx, hipEventSynchronize(part.staged_read));   // the upload of the call before has left the staging block
-    {
-        Scope s1(ctx, "partition compaction");
-        T* staged = static_cast<T*>(part.staged_host);
-        const uint32_t* reps = part.reps.data();
-        std::atomic<bool> bad{false};
-        auto run = [&](size_t k0, size_t k1) {
-            bool ok = true;
-            for (size_t k = k0; k < k1; k++) ok &= partition_value<F>(values, reps[k], p3, staged + k);
-            if (!ok) bad.store(true, std::memory_order_relaxed);
-        };
-        const size_t nthreads = K >= ((size_t)1 << 18) && ctx->copy_threads > 1 ? (size_t)ctx->copy_threads : 1;
-        if (nthreads == 1) {
-            run(0, K);
-        } else {
-            std::vector<std::thread> workers;
-            const size_t per = (K + nthreads - 1) / nthreads;
-            try {   // a thread the system refuses: the calling thread takes its share
-                for (size_t i = 1; i < nthreads; i++) workers.emplace_back(run, std::min(K, i * per), std::min(K, (i + 1) * per));
-            } catch (...) {
-            }
-            const size_t started = workers.size() + 1;
-            run(0, std::min(K, per));
-            if (started < nthreads) run(std::min(K, started * per), K);
-            for (auto& w : workers) w.join();
-        }
-        if (bad.load()) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
-    }
-    T* staged_dev = tmp.get<T>(K);
-    if (!staged_dev) return fail(ctx, GB_ERR_OOM, "partition staging");
-    {
-        Scope s2(ctx, "partition upload");
-        HIP_TRY(ctx, hipMemcpyAsync(staged_dev, part.staged_host, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipEventRecord(part.staged_read, st));
-    }
-    {
-        Scope s3(ctx, "partition expansion");
-        gbk::expand_partition<F>(part.slots_dev, staged_dev, matrix_dev, c->cfg.degree_bits, c->cfg.num_wires, st);
-    }
-    if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
-    return GB_OK;
-}
-
-template <class F>
-static gb_status prove_partition(Circuit<F>* c, const void* values, uint32_t flags, const void* salts, void* proof_out, size_t proof_cap,
-                                 size_t* proof_len, const RetryHint* hint) {
-    typedef typename F::T T;
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const gb_circuit_config& cfg = c->cfg;
-    const size_t n = (size_t)1 << cfg.degree_bits, N = n << cfg.rate_bits;
-    const u32 nw = cfg.num_wires;
-    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
-    hipStream_t st = ctx->stream;
-    gb_status s;
-    std::vector<uint64_t> pis;
-    if ((s = partition_public_inputs<F>(c, values, p3, &pis))) return s;
-    struct MatrixGuard {   // the expanded matrix: a pool block, handed to c->part when the attempt leaves retry state behind
-        gb_ctx* ctx; void* p; size_t bytes;
-        ~MatrixGuard() { if (p) pool_free(ctx, p, bytes); }
-    } matrix{ctx, nullptr, (size_t)nw * n * sizeof(T)};
-    TmpAlloc tmp(ctx);
-    // the retry (prover.rs:186-226): the caller re-drew values[representative_map[row * num_wires + wire]] - one cell of the matrix
-    // the failed attempt kept, provided that cell is alone in its class (prover_data.random_wire is)
-    bool incremental = hint && !salts && c->retry.wires && c->retry.seg.state && c->part.matrix && hint->wire < nw && hint->row < n;
-    if (incremental) {
-        uint32_t slot = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&slot, c->part.slots_dev + hint->row * nw + hint->wire, sizeof slot, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        T v;
-        if (slot >= c->part.reps.size() || c->part.is_shared_slot(slot)) {
-            incremental = false;
-        } else {
-            // (every other used entry is the failed attempt's, which was checked then)
-            if (!partition_value<F>(values, c->part.reps[slot], p3, &v)) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
-            matrix.p = c->part.matrix;
-            c->part.matrix = nullptr;
-            c->part.matrix_bytes = 0;
-            Scope sc(ctx, "compute full witness");
-            u32* cell = reinterpret_cast<u32*>(static_cast<T*>(matrix.p) + (size_t)hint->wire * n + hint->row);
-            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)v, 1, st));
-            if (sizeof(T) == 8) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(cell + 1), (int)(u32)((u64)v >> 32), 1, st));
-        }
-    }
-    if (!incremental) {
-        hint = nullptr;
-        c->drop_retry();   // (with the matrix of an earlier attempt) before the new one is allocated
-        if (pool_alloc(ctx, matrix.bytes, &matrix.p) != hipSuccess) { matrix.p = nullptr; return fail(ctx, GB_ERR_OOM, "partition witness matrix"); }
-        if ((s = expand_partition_stage<F>(c, tmp, values, flags, static_cast<T*>(matrix.p)))) return s;
-    }
-    // the proof proper: the device-witness path of prove().  Host salts go to the device with the witness.
-    const T* salts_dev = nullptr;
-    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // the seed goes to prove() as it is
-    if (seeded) {
-        salts_dev = static_cast<const T*>(salts);
-    } else if (salts) {
-        const size_t count = (size_t)3 * GB_SALT_SIZE * N;
-        T* sd = tmp.get<T>(count);
-        if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
-        HIP_TRY(ctx, hipMemcpyAsync(sd, salts, count * sizeof(T), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));   // the salts are the caller's again
-        if (p3) p3_to_canonical_dev<F>(sd, count, st);
-        salts_dev = sd;
-    }
-    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE | (seeded ? GB_SALTS_FROM_SEED : 0u), pis.data(), pis.size(), salts_dev, proof_out,
-                 proof_cap, proof_len, hint);
-    if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
-        c->part.matrix = matrix.p;
-        c->part.matrix_bytes = matrix.bytes;
-        matrix.p = nullptr;
-    }
-    return s;
-}
-
-template <class F>
-static gb_status abi_expand_partition(Circuit<F>* c, const void* values, uint32_t flags, void* witness_dev_out) {
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TmpAlloc tmp(ctx);
-    return expand_partition_stage<F>(c, tmp, values, flags, static_cast<typename F::T*>(witness_dev_out));
-}
-
-
-// ---------------------------------------------------------------------------------------------- the witness generators
-// prove()'s first call, generate_partial_witness (plonk/prover.rs:136-158; "run N generators", iop/generator.rs:25-106), on the
-// device: the inputs are uploaded and scattered to their classes, the schedule's launches (generators.hpp) fill the values array -
-// one canonical word per class, the slots of the partition map first - and one block comes back: the public inputs' values and
-// the error word.  k_expand_partition then reads the front of that array where gb_prove_partition reads its staged upload.
-template <class F>
-static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_values, uint32_t flags, typename F::T* values_dev,
-                                std::vector<uint64_t>* pis) {
-    typedef typename F::T T;
-    namespace GN = gbk::gen;
-    gb_ctx* ctx = c->ctx;
-    gb_circuit::Generators& g = c->gens;
-    const GN::Schedule& sc = g.sched;
-    hipStream_t st = ctx->stream;
-    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
-    const size_t ni = sc.input_cls.size(), npi = sc.pi_cls.size();
-    Scope scope(ctx, "run generators");
-    // the inputs: canonical, below p, and equal where two of them name one class (witness.rs:340-350).  They go up in slices of
-    // the context's page-locked arena (stage_up), each filled and handed to one asynchronous copy; only a context that has no
-    // arena copies from pageable memory, and waits for that copy before the buffer goes
-    auto canonical = [&](size_t i) {
-        T v = static_cast<const T*>(input_values)[i];
-        return p3 ? (T)Host<F>::p3_to_canonical(F::reduce_word(v)) : v;
-    };
-    HIP_TRY(ctx, hipMemsetAsync(values_dev, 0, (size_t)sc.num_classes * sizeof(T), st));
-    HIP_TRY(ctx, hipMemsetAsync(g.err_dev, 0, GN::ERROR_WORDS * sizeof(uint32_t), st));
-    if (ni) {
-        T* in_dev = tmp.get<T>(ni);
-        if (!in_dev) return fail(ctx, GB_ERR_OOM, "generator inputs");
-        const size_t slice = XFER_UP_BYTES / 4 / sizeof(T);
-        std::vector<T> pageable;
-        for (size_t i0 = 0; i0 < ni; i0 += slice) {
-            const size_t count = std::min(slice, ni - i0);
-            T* host = static_cast<T*>(stage_up(ctx, count * sizeof(T)));
-            const bool staged = host != nullptr;
-            if (!staged) {
-                pageable.resize(count);
-                host = pageable.data();
-            }
-            for (size_t i = i0; i < i0 + count; i++) {
-                const T v = canonical(i);
-                if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element (input " + std::to_string(i) + ")");
-                host[i - i0] = v;
-                if (sc.input_first[i] != i && canonical(sc.input_first[i]) != v)
-                    return fail(ctx, GB_ERR_INVALID, "Partition containing target " + std::to_string(sc.class_reps[sc.input_cls[i]]) +
-                                " was set twice with different values (inputs " + std::to_string(sc.input_first[i]) + " and " + std::to_string(i) + ")");
-            }
-            HIP_TRY(ctx, hipMemcpyAsync(in_dev + i0, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-            if (!staged) HIP_TRY(ctx, hipStreamSynchronize(st));
-        }
-        gbk::scatter_inputs<F>(g.input_cls_dev, in_dev, (u32)ni, values_dev, st);
-    }
-    gbk::run_generators<F>(g.device, sc.launches.data(), sc.launches.size(), sc.level_off.data(), values_dev, g.err_dev, st);
-    u64* back_dev = tmp.get<u64>(npi + GN::ERROR_WORDS);
-    if (!back_dev) return fail(ctx, GB_ERR_OOM, "generator read-back");
-    gbk::gather_public<F>(g.pi_cls_dev, (u32)npi, values_dev, g.err_dev, back_dev, st);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
-    std::vector<u64> back(npi + GN::ERROR_WORDS);
-    {
-        ReadBack rb(ctx);
-        if (gb_status rs = rb.add(back.data(), back_dev, back.size() * sizeof(u64))) return rs;
-        if (gb_status rs = rb.finish()) return rs;
-    }
-    const u32 code = (u32)back[npi], record = (u32)back[npi + 1], cls = (u32)back[npi + 2];
-    if (code != GN::ERR_NONE) {
-        const std::string rec = "generator record " + std::to_string(record) + ": ";
-        const std::string target = cls < sc.class_reps.size() ? std::to_string(sc.class_reps[cls]) : std::string("?");
-        switch (code) {
-            case GN::ERR_SET_TWICE:
-                return fail(ctx, GB_ERR_INVALID, rec + "Partition containing target " + target + " was set twice with different values");
-            case GN::ERR_SWAP_NOT_BOOLEAN:
-                return fail(ctx, GB_ERR_INVALID, rec + "the swap wire (target " + target + ") is neither 0 nor 1");
-            case GN::ERR_ACCESS_INDEX:
-                return fail(ctx, GB_ERR_INVALID, rec + "Access index (target " + target + ") is larger than the vector size");
-            case GN::ERR_SPLIT_TOO_LARGE:
-                return fail(ctx, GB_ERR_INVALID, rec + "Integer too large to fit in given number of limbs");
-            case GN::ERR_DIVIDE_BY_ZERO:
-                if (cls >= sc.class_reps.size()) return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (INV in a generator program)");
-                return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (the denominator at target " + target + ")");
-            case GN::ERR_NO_SQUARE_ROOT:
-                return fail(ctx, GB_ERR_INVALID, rec + "SQRT of a non-residue in a generator program (called `Option::unwrap()` on a `None` value)");
-            case GN::ERR_NOT_BOOLEAN:
-                return fail(ctx, GB_ERR_INVALID, rec + "not a bool (target " + target + ")");
-            case GN::ERR_NO_PROGRAM_TABLES:   // the schedule always sets program_regs with a program generator: not reachable from the ABI
-                return fail(ctx, GB_ERR_HIP, rec + "a program generator was run without the program tables");
-            default:
-                return fail(ctx, GB_ERR_HIP, rec + "unknown generator error word");
-        }
-    }
-    if (pis) pis->assign(back.begin(), back.begin() + npi);
-    return GB_OK;
-}
-
-template <class F>
-static gb_status prove_inputs(Circuit<F>* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
-                              size_t proof_cap, size_t* proof_len, const RetryHint* hint) {
-    typedef typename F::T T;
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const gb_circuit_config& cfg = c->cfg;
-    const size_t n = (size_t)1 << cfg.degree_bits, N = n << cfg.rate_bits;
-    const u32 nw = cfg.num_wires;
-    const bool p3 = (flags & GB_INPUT_P3_REPR) != 0;
-    hipStream_t st = ctx->stream;
-    gb_circuit::Generators& g = c->gens;
-    gb_status s;
-    std::vector<uint64_t> pis;
-    struct MatrixGuard {
-        gb_ctx* ctx; void* p; size_t bytes;
-        ~MatrixGuard() { if (p) pool_free(ctx, p, bytes); }
-    } matrix{ctx, nullptr, (size_t)nw * n * sizeof(T)};
-    TmpAlloc tmp(ctx);
-    // the retry (prover.rs:186-226): the caller re-drew ONE input.  Where no generator reads, writes or checks its class, no public
-    // input is in it and one wire cell alone carries it - prover_data.random_wire - the matrix and the public inputs the failed
-    // attempt kept are right but for that cell (prove_partition's incremental path from here on)
-    bool incremental = hint && !salts && c->retry.wires && c->retry.seg.state && c->part.matrix && g.kept_for == c->part.matrix &&
-                       hint->wire < nw && hint->row < n;
-    if (incremental) {
-        const uint64_t target = hint->row * nw + hint->wire;
-        auto it = std::lower_bound(g.input_index.begin(), g.input_index.end(), std::make_pair(target, (uint32_t)0));
-        if (it == g.input_index.end() || it->first != target || !g.input_fast[it->second]) {
-            incremental = false;
-        } else {
-            T v = static_cast<const T*>(input_values)[it->second];
-            if (p3) v = (T)Host<F>::p3_to_canonical(F::reduce_word(v));
-            if ((u64)v >= F::ORDER) return fail(ctx, GB_ERR_INVALID, "non-canonical witness element");
-            pis = g.kept_pis;
-            matrix.p = c->part.matrix;
-            c->part.matrix = nullptr;
-            c->part.matrix_bytes = 0;
-            Scope sc(ctx, "compute full witness");
-            u32* cell = reinterpret_cast<u32*>(static_cast<T*>(matrix.p) + (size_t)hint->wire * n + hint->row);
-            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)cell, (int)(u32)(u64)v, 1, st));
-            if (sizeof(T) == 8) HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(cell + 1), (int)(u32)((u64)v >> 32), 1, st));
-        }
-    }
-    g.kept_for = nullptr;
-    if (!incremental) {
-        hint = nullptr;
-        c->drop_retry();
-        if (pool_alloc(ctx, matrix.bytes, &matrix.p) != hipSuccess) { matrix.p = nullptr; return fail(ctx, GB_ERR_OOM, "witness matrix"); }
-        T* values_dev = tmp.get<T>(g.sched.num_classes);
-        if (!values_dev) return fail(ctx, GB_ERR_OOM, "generated values");
-        if ((s = generate_stage<F>(c, tmp, input_values, flags, values_dev, &pis))) return s;
-        Scope sc(ctx, "compute full witness");   // full_witness(): the expansion alone, straight from the generated values
-        gbk::expand_partition<F>(c->part.slots_dev, values_dev, static_cast<T*>(matrix.p), cfg.degree_bits, nw, st);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, GB_ERR_HIP, "kernel launch failed");
-    }
-    const T* salts_dev = nullptr;
-    const bool seeded = (flags & GB_SALTS_FROM_SEED) != 0;   // the seed goes to prove() as it is
-    if (seeded) {
-        salts_dev = static_cast<const T*>(salts);
-    } else if (salts) {
-        const size_t count = (size_t)3 * GB_SALT_SIZE * N;
-        T* sd = tmp.get<T>(count);
-        if (!sd) return fail(ctx, GB_ERR_OOM, "salt staging");
-        HIP_TRY(ctx, hipMemcpyAsync(sd, salts, count * sizeof(T), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));   // the salts are the caller's again
-        if (p3) p3_to_canonical_dev<F>(sd, count, st);
-        salts_dev = sd;
-    }
-    s = prove<F>(c, ColSrc(matrix.p), GB_INPUT_DEVICE | (seeded ? GB_SALTS_FROM_SEED : 0u), pis.data(), pis.size(), salts_dev, proof_out,
-                 proof_cap, proof_len, hint);
-    if (s == GB_ERR_PERM_ARG_ZERO && c->retry.wires) {   // prove() kept its wires commitment: keep the matrix it was made from
-        c->part.matrix = matrix.p;
-        c->part.matrix_bytes = matrix.bytes;
-        g.kept_for = matrix.p;
-        g.kept_pis = pis;
-        matrix.p = nullptr;
-    }
-    return s;
-}
-
-template <class F>
-static gb_status abi_generate_partition(Circuit<F>* c, const void* input_values, uint32_t flags, void* values_dev_out) {
-    gb_ctx* ctx = c->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    TmpAlloc tmp(ctx);
-    return generate_stage<F>(c, tmp, input_values, flags, static_cast<typename F::T*>(values_dev_out), nullptr);
-}
-
 extern "C" {
 
 gb_status gb_pow_grind(gb_ctx* ctx, uint32_t field, const void* sponge_state, uint32_t witness_pos, uint32_t min_leading_zeros,
@@ -2179,7 +1893,7 @@ gb_status gb_batch_eval_ext(gb_batch* b, const void* z, void* out) try {
     if (!b) return fail(nullptr, GB_ERR_INVALID, "null batch");
     if (!z || !out) return fail(b->ctx, GB_ERR_INVALID, "null argument");
     if (!b->coeffs) return fail(b->ctx, GB_ERR_INVALID, "a stand-alone Merkle tree holds no polynomials");
-    return b->field == GB_GOLDILOCKS ? batch_eval_ext<GlF>(b, z, out) : batch_eval_ext<BbF>(b, z, out);
+    return by_field(b->field, [&](auto f) { return batch_eval_ext<decltype(f)>(b, z, out); });
 } GB_CATCH(b ? b->ctx : nullptr)
 
 static gb_status check_circuit_cfg(gb_ctx* ctx, const gb_circuit_config* cfg, ColSrc constants_sigmas, const void* k_is,
@@ -2231,8 +1945,7 @@ static gb_status circuit_create_dummy(gb_ctx* ctx, const gb_circuit_config* cfg,
     for (u32 g = 0; g < 3; g++) gs.g[g] = gb_gate{GB_GATE_NOOP, 0, 0, 0, 3};
     gs.g[cfg->gate_constant] = gb_gate{GB_GATE_CONSTANT, cfg->num_constants, 0, 0, 3};
     gs.g[cfg->gate_pi] = gb_gate{GB_GATE_PUBLIC_INPUT, hout, 0, 0, 3};
-    return cfg->field == GB_GOLDILOCKS ? circuit_create<GlF>(ctx, cfg, gs, false, constants_sigmas, k_is, flags, out)
-                                       : circuit_create<BbF>(ctx, cfg, gs, false, constants_sigmas, k_is, flags, out);
+    return by_field(cfg->field, [&](auto f) { return circuit_create<decltype(f)>(ctx, cfg, gs, false, constants_sigmas, k_is, flags, out); });
 }
 
 gb_status gb_circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const void* constants_sigmas, const void* k_is,
@@ -2251,16 +1964,13 @@ static gb_status circuit_create_general(gb_ctx* ctx, const gb_circuit_config* cf
     if (gb_status s = check_circuit_cfg(ctx, cfg, constants_sigmas, k_is, flags, out)) return s;
     gbk::gates::GateSet gs{};
     ParsedPrograms progs;
-    const bool gl = cfg->field == GB_GOLDILOCKS;
-    if (table)
-        if (gb_status s = gl ? parse_programs<GlF>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs)
-                             : parse_programs<BbF>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs))
-            return s;
-    const gbk::gates::ProgramSet* ps = table ? &progs.set : nullptr;
-    if (gb_status s = gl ? build_gate_set<GlF>(ctx, cfg, gates, num_gates, &gs, ps) : build_gate_set<BbF>(ctx, cfg, gates, num_gates, &gs, ps))
-        return s;
-    return gl ? circuit_create<GlF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out, &progs)
-              : circuit_create<BbF>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out, &progs);
+    return by_field(cfg->field, [&](auto f) -> gb_status {
+        typedef decltype(f) F;
+        if (table)
+            if (gb_status s = parse_programs<F>(ctx, cfg, table->words, table->offsets, table->num_programs, &progs)) return s;
+        if (gb_status s = build_gate_set<F>(ctx, cfg, gates, num_gates, &gs, table ? &progs.set : nullptr)) return s;
+        return circuit_create<F>(ctx, cfg, gs, true, constants_sigmas, k_is, flags, out, &progs);
+    });
 }
 
 gb_status gb_circuit_create_gates(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates,
@@ -2296,8 +2006,9 @@ static gb_status verifier_create_checked(gb_ctx* ctx, const gb_circuit_config* c
         cfg->max_quotient_degree_factor == 0 || cfg->arity_bits > 8 || cfg->cap_height > 24 ||
         cfg->degree_bits + cfg->rate_bits > (cfg->field == GB_GOLDILOCKS ? 32u : 27u) || cfg->num_wires > 4096)
         return fail(ctx, GB_ERR_INVALID, "bad circuit config");
-    return cfg->field == GB_GOLDILOCKS ? verifier_create<GlF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, table)
-                                       : verifier_create<BbF>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, table);
+    return by_field(cfg->field, [&](auto f) {
+        return verifier_create<decltype(f)>(ctx, cfg, gates, num_gates, k_is, constants_sigmas_cap, circuit_digest, out, table);
+    });
 }
 gb_status gb_verifier_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gb_gate* gates, uint32_t num_gates, const void* k_is,
                              const void* constants_sigmas_cap, const void* circuit_digest, gb_circuit** out) try {
@@ -2328,7 +2039,7 @@ gb_status gb_circuit_free(gb_circuit* c) try {
 gb_status gb_circuit_constants_sigmas_commitment(gb_circuit* c, gb_batch** out) try {
     if (!c || !out) return fail(c ? c->ctx : nullptr, GB_ERR_INVALID, "null argument");
     if (c->verify_only) return fail(c->ctx, GB_ERR_INVALID, "this circuit object was made by gb_verifier_create: it holds no commitment");
-    *out = c->field == GB_GOLDILOCKS ? static_cast<Circuit<GlF>*>(c)->cs : static_cast<Circuit<BbF>*>(c)->cs;
+    *out = by_field(c, [](auto* cf) { return cf->cs; });
     return GB_OK;
 } GB_CATCH_CIRCUIT(c)
 
@@ -2357,14 +2068,25 @@ gb_status gb_circuit_fri_reduction_arity_bits(gb_circuit* c, uint32_t* arity_bit
     return GB_OK;
 } GB_CATCH_CIRCUIT(c)
 
+// What every gb_prove* entry checks of its proof buffer and its salts, behind the checks of its own witness argument (all of
+// them GB_ERR_INVALID): the matrix entries below, the witness fronts of witness_host.inc
+static gb_status prove_guard(gb_circuit* c, uint32_t flags, const void* salts, const size_t* proof_len) {
+    gb_ctx* ctx = c->ctx;
+    if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
+    if (c->cfg.zero_knowledge && !salts)
+        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
+    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
+    return need_arity_list(c);
+}
+
 static gb_status prove_entry(gb_circuit* c, ColSrc witness, uint32_t flags, const uint64_t* public_inputs,
                              size_t num_public_inputs, const void* salts, void* proof_out, size_t proof_cap, size_t* proof_len,
                              const RetryHint* hint = nullptr) {
     if (!c) return fail(nullptr, GB_ERR_INVALID, "null circuit");
     gb_ctx* ctx = c->ctx;
-    if (!witness || !proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
+    if (!witness) return fail(ctx, GB_ERR_INVALID, "null argument");
     if (flags & ~GB_PROVE_FLAGS) return fail(ctx, GB_ERR_INVALID, "unknown bits in flags");
-    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
     if (witness.ptrs && !c->verify_only)
         for (u32 w = 0; w < c->cfg.num_wires; w++)
             if (!witness.ptrs[w]) return fail(ctx, GB_ERR_INVALID, "null wire column pointer");
@@ -2372,13 +2094,10 @@ static gb_status prove_entry(gb_circuit* c, ColSrc witness, uint32_t flags, cons
     if (num_public_inputs != c->cfg.num_public_inputs)  // the reference reads them off the witness: always CommonCircuitData's count
         return fail(ctx, GB_ERR_INVALID, "Number of public inputs doesn't match circuit data.");
     if (c->verify_only) return fail(ctx, GB_ERR_INVALID, "this circuit object was made by gb_verifier_create: it can only verify");
-    if (c->cfg.zero_knowledge && !salts)
-        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with gb_prove_salted (the salts are a host input)");
-    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
-    if (gb_status s = need_arity_list(c)) return s;
-    return c->field == GB_GOLDILOCKS
-               ? prove<GlF>(static_cast<Circuit<GlF>*>(c), witness, flags, public_inputs, num_public_inputs, salts, proof_out, proof_cap, proof_len, hint)
-               : prove<BbF>(static_cast<Circuit<BbF>*>(c), witness, flags, public_inputs, num_public_inputs, salts, proof_out, proof_cap, proof_len, hint);
+    if (gb_status s = prove_guard(c, flags, salts, proof_len)) return s;
+    return by_field(c, [&](auto* cf) {
+        return prove(cf, witness, flags, public_inputs, num_public_inputs, salts, proof_out, proof_cap, proof_len, hint);
+    });
 }
 
 gb_status gb_prove(gb_circuit* c, const void* witness, uint32_t flags, const uint64_t* public_inputs, size_t num_public_inputs,
@@ -2447,8 +2166,7 @@ static gb_status zs_entry(gb_circuit* c, ColSrc witness, uint32_t flags, const v
     if (witness.ptrs)
         for (u32 w = 0; w < c->cfg.num_routed_wires; w++)
             if (!witness.ptrs[w]) return fail(c->ctx, GB_ERR_INVALID, "null wire column pointer");
-    return c->field == GB_GOLDILOCKS ? abi_zs_partial_products<GlF>(static_cast<Circuit<GlF>*>(c), witness, flags, betas, gammas, values_out)
-                                     : abi_zs_partial_products<BbF>(static_cast<Circuit<BbF>*>(c), witness, flags, betas, gammas, values_out);
+    return by_field(c, [&](auto* cf) { return abi_zs_partial_products(cf, witness, flags, betas, gammas, values_out); });
 }
 
 gb_status gb_zs_partial_products(gb_circuit* c, const void* witness, uint32_t flags, const void* betas, const void* gammas,
@@ -2461,288 +2179,13 @@ gb_status gb_zs_partial_products_cols(gb_circuit* c, const void* const* wire_col
     return zs_entry(c, ColSrc::columns(wire_cols), flags, betas, gammas, values_out);
 } GB_CATCH_CIRCUIT(c)
 
-// ---- the partition witness (templates above: prove_partition, expand_partition_stage)
-gb_status gb_circuit_set_partition(gb_circuit* c, const uint64_t* representative_map, uint64_t num_targets,
-                                   const uint64_t* public_input_targets, size_t num_public_inputs) try {
-    if (gb_status s = stage_guard(c)) return s;
-    gb_ctx* ctx = c->ctx;
-    const uint64_t cells = (uint64_t)c->cfg.num_wires << c->cfg.degree_bits;
-    gbk::partition::SlotMap m;
-    const char* msg = "";
-    if (const int ms = gbk::partition::build_slot_map(representative_map, num_targets, cells, public_input_targets, num_public_inputs,
-                                                      c->cfg.num_public_inputs, &m, &msg))
-        return fail(ctx, (gb_status)ms, std::string("gb_circuit_set_partition: ") + msg);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    c->drop_retry();
-    c->drop_partition();
-    void* p = nullptr;
-    HIP_TRY(ctx, hipMalloc(&p, std::max<size_t>(4, m.slots.size() * sizeof(uint32_t))));
-    c->part.slots_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, hipMemcpy(p, m.slots.data(), m.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->part.rep_map.resize(num_targets);
-    for (uint64_t t = 0; t < num_targets; t++) c->part.rep_map[t] = (uint32_t)representative_map[t];
-    c->part.reps = std::move(m.reps);
-    c->part.pi_reps = std::move(m.pi_reps);
-    c->part.shared = std::move(m.shared);
-    c->part.num_targets = num_targets;
-    c->part.set = true;
-    return GB_OK;
-} GB_CATCH_CIRCUIT(c)
-
-static gb_status partition_guard(gb_circuit* c, const void* values, uint32_t flags, uint32_t allowed = GB_PUBLIC_INPUT_FLAGS) {
-    if (gb_status s = stage_guard(c)) return s;
-    if (!values) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    if (flags & ~allowed) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
-    if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the partition witness is a host object: GB_INPUT_DEVICE does not apply");
-    if (!c->part.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_partition has not been called on this circuit");
-    return GB_OK;
-}
-
-static gb_status prove_partition_entry(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out,
-                                       size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
-    if (gb_status s = partition_guard(c, values, flags, GB_PROVE_FLAGS)) return s;
-    gb_ctx* ctx = c->ctx;
-    if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
-    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
-    if (c->cfg.zero_knowledge && !salts)
-        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
-    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
-    if (gb_status s = need_arity_list(c)) return s;
-    return c->field == GB_GOLDILOCKS
-               ? prove_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, salts, proof_out, proof_cap, proof_len, hint)
-               : prove_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, salts, proof_out, proof_cap, proof_len, hint);
-}
-
-gb_status gb_prove_partition(gb_circuit* c, const void* values, uint32_t flags, const void* salts, void* proof_out, size_t proof_cap,
-                             size_t* proof_len) try {
-    return prove_partition_entry(c, values, flags, salts, proof_out, proof_cap, proof_len);
-} GB_CATCH_CIRCUIT(c)
-
-gb_status gb_prove_partition_retry(gb_circuit* c, const void* values, uint32_t flags, uint32_t wire, uint64_t row, void* proof_out,
-                                   size_t proof_cap, size_t* proof_len) try {
-    const RetryHint hint{wire, row};
-    return prove_partition_entry(c, values, flags, nullptr, proof_out, proof_cap, proof_len, &hint);
-} GB_CATCH_CIRCUIT(c)
-
-gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags, void* witness_dev_out) try {
-    if (gb_status s = partition_guard(c, values, flags)) return s;
-    if (!witness_dev_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    return c->field == GB_GOLDILOCKS ? abi_expand_partition<GlF>(static_cast<Circuit<GlF>*>(c), values, flags, witness_dev_out)
-                                     : abi_expand_partition<BbF>(static_cast<Circuit<BbF>*>(c), values, flags, witness_dev_out);
-} GB_CATCH_CIRCUIT(c)
-
-// ---- generator programs: witness generators as data (generator_programs.hpp checks them, generators.hpp gen_program runs them)
-gb_status gb_circuit_set_generator_programs(gb_circuit* c, const uint64_t* program_words, const uint32_t* program_offsets,
-                                            uint32_t num_programs) try {
-    namespace GN = gbk::gen;
-    if (gb_status s = stage_guard(c)) return s;
-    gb_ctx* ctx = c->ctx;
-    if (!c->part.set)
-        return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generator_programs: gb_circuit_set_partition has not been called on this circuit");
-    GN::GeneratorPrograms parsed;
-    std::string msg;
-    const uint64_t order = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::ORDER : (uint64_t)BbF::ORDER;
-    if (!GN::parse_generator_programs(program_words, program_offsets, num_programs, order, c->cfg.num_constants, &parsed, &msg))
-        return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generator_programs: " + msg);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    c->drop_retry();
-    c->drop_generator_programs();   // and the schedule built on the old ones
-    if (parsed.empty()) return GB_OK;
-    std::vector<uint64_t> lits(parsed.lits.size());   // device form, once
-    for (size_t i = 0; i < lits.size(); i++)
-        lits[i] = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::enc(parsed.lits[i]) : (uint64_t)BbF::enc(parsed.lits[i]);
-    auto upload = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    gb_circuit::GeneratorPrograms& gp = c->gen_programs;
-    void* p = nullptr;
-    HIP_TRY(ctx, upload(parsed.headers.data(), parsed.headers.size() * sizeof(GN::ProgramHeader), &p));
-    gp.headers_dev = static_cast<GN::ProgramHeader*>(p);
-    HIP_TRY(ctx, upload(parsed.instrs.data(), parsed.instrs.size() * sizeof(uint64_t), &p));
-    gp.instrs_dev = static_cast<uint64_t*>(p);
-    HIP_TRY(ctx, upload(lits.data(), lits.size() * sizeof(uint64_t), &p));
-    gp.lits_dev = static_cast<uint64_t*>(p);
-    gp.host = std::move(parsed);
-    return GB_OK;
-} GB_CATCH_CIRCUIT(c)
-
-// ---- the witness generators (templates above: generate_stage, prove_inputs)
-// replaces the host's generate_partial_witness (plonk/prover.rs:136-158, iop/generator.rs:25-106): the generators as data, scheduled once
-gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint64_t num_generators, const uint64_t* input_targets,
-                                    uint64_t num_inputs, const uint64_t* constants, uint32_t flags) try {
-    namespace GN = gbk::gen;
-    if (gb_status s = stage_guard(c)) return s;
-    gb_ctx* ctx = c->ctx;
-    if (flags) return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generators: unknown bits in flags");
-    if (!c->part.set) return fail(ctx, GB_ERR_INVALID, "gb_circuit_set_generators: gb_circuit_set_partition has not been called on this circuit");
-    static_assert(sizeof(gb_generator) == sizeof(GN::Record) && offsetof(gb_generator, a) == offsetof(GN::Record, a) &&
-                  offsetof(gb_generator, b) == offsetof(GN::Record, b) && offsetof(gb_generator, gate) == offsetof(GN::Record, gate), "gb_generator");
-    std::vector<GN::GateDesc> gates(c->gates.num_gates);
-    for (u32 i = 0; i < c->gates.num_gates; i++) {
-        const gb_gate& gg = c->gates.g[i];
-        gates[i] = GN::GateDesc{gg.kind, gg.param, gg.param2, gg.param3};
-    }
-    GN::CircuitDesc d;
-    d.representative_map = c->part.rep_map.data();
-    d.num_targets = c->part.num_targets;
-    d.num_wires = c->cfg.num_wires;
-    d.degree_bits = c->cfg.degree_bits;
-    d.num_constants = c->cfg.num_constants;
-    d.ext_degree = c->field == GB_GOLDILOCKS ? GlF::D : BbF::D;
-    d.order = c->field == GB_GOLDILOCKS ? (uint64_t)GlF::ORDER : (uint64_t)BbF::ORDER;
-    d.slot_reps = c->part.reps.data();
-    d.num_slots = c->part.reps.size();
-    d.pi_reps = c->part.pi_reps.data();
-    d.num_public_inputs = c->part.pi_reps.size();
-    d.gates = gates.data();
-    d.num_gates = (uint32_t)gates.size();
-    d.constants = constants;
-    d.programs = &c->gen_programs.host;
-    GN::Schedule sched;
-    std::string msg;
-    if (const int ss = GN::build_schedule(d, static_cast<const GN::Record*>(generators), num_generators, input_targets, num_inputs, GN::GROUP, &sched,
-                                          &msg))
-        return fail(ctx, (gb_status)ss, "gb_circuit_set_generators: " + msg);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    c->drop_retry();
-    c->drop_generators();
-    gb_circuit::Generators& g = c->gens;
-    // the inputs that are not the first of their class are compared on the host and left out of the scatter
-    std::vector<uint32_t> scatter(sched.input_cls);
-    std::vector<uint32_t> per_class(sched.num_classes, 0);
-    for (size_t i = 0; i < scatter.size(); i++) {
-        per_class[sched.input_cls[i]]++;
-        if (sched.input_first[i] != i) scatter[i] = GN::OUT_SKIP;
-    }
-    g.input_fast.assign(scatter.size(), 0);
-    g.input_index.resize(scatter.size());
-    for (size_t i = 0; i < scatter.size(); i++) {
-        const uint32_t cl = sched.input_cls[i];
-        g.input_index[i] = std::make_pair(input_targets[i], (uint32_t)i);
-        bool fast = sched.input_free[i] && per_class[cl] == 1 && cl < sched.num_slots && !c->part.is_shared_slot(cl);
-        for (uint32_t pc : sched.pi_cls) fast = fast && pc != cl;
-        g.input_fast[i] = fast;
-    }
-    std::sort(g.input_index.begin(), g.input_index.end());
-    auto upload = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max<size_t>(16, bytes));
-        if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    void* p = nullptr;
-    HIP_TRY(ctx, upload(sched.ops.data(), sched.ops.size() * sizeof(GN::Op), &p));
-    g.ops_dev = static_cast<GN::Op*>(p);
-    HIP_TRY(ctx, upload(sched.args.data(), sched.args.size() * sizeof(uint32_t), &p));
-    g.args_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, upload(sched.level_off.data(), sched.level_off.size() * sizeof(uint32_t), &p));
-    g.level_off_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, upload(scatter.data(), scatter.size() * sizeof(uint32_t), &p));
-    g.input_cls_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, upload(sched.pi_cls.data(), sched.pi_cls.size() * sizeof(uint32_t), &p));
-    g.pi_cls_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, upload(nullptr, 0, &p));
-    g.err_dev = static_cast<uint32_t*>(p);
-    HIP_TRY(ctx, upload(sched.row_constants.data(), sched.row_constants.size() * sizeof(uint64_t), &p));
-    g.row_constants_dev = static_cast<uint64_t*>(p);
-    if (!GN::device_schedule(sched, g.ops_dev, g.args_dev, g.level_off_dev, c->gen_programs.headers_dev, c->gen_programs.instrs_dev,
-                             c->gen_programs.lits_dev, g.row_constants_dev, &g.device, &msg)) {
-        c->drop_generators();
-        return fail(ctx, GB_ERR_HIP, msg);
-    }
-    std::vector<uint64_t>().swap(sched.row_constants);
-    // the kernels read ops and args from the device; the host keeps what it launches and reports with
-    std::vector<GN::Op>().swap(sched.ops);
-    std::vector<uint32_t>().swap(sched.args);
-    g.sched = std::move(sched);
-    g.set = true;
-    return GB_OK;
-} GB_CATCH_CIRCUIT(c)
-
-static gb_status schedule_guard(gb_circuit* c) {   // a schedule is set
-    if (gb_status s = stage_guard(c)) return s;
-    if (!c->part.set || !c->gens.set) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_set_generators has not been called on this circuit");
-    return GB_OK;
-}
-static gb_status generators_guard(gb_circuit* c, const void* input_values, uint32_t flags,
-                                  uint32_t allowed = GB_PUBLIC_INPUT_FLAGS) {   // and these are inputs for it
-    if (gb_status s = stage_guard(c)) return s;
-    if (flags & ~allowed) return fail(c->ctx, GB_ERR_INVALID, "unknown bits in flags");
-    if (flags & GB_INPUT_DEVICE) return fail(c->ctx, GB_ERR_INVALID, "the inputs are a host object: GB_INPUT_DEVICE does not apply");
-    if (gb_status s = schedule_guard(c)) return s;
-    if (!input_values && !c->gens.sched.input_cls.empty()) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    return GB_OK;
-}
-
-// what a host that polls "run N generators" would log (iop/generator.rs:25-30)
-gb_status gb_circuit_generators_info(gb_circuit* c, uint32_t* num_levels, uint32_t* num_launches, uint32_t* num_unrunnable,
-                                     uint32_t* num_checks, uint32_t* num_classes) try {
-    if (gb_status s = schedule_guard(c)) return s;
-    const gbk::gen::Schedule& sc = c->gens.sched;
-    if (num_levels) *num_levels = sc.num_levels;
-    if (num_launches) *num_launches = (uint32_t)sc.launches.size();
-    if (num_unrunnable) *num_unrunnable = sc.num_unrunnable;
-    if (num_checks) *num_checks = sc.num_checks;
-    if (num_classes) *num_classes = sc.num_classes;
-    return GB_OK;
-} GB_CATCH_CIRCUIT(c)
-
-// the keys of PartitionWitness.values (iop/witness.rs:318-330) that the generated array holds, in its order
-gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_out, uint64_t capacity) try {
-    if (gb_status s = schedule_guard(c)) return s;
-    const gbk::gen::Schedule& sc = c->gens.sched;
-    if (!class_targets_out || capacity < sc.class_reps.size()) return fail(c->ctx, GB_ERR_INVALID, "class_targets_out holds fewer than num_classes entries");
-    for (size_t k = 0; k < sc.class_reps.size(); k++) class_targets_out[k] = sc.class_reps[k];
-    return GB_OK;
-} GB_CATCH_CIRCUIT(c)
-
-// generate_partial_witness (iop/generator.rs:25-106) alone
-gb_status gb_generate_partition(gb_circuit* c, const void* input_values, uint32_t flags, void* values_dev_out) try {
-    if (gb_status s = generators_guard(c, input_values, flags)) return s;
-    if (!values_dev_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    return c->field == GB_GOLDILOCKS ? abi_generate_partition<GlF>(static_cast<Circuit<GlF>*>(c), input_values, flags, values_dev_out)
-                                     : abi_generate_partition<BbF>(static_cast<Circuit<BbF>*>(c), input_values, flags, values_dev_out);
-} GB_CATCH_CIRCUIT(c)
-
-static gb_status prove_inputs_entry(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
-                                    size_t proof_cap, size_t* proof_len, const RetryHint* hint = nullptr) {
-    if (gb_status s = generators_guard(c, input_values, flags, GB_PROVE_FLAGS)) return s;
-    gb_ctx* ctx = c->ctx;
-    if (!proof_len) return fail(ctx, GB_ERR_INVALID, "null argument");
-    if ((flags & GB_SALTS_FROM_SEED) && !salts) return fail(ctx, GB_ERR_INVALID, "GB_SALTS_FROM_SEED without a seed (salts is null)");
-    if (c->cfg.zero_knowledge && !salts)
-        return fail(ctx, GB_ERR_INVALID, "a zero-knowledge circuit is proved with salts (a host input, as for gb_prove_salted)");
-    if (!c->cfg.zero_knowledge && salts) return fail(ctx, GB_ERR_INVALID, "salts given for a circuit without zero_knowledge");
-    if (gb_status s = need_arity_list(c)) return s;
-    return c->field == GB_GOLDILOCKS
-               ? prove_inputs<GlF>(static_cast<Circuit<GlF>*>(c), input_values, flags, salts, proof_out, proof_cap, proof_len, hint)
-               : prove_inputs<BbF>(static_cast<Circuit<BbF>*>(c), input_values, flags, salts, proof_out, proof_cap, proof_len, hint);
-}
-
-// prove() (plonk/prover.rs:136-158): generate_partial_witness, then prove_with_partition_witness
-gb_status gb_prove_inputs(gb_circuit* c, const void* input_values, uint32_t flags, const void* salts, void* proof_out,
-                          size_t proof_cap, size_t* proof_len) try {
-    return prove_inputs_entry(c, input_values, flags, salts, proof_out, proof_cap, proof_len);
-} GB_CATCH_CIRCUIT(c)
-
-// the second or third attempt of prove_with_partition_witness's loop (plonk/prover.rs:186-226)
-gb_status gb_prove_inputs_retry(gb_circuit* c, const void* input_values, uint32_t flags, uint32_t wire, uint64_t row,
-                                void* proof_out, size_t proof_cap, size_t* proof_len) try {
-    const RetryHint hint{wire, row};
-    return prove_inputs_entry(c, input_values, flags, nullptr, proof_out, proof_cap, proof_len, &hint);
-} GB_CATCH_CIRCUIT(c)
-
 gb_status gb_quotient_polys(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial_products, const void* public_inputs_hash,
                             const void* betas, const void* gammas, const void* alphas, uint32_t flags, void* chunks_out) try {
     if (gb_status s = stage_guard(c)) return s;
     if (!public_inputs_hash || !betas || !gammas || !alphas || !chunks_out) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    return c->field == GB_GOLDILOCKS
-               ? abi_quotient_polys<GlF>(static_cast<Circuit<GlF>*>(c), wires, zs_partial_products, public_inputs_hash, betas, gammas, alphas, flags, chunks_out)
-               : abi_quotient_polys<BbF>(static_cast<Circuit<BbF>*>(c), wires, zs_partial_products, public_inputs_hash, betas, gammas, alphas, flags, chunks_out);
+    return by_field(c, [&](auto* cf) {
+        return abi_quotient_polys(cf, wires, zs_partial_products, public_inputs_hash, betas, gammas, alphas, flags, chunks_out);
+    });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_prove_openings(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial_products, gb_batch* quotient, const void* zeta,
@@ -2750,9 +2193,9 @@ gb_status gb_prove_openings(gb_circuit* c, gb_batch* wires, gb_batch* zs_partial
     if (gb_status s = stage_guard(c)) return s;
     if (gb_status s = need_arity_list(c)) return s;
     if (!zeta || !challenger || !fri_proof_len) return fail(c->ctx, GB_ERR_INVALID, "null argument");
-    return c->field == GB_GOLDILOCKS
-               ? abi_prove_openings<GlF>(static_cast<Circuit<GlF>*>(c), wires, zs_partial_products, quotient, zeta, challenger, fri_proof_out, fri_proof_cap, fri_proof_len)
-               : abi_prove_openings<BbF>(static_cast<Circuit<BbF>*>(c), wires, zs_partial_products, quotient, zeta, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
+    return by_field(c, [&](auto* cf) {
+        return abi_prove_openings(cf, wires, zs_partial_products, quotient, zeta, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
+    });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t num_oracles, const void* points,
@@ -2781,14 +2224,14 @@ gb_status gb_fri_prove_openings(gb_ctx* ctx, gb_batch* const* oracles, uint32_t 
     if (num_query_rounds == 0) return fail(ctx, GB_ERR_INVALID, "num_query_rounds is zero: a proof without queries proves nothing");
     if (num_query_rounds > GB_MAX_FRI_QUERY_ROUNDS) return fail(ctx, GB_ERR_INVALID, "more than GB_MAX_FRI_QUERY_ROUNDS query rounds");
     const std::vector<uint32_t> arity(reduction_arity_bits, reduction_arity_bits + num_layers);
-    return b0->field == GB_GOLDILOCKS
-               ? abi_fri_prove_openings<GlF>(ctx, oracles, num_oracles, points, batch_sizes, num_batches, polynomials, arity, proof_of_work_bits,
-                                             num_query_rounds, challenger, fri_proof_out, fri_proof_cap, fri_proof_len)
-               : abi_fri_prove_openings<BbF>(ctx, oracles, num_oracles, points, batch_sizes, num_batches, polynomials, arity, proof_of_work_bits,
-                                             num_query_rounds, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
+    return by_field(b0->field, [&](auto f) {
+        return abi_fri_prove_openings<decltype(f)>(ctx, oracles, num_oracles, points, batch_sizes, num_batches, polynomials, arity, proof_of_work_bits,
+                                                   num_query_rounds, challenger, fri_proof_out, fri_proof_cap, fri_proof_len);
+    });
 } GB_CATCH(ctx)
 
 }  // extern "C"
 
+#include "witness_host.inc"
 #include "check_host.inc"
 #include "sigma_host.inc"

@@ -201,8 +201,7 @@ gb_status gb_circuit_decode_sigmas(gb_circuit* c, uint32_t flags, void* info) tr
     if (gb_status s = stage_guard(c)) return s;
     if (flags) return fail(c->ctx, GB_ERR_INVALID, "gb_circuit_decode_sigmas: flags must be 0");
     gb_sigma_info* out = static_cast<gb_sigma_info*>(info);
-    return c->field == GB_GOLDILOCKS ? decode_sigmas<GlF>(static_cast<Circuit<GlF>*>(c), out)
-                                     : decode_sigmas<BbF>(static_cast<Circuit<BbF>*>(c), out);
+    return by_field(c, [&](auto* cf) { return decode_sigmas(cf, out); });
 } GB_CATCH_CIRCUIT(c)
 
 gb_status gb_circuit_copy_classes(gb_circuit* c, uint32_t* first_cell_out) try {

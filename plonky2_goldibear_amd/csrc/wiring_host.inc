@@ -183,11 +183,10 @@ gb_status gb_wiring_sigmas(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, ui
     if (dev_out && (reinterpret_cast<uintptr_t>(sigmas_out) & 15))
         return fail(ctx, GB_ERR_INVALID, "gb_wiring_sigmas: a device sigmas_out must be 16-byte aligned");
     gb_wiring_info* out = static_cast<gb_wiring_info*>(info);
-    const gb_status s = field == GB_GOLDILOCKS
-        ? wiring_sigmas<GlF>(ctx, degree_bits, num_wires, num_routed_wires, k_is, copy_constraints, num_copies, num_targets, dev_out, sigmas_out,
-                             representative_map_out, out)
-        : wiring_sigmas<BbF>(ctx, degree_bits, num_wires, num_routed_wires, k_is, copy_constraints, num_copies, num_targets, dev_out, sigmas_out,
-                             representative_map_out, out);
+    const gb_status s = by_field(field, [&](auto f) {
+        return wiring_sigmas<decltype(f)>(ctx, degree_bits, num_wires, num_routed_wires, k_is, copy_constraints, num_copies, num_targets, dev_out,
+                                          sigmas_out, representative_map_out, out);
+    });
     if (s != GB_OK) (void)hipStreamSynchronize(ctx->stream);   // nothing of a refused call still reads or writes the caller's blocks
     return s;
 } GB_CATCH(ctx)

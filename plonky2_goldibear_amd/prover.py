@@ -82,6 +82,39 @@ class _FriParamsOps:
         return [int(arr[i]) for i in range(n.value)]
 
 
+NO_RANDOM_WIRE = "Permutation argument division by zero but no random wire was given to randomize the witness"
+
+
+def prove_with_retries(data, redraw, prove_once, retry_wire, rng=None, salted=False, p3_repr=False, nothing_to_redraw=NO_RANDOM_WIRE):
+    """The retry loop of prove_with_partition_witness (plonk/prover.rs:183-226) around one front's proof proper.  When the
+    permutation argument hits a zero denominator (ProverError::InvZeroPermArg - with a 31-bit field and 2^20 rows about one proof
+    in five) the reference overwrites `random_wire` with a fresh F::rand() and tries again, at most 3 attempts.
+    data: the CircuitData (field, perm_arg_retries, drop_retry).  redraw(value): write the fresh value where this front keeps the
+    random wire - None where it has nothing to re-draw (the error text is nothing_to_redraw).  prove_once(hint) -> proof bytes,
+    raising PermArgZeroError; hint is retry_wire on the second and third attempts - they differ from the failed one in that wire
+    only, and the library rebuilds just its column where it kept the rest - and None on the first and whenever salts or a seed
+    are in play (salted: the full computation).  retry_wire None: the circuit has no random wire.  One rng draw per retry."""
+    data.perm_arg_retries = 0
+    for attempt in range(data.MAX_PERM_ARG_RETRIES):
+        if attempt > 0:
+            if redraw is None:
+                raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, nothing_to_redraw)
+            rng = rng or np.random.default_rng()
+            p = 0xFFFFFFFF00000001 if data.field == N.GB_GOLDILOCKS else 2013265921
+            val = int(rng.integers(0, p, dtype=np.uint64))
+            if p3_repr and data.field == N.GB_BABYBEAR:
+                val = (val << 32) % p   # the Montgomery word of p3's BabyBear
+            redraw(val)
+            data.perm_arg_retries = attempt
+        try:
+            return prove_once(retry_wire if attempt > 0 and not salted else None)
+        except N.PermArgZeroError:
+            if retry_wire is None:   # no retry will follow: do not keep the failed attempt's commitment on the device
+                data.drop_retry()
+    data.drop_retry()   # giving up: the failed attempt's wires commitment and witness copy (~12 GB at 2^20 rows) go back
+    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+
+
 SigmaInfo = collections.namedtuple("SigmaInfo", [name for name, _ in N.gb_sigma_info._fields_])
 SigmaInfo.__doc__ = "gb_sigma_info: what CircuitData.decode_sigmas found"
 
@@ -179,44 +212,28 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         (gb_prove_cols).  p3_repr: host elements are the reference's in-memory words (GB_INPUT_P3_REPR).  seed: 32 bytes the
         library generates a zero-knowledge circuit's salts from, on the device (GB_SALTS_FROM_SEED) - one seed per proof."""
         self._seed_bytes(seed, salts)
-        self.perm_arg_retries = 0
-        for attempt in range(self.MAX_PERM_ARG_RETRIES):
-            if attempt > 0:
-                if random_wire is None:
-                    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "Permutation argument division by zero but no "
-                                                        "random wire was given to randomize the witness")
-                rng = rng or np.random.default_rng()
-                col, row = random_wire
-                p = 0xFFFFFFFF00000001 if self.field == N.GB_GOLDILOCKS else 2013265921
-                val = int(rng.integers(0, p, dtype=np.uint64))
-                if p3_repr and self.field == N.GB_BABYBEAR:
-                    val = (val << 32) % p   # the Montgomery word of p3's BabyBear
-                if is_column_list(witness) and isinstance(witness[col], np.ndarray):
-                    witness[col][row] = val
-                elif isinstance(witness, np.ndarray):
-                    witness[col, row] = val
-                else:  # torch device tensor(s) holding the same-width integer bit pattern
-                    t = witness[col] if is_column_list(witness) else witness
-                    sval = val - (1 << (8 * t.element_size())) if val >> (8 * t.element_size() - 1) else val
-                    if is_column_list(witness):
-                        t[row] = sval
-                    else:
-                        t[col, row] = sval
-                    # that write is on torch's current stream; the library reads the column on its own stream: order them
-                    import torch
-                    torch.cuda.current_stream(t.device).synchronize()
-                self.perm_arg_retries = attempt
-            try:
-                # the second and third attempts differ from the failed one in the random wire only: gb_prove_retry rebuilds just
-                # that column of the wires commitment where the library kept the rest (no salts)
-                retry = (col, row) if attempt > 0 and salts is None and seed is None else None
-                return self.prove_once(witness, public_inputs, salts, retry_wire=retry, p3_repr=p3_repr, seed=seed)
-            except N.PermArgZeroError:
-                if random_wire is None:   # no retry will follow: do not keep the failed attempt's commitment on the device
-                    self.drop_retry()
-                continue
-        self.drop_retry()   # giving up: the failed attempt's wires commitment and witness copy (~12 GB at 2^20 rows) go back
-        raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+
+        def redraw(val):
+            col, row = random_wire
+            if is_column_list(witness) and isinstance(witness[col], np.ndarray):
+                witness[col][row] = val
+            elif isinstance(witness, np.ndarray):
+                witness[col, row] = val
+            else:  # torch device tensor(s) holding the same-width integer bit pattern
+                t = witness[col] if is_column_list(witness) else witness
+                sval = val - (1 << (8 * t.element_size())) if val >> (8 * t.element_size() - 1) else val
+                if is_column_list(witness):
+                    t[row] = sval
+                else:
+                    t[col, row] = sval
+                # that write is on torch's current stream; the library reads the column on its own stream: order them
+                import torch
+                torch.cuda.current_stream(t.device).synchronize()
+
+        return prove_with_retries(self, redraw if random_wire is not None else None,
+                                  lambda hint: self.prove_once(witness, public_inputs, salts, retry_wire=hint, p3_repr=p3_repr, seed=seed),
+                                  tuple(random_wire) if random_wire is not None else None, rng=rng,
+                                  salted=salts is not None or seed is not None, p3_repr=p3_repr)
 
     def drop_retry(self):
         """release what an attempt that ended in PermArgZeroError keeps on the device for the incremental retry"""
@@ -244,31 +261,46 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         if tuple(shape) != want:
             raise N.ShapeError(N.GB_ERR_INVALID, "witness must be %r, got %r" % (want, tuple(shape)))
         pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
-        if self._proof_buf is None:
-            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
-        n = C.c_size_t()
-        pis_ptr = pis.ctypes.data if pis.size else None
-        if sbuf is not None:
-            st = getattr(lib, "gb_prove_salted" + sfx)(self.handle, ptr, flags | N.GB_SALTS_FROM_SEED, pis_ptr, pis.size,
-                                                       C.cast(sbuf, C.c_void_p), self._proof_buf.ctypes.data, self._proof_buf.size,
-                                                       C.byref(n))
-        elif salts is None and retry_wire is not None:   # (wire, row): the one element re-drawn since the attempt that failed
-            st = getattr(lib, "gb_prove_retry" + sfx)(self.handle, ptr, flags, int(retry_wire[0]), int(retry_wire[1]), pis_ptr, pis.size,
-                                                      self._proof_buf.ctypes.data, self._proof_buf.size, C.byref(n))
-        elif salts is None:
-            st = getattr(lib, "gb_prove" + sfx)(self.handle, ptr, flags, pis_ptr, pis.size, self._proof_buf.ctypes.data,
-                                                self._proof_buf.size, C.byref(n))
-        else:
+        sptr = None
+        if salts is not None and sbuf is None:
             sptr, sshape, sflags, skeep = _as_input(np.reshape(salts, (3 * N.GB_SALT_SIZE, -1)) if isinstance(salts, np.ndarray)
                                                     else salts.reshape(3 * N.GB_SALT_SIZE, -1), self.field)
             if tuple(sshape) != (3 * N.GB_SALT_SIZE, 1 << (self.cfg.degree_bits + self.cfg.rate_bits)) or sflags != (flags & N.GB_INPUT_DEVICE):
                 raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N] in the same memory space as the witness")
-            st = getattr(lib, "gb_prove_salted" + sfx)(self.handle, ptr, flags, pis_ptr, pis.size, sptr, self._proof_buf.ctypes.data,
-                                                       self._proof_buf.size, C.byref(n))
-            del skeep
-        N.check(st, self.ctx.handle)
+        got = self._prove_call("gb_prove", ptr, flags, (pis.ctypes.data if pis.size else None, pis.size), sptr, retry_wire, sbuf,
+                               salted_name="gb_prove_salted", sfx=sfx)
         del keep
+        return got
+
+    def _prove_call(self, name, ptr, flags, mid, salts_ptr, retry_wire, sbuf, salted_name=None, sfx=""):
+        """The one proof call behind prove_once / prove_partition_once / prove_inputs_once -> proof bytes.  `name`(handle, ptr, flags,
+        *mid, salts, out, cap, len) is the front's entry; `name`_retry takes (wire, row) behind the flags and no salts - the attempt
+        after a failure, never with salts or a seed; salted_name: the entry that takes the salts where `name` itself takes none
+        (gb_prove); sfx: "_cols" for the entries that take a column list.  sbuf: the seed buffer of _seed_bytes, which goes where
+        the salts go, under GB_SALTS_FROM_SEED."""
+        if self._proof_buf is None:
+            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
+        n = C.c_size_t()
+        out = (self._proof_buf.ctypes.data, self._proof_buf.size, C.byref(n))
+        if sbuf is not None:
+            flags, salts_ptr = flags | N.GB_SALTS_FROM_SEED, C.cast(sbuf, C.c_void_p)
+        if salts_ptr is None and retry_wire is not None:   # (wire, row): the one element re-drawn since the attempt that failed
+            st = getattr(self._lib, name + "_retry" + sfx)(self.handle, ptr, flags, int(retry_wire[0]), int(retry_wire[1]), *mid, *out)
+        elif salts_ptr is None and salted_name is not None:
+            st = getattr(self._lib, name + sfx)(self.handle, ptr, flags, *mid, *out)
+        else:
+            st = getattr(self._lib, (salted_name or name) + sfx)(self.handle, ptr, flags, *mid, salts_ptr, *out)
+        N.check(st, self.ctx.handle)
         return self._proof_buf[: n.value].tobytes()
+
+    def _host_salts(self, salts):
+        """[3][4][N] host salts of a witness front -> (pointer, the array that owns it); (None, None) without salts"""
+        if salts is None:
+            return None, None
+        sa = np.ascontiguousarray(salts, dtype=self._dt).reshape(3 * N.GB_SALT_SIZE, -1)
+        if sa.shape[1] != 1 << (self.cfg.degree_bits + self.cfg.rate_bits):
+            raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N]")
+        return sa.ctypes.data, sa
 
     # ---- prove() from the partition witness (include/goldibear_gpu.h: gb_circuit_set_partition, gb_prove_partition*)
     def set_partition(self, representative_map, public_input_targets=()):
@@ -292,54 +324,21 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         salts / seed as for prove_once (both host)."""
         sbuf = self._seed_bytes(seed, salts)
         v, flags = self._partition_values(values, p3_repr)
-        if self._proof_buf is None:
-            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
-        n = C.c_size_t()
-        out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
-        if sbuf is not None:
-            st = self._lib.gb_prove_partition(self.handle, v.ctypes.data, flags | N.GB_SALTS_FROM_SEED, C.cast(sbuf, C.c_void_p), out, cap,
-                                              C.byref(n))
-        elif salts is None and retry_wire is not None:
-            st = self._lib.gb_prove_partition_retry(self.handle, v.ctypes.data, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap,
-                                                    C.byref(n))
-        else:
-            sa = None
-            if salts is not None:
-                sa = np.ascontiguousarray(salts, dtype=self._dt).reshape(3 * N.GB_SALT_SIZE, -1)
-                if sa.shape[1] != 1 << (self.cfg.degree_bits + self.cfg.rate_bits):
-                    raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N]")
-            st = self._lib.gb_prove_partition(self.handle, v.ctypes.data, flags, sa.ctypes.data if sa is not None else None, out, cap,
-                                              C.byref(n))
-        N.check(st, self.ctx.handle)
-        return self._proof_buf[: n.value].tobytes()
+        sptr, keep = self._host_salts(salts) if sbuf is None else (None, None)
+        return self._prove_call("gb_prove_partition", v.ctypes.data, flags, (), sptr, retry_wire, sbuf)
 
     def prove_partition(self, values, representative=None, random_wire=None, rng=None, salts=None, p3_repr=False, seed=None):
         """prove_with_partition_witness (plonk/prover.rs:160-226) on the reference's own witness object: the retry loop of prove()
         over gb_prove_partition / gb_prove_partition_retry.  random_wire = (column, row) as for prove(); `representative` is the
         entry of `values` that holds it (representative_map[row * num_wires + column]), re-drawn in place after InvZeroPermArg."""
         self._seed_bytes(seed, salts)
-        self.perm_arg_retries = 0
-        for attempt in range(self.MAX_PERM_ARG_RETRIES):
-            if attempt > 0:
-                if random_wire is None or representative is None:
-                    raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "Permutation argument division by zero but no "
-                                                        "random wire was given to randomize the witness")
-                rng = rng or np.random.default_rng()
-                p = 0xFFFFFFFF00000001 if self.field == N.GB_GOLDILOCKS else 2013265921
-                val = int(rng.integers(0, p, dtype=np.uint64))
-                if p3_repr and self.field == N.GB_BABYBEAR:
-                    val = (val << 32) % p
-                values[int(representative)] = val
-                self.perm_arg_retries = attempt
-            try:
-                retry = random_wire if attempt > 0 and salts is None and seed is None else None
-                return self.prove_partition_once(values, salts, retry_wire=retry, p3_repr=p3_repr, seed=seed)
-            except N.PermArgZeroError:
-                if random_wire is None:
-                    self.drop_retry()
-                continue
-        self.drop_retry()
-        raise N.TooManyPermArgFailuresError(N.GB_ERR_PERM_ARG_ZERO, "ProverError::TooManyPermArgFailures")
+
+        def redraw(val):
+            values[int(representative)] = val
+
+        return prove_with_retries(self, redraw if random_wire is not None and representative is not None else None,
+                                  lambda hint: self.prove_partition_once(values, salts, retry_wire=hint, p3_repr=p3_repr, seed=seed),
+                                  random_wire, rng=rng, salted=salts is not None or seed is not None, p3_repr=p3_repr)
 
     def expand_partition(self, values, p3_repr=False):
         """partition_witness.full_witness() (iop/witness.rs:359-371) alone: -> a torch device tensor [num_wires][n] of canonical
@@ -419,24 +418,8 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         salts / seed as for prove_once (both host)."""
         sbuf = self._seed_bytes(seed, salts)
         v, flags = self._input_values(input_values, p3_repr)
-        if self._proof_buf is None:
-            self._proof_buf = np.empty(8 << 20, dtype=np.uint8)
-        n = C.c_size_t()
-        out, cap = self._proof_buf.ctypes.data, self._proof_buf.size
-        vp = v.ctypes.data if v.size else None
-        if sbuf is not None:
-            st = self._lib.gb_prove_inputs(self.handle, vp, flags | N.GB_SALTS_FROM_SEED, C.cast(sbuf, C.c_void_p), out, cap, C.byref(n))
-        elif salts is None and retry_wire is not None:
-            st = self._lib.gb_prove_inputs_retry(self.handle, vp, flags, int(retry_wire[0]), int(retry_wire[1]), out, cap, C.byref(n))
-        else:
-            sa = None
-            if salts is not None:
-                sa = np.ascontiguousarray(salts, dtype=self._dt).reshape(3 * N.GB_SALT_SIZE, -1)
-                if sa.shape[1] != 1 << (self.cfg.degree_bits + self.cfg.rate_bits):
-                    raise N.ShapeError(N.GB_ERR_INVALID, "salts must be [3][4][N]")
-            st = self._lib.gb_prove_inputs(self.handle, vp, flags, sa.ctypes.data if sa is not None else None, out, cap, C.byref(n))
-        N.check(st, self.ctx.handle)
-        return self._proof_buf[: n.value].tobytes()
+        sptr, keep = self._host_salts(salts) if sbuf is None else (None, None)
+        return self._prove_call("gb_prove_inputs", v.ctypes.data if v.size else None, flags, (), sptr, retry_wire, sbuf)
 
     # ---- does the witness satisfy the circuit?  (include/goldibear_gpu.h: gb_check_witness, gb_check_partition, gb_check_inputs)
     def _check_call(self, call, max_violations):

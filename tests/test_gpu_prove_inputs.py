@@ -11,7 +11,8 @@ builder mirror (BuiltCircuit.generate_partition_witness); every comparison is ex
     circuit proves a good witness afterwards; a non-canonical input; calls before gb_circuit_set_generators; a program gate's
     record (GB_ERR_UNSUPPORTED);
   * a zero-knowledge circuit with salts; the retry after InvZeroPermArg == gb_prove_partition_retry, with and without kept
-    state; a circuit that never calls gb_circuit_set_generators proves as before and runs no generator scope;
+    state; the retry across the fronts (csrc/witness_host.inc: gb_prove_partition_retry builds on a matrix gb_prove_inputs kept,
+    gb_prove_inputs_retry does not build on one gb_prove_partition kept); a circuit that never calls gb_circuit_set_generators proves as before and runs no generator scope;
   * more inputs than one slice of the page-locked upload holds (1 MB: 131 072 Goldilocks / 262 144 BabyBear words)."""
 import ctypes as C
 
@@ -271,6 +272,46 @@ def test_retry_after_inv_zero_perm_arg(ctx, degree_bits):
     data.arm_perm_arg_failure()
     proof = c.prove_inputs(pw, np.random.default_rng(5))
     assert data.perm_arg_retries == 1 and c.verify(proof)
+    data.free()
+    ctx.trim()
+
+
+def test_retry_across_the_partition_and_inputs_fronts(ctx):
+    """What a failed attempt keeps is one state, whichever front kept it (2^16 rows: the smallest size at which one does).
+    (a) gb_prove_inputs fails, gb_prove_partition_retry builds on its matrix - it needs the matrix alone, the public inputs are
+    read off `values`: no expansion runs.  (b) gb_prove_partition fails, gb_prove_inputs_retry does not build on its matrix - no
+    public inputs were kept with it: the generators run, the full computation.  Either way the bytes are those of the re-drawn
+    witness proved from the matrix."""
+    b, pw = CS.factorial_circuit(count=60, num_challenges=3)
+    while b.num_gates() < (1 << 16) - 40:
+        b.add_gate(NoopGate())
+    c = b.build(ctx)
+    assert c.degree_bits == 16
+    c.set_generators(pw=pw)
+    data = c.data
+    rw = (c.random_wire[1], c.random_wire[0])                     # (column, row)
+    rw_target = c.target_index(wire(*c.random_wire))
+    rw_input = c._input_targets.index(wire(*c.random_wire))
+    v0 = c.generate_partition_witness(pw, np.random.default_rng(SEED))
+    i0 = c.input_values(pw, np.random.default_rng(SEED))
+    wires, pis = c.generate_witness(pw, np.random.default_rng(SEED))
+    v, i = v0.copy(), i0.copy()
+    v[rw_target] = i[rw_input] = wires[rw] = np.uint64(0xFEDCBA9876543210 % GL.P)
+    want = data.prove_once(wires, pis)
+    ctx.set_profiling(True)
+    data.arm_perm_arg_failure()
+    with pytest.raises(PermArgZeroError):
+        data.prove_inputs_once(i0)
+    ctx.scope_reset()
+    assert data.prove_partition_once(v, retry_wire=rw) == want      # (a)
+    assert ctx.scope_ms("partition expansion")[1] == 0
+    data.arm_perm_arg_failure()
+    with pytest.raises(PermArgZeroError):
+        data.prove_partition_once(v0)
+    ctx.scope_reset()
+    assert data.prove_inputs_once(i, retry_wire=rw) == want         # (b)
+    assert ctx.scope_ms("run generators")[1] == 1
+    ctx.set_profiling(False)
     data.free()
     ctx.trim()
 
