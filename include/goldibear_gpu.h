@@ -772,7 +772,7 @@ gb_status gb_verify(gb_circuit* c, const void* proof, size_t proof_len);
  * initial paths by oracle, each layer's consistency check and then its path, the final polynomial).
  *   c       any handle gb_verify accepts, either field - a gb_verifier_create* object made with a NULL context included
  *   ctx     the device; NULL, or a circuit that belongs to another context: GB_ERR_INVALID
- *   flags   0 (anything else: GB_ERR_INVALID).  Compressed proofs are not taken: decompress or use gb_verify_compressed
+ *   flags   0 (anything else: GB_ERR_INVALID).  Compressed proofs go to gb_verify_compressed_batch below
  *   results gb_verify_result[num_proofs], host
  * Returns GB_OK: every proof verified; GB_ERR_VERIFY: the call completed, at least one proof did not verify (results says which -
  * GB_ERR_INVALID proofs included); anything else: the call did not complete and results is unspecified.  num_proofs == 0: GB_OK.
@@ -805,6 +805,34 @@ typedef struct gb_verify_result {
 gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
                           uint32_t flags, void* results /* gb_verify_result[num_proofs] */);
 const char* gb_verify_check_text(uint32_t check); /* "" for GB_VCHECK_NONE and for a value that is no check */
+/* gb_verify_batch for COMPRESSED proofs (CompressedProofWithPublicInputs bytes, below): gb_verify_compressed of many proofs of ONE
+ * circuit, checked as they stand - nothing is decompressed into bytes, and a sibling hash or a coset that several query rounds
+ * share is hashed once.  For every i, results[i].status is what gb_verify_compressed(c, proofs[i], proof_lens[i]) returns and
+ * gb_verify_check_text(results[i].check) the text it leaves in gb_last_error; query_round and index are what gb_verify_batch
+ * reports on the decompressed proof.  Of several failing checks the one gb_verify_compressed reaches first is named:
+ * decompression first (parse errors, the stored query indices against the transcript's, a missing sibling), then gb_verify's
+ * order on the decompressed proof (above).  ctx, c, flags, results, the return values, num_proofs == 0, "verify_chunk_bytes" and
+ * the summary in gb_last_error are gb_verify_batch's.
+ * The host stage (on the context's "copy_threads") parses, replays the transcript, compares the stored indices, counts from the
+ * indices alone how many siblings every stored path must hold (hash/path_compression.rs:56-95), and checks the vanishing identity
+ * and the proof of work.  A path with too few siblings fails as gb_verify_compressed fails it; a proof with a path that holds MORE
+ * than needed (gb_verify_compressed ignores the surplus) is decompressed and verified on the host, as is every proof of a circuit
+ * with more than 256 query rounds; every other proof goes to the device with a directory of its entries - offsets the host
+ * computed from the indices and checked against the proof's length; the kernels read proof bytes as field words only.
+ * ctx NULL is GB_ERR_INVALID as for gb_verify_batch; where the other arguments are in order the host stage has still run, on the
+ * calling thread and touching no device, and results holds its verdicts - GB_ERR_INVALID with check 0 for every proof that only a
+ * device could decide (tests/sanitize drives the parser and the sibling count this way).
+ * Timing scopes: "verify compressed batch: host stage", "verify compressed batch: upload", "verify compressed batch: queries"
+ * (fri_combine_initial, the folds with the inferred evaluations, the final polynomial), "verify compressed batch: paths" (every
+ * tree's shared paths; it runs second because a layer tree's leaf is a re-inflated coset).
+ * The checks only a compressed proof can fail (an enum, numbered from 16: the GB_VCHECK_ macros above are gb_verify's own): */
+enum {
+    GB_VCHECK_COMPRESSED_INDICES = 16,         /* GB_ERR_VERIFY: the stored query indices are not the transcript's */
+    GB_VCHECK_COMPRESSED_MISSING_SIBLING = 17, /* GB_ERR_INVALID: a stored Merkle path holds fewer siblings than the indices demand */
+    GB_VCHECK_COMPRESSED_TRAILING = 18         /* GB_ERR_INVALID: "trailing bytes in compressed proof" */
+};
+gb_status gb_verify_compressed_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens,
+                                     uint32_t num_proofs, uint32_t flags, void* results /* gb_verify_result[num_proofs] */);
 /* Compressed proofs, on the host like the reference's (hash/path_compression.rs, fri/proof.rs:137-384, plonk/proof.rs:96-260):
  * gb_proof_compress = ProofWithPublicInputs::compress -> CompressedProofWithPublicInputs bytes (util/serialization/mod.rs:2168-2256:
  * Merkle paths of one tree share their siblings, a repeated query index is stored once, the FRI evaluation the verifier can infer

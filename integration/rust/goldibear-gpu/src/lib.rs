@@ -353,6 +353,8 @@ extern "C" {
     fn gb_verify_batch(ctx: *mut gb_ctx, c: *mut gb_circuit, proofs: *const *const c_void, proof_lens: *const usize, num_proofs: u32,
                        flags: u32, results: *mut c_void) -> i32;
     fn gb_verify_check_text(check: u32) -> *const c_char;
+    fn gb_verify_compressed_batch(ctx: *mut gb_ctx, c: *mut gb_circuit, proofs: *const *const c_void, proof_lens: *const usize,
+                                  num_proofs: u32, flags: u32, results: *mut c_void) -> i32;
     fn gb_circuit_constants_sigmas_commitment(c: *mut gb_circuit, out: *mut *mut gb_batch) -> i32;
     fn gb_zs_partial_products(c: *mut gb_circuit, witness: *const c_void, flags: u32, betas: *const c_void, gammas: *const c_void,
                               values_out: *mut c_void) -> i32;
@@ -1422,6 +1424,21 @@ impl<'c, W: Copy + Default> GpuCircuit<'c, W> {
         let st = unsafe {
             gb_verify_batch(self.ctx.0, self.handle, ptrs.as_ptr(), lens.as_ptr(), proofs.len() as u32, 0,
                             res.as_mut_ptr() as *mut c_void)
+        };
+        if st != GB_ERR_VERIFY {
+            check(self.ctx.0, st)?;
+        }
+        Ok(res)
+    }
+    /// `verify_batch` for `CompressedProofWithPublicInputs` bytes, checked as they stand (`gb_verify_compressed_batch`): `status` is
+    /// what `verify_compressed` would answer
+    pub fn verify_compressed_batch(&self, proofs: &[&[u8]]) -> Result<Vec<gb_verify_result>, GpuError> {
+        let ptrs: Vec<*const c_void> = proofs.iter().map(|p| p.as_ptr() as *const c_void).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut res = vec![gb_verify_result::default(); proofs.len()];
+        let st = unsafe {
+            gb_verify_compressed_batch(self.ctx.0, self.handle, ptrs.as_ptr(), lens.as_ptr(), proofs.len() as u32, 0,
+                                       res.as_mut_ptr() as *mut c_void)
         };
         if st != GB_ERR_VERIFY {
             check(self.ctx.0, st)?;

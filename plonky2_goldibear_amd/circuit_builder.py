@@ -1599,3 +1599,7 @@ class BuiltCircuit:
     def verify_batch(self, proofs):
         """CircuitData.verify_batch: one native.VerifyResult per proof, the query rounds checked on the device"""
         return self.data.verify_batch(proofs)
+
+    def verify_compressed_batch(self, proofs):
+        """CircuitData.verify_compressed_batch: one native.VerifyResult per compressed proof, checked as they stand on the device"""
+        return self.data.verify_compressed_batch(proofs)

@@ -76,7 +76,7 @@ std::vector<std::vector<typename F::T>> decompress_paths(const std::vector<const
             const Hash cur = seen.at(index);
             auto it = seen.find(index ^ 1);
             if (it == seen.end()) {
-                if ((next[k] + 1) * H > compressed[k]->size()) throw VerifyFail{GB_ERR_INVALID, "compressed Merkle proof is missing a sibling"};
+                if ((next[k] + 1) * H > compressed[k]->size()) vfail(GB_VCHECK_COMPRESSED_MISSING_SIBLING);
                 Hash sib;
                 std::copy(compressed[k]->begin() + next[k] * H, compressed[k]->begin() + (next[k] + 1) * H, sib.begin());
                 next[k]++;
@@ -171,6 +171,78 @@ std::vector<uint8_t> compress_impl(Circuit<F>* c, const uint8_t* bytes, size_t l
     return std::move(w.out);
 }
 
+// The bytes of a CompressedProofWithPublicInputs, read once for gb_proof_decompress, gb_verify_compressed and the batch verifier's
+// host stage (read_compressed_fri_query_rounds, serialization/mod.rs:1102-1150): caps, openings, the stored query indices, per
+// tree the entries of the distinct indices in ascending order, the final polynomial, the proof-of-work witness, the public inputs
+// (no count: what is left).  Every word is checked canonical where it stands; an entry is kept as its place in the bytes.
+struct CompressedEntry {
+    u64 index;          // the leaf (an oracle tree: the query index; a layer tree: the coset index)
+    size_t row[4];      // byte offset of the row per oracle ([0] alone for a layer: the coset without its inferred element)
+    u32 siblings[4];    // the length byte behind the row; the stored siblings follow it
+};
+struct CompressedIndex {
+    std::vector<u64> stored;                        // the query indices as stored
+    std::vector<CompressedEntry> initial;           // ascending
+    std::vector<std::vector<CompressedEntry>> steps;   // per layer, ascending
+    size_t queries_begin = 0, queries_end = 0;      // the entries' bytes
+    static const CompressedEntry& at(const std::vector<CompressedEntry>& v, u64 index) {
+        auto it = std::lower_bound(v.begin(), v.end(), index, [](const CompressedEntry& e, u64 i) { return e.index < i; });
+        if (it == v.end() || it->index != index) throw std::out_of_range("compressed entry");
+        return *it;
+    }
+};
+template <class F>
+size_t canon_span(ProofReader<F>& rd, size_t n) {   // n canonical words: where they begin
+    const size_t at = rd.off;
+    for (size_t i = 0; i < n; i++) (void)rd.field_canonical();
+    return at;
+}
+template <class F>
+void parse_compressed(const Circuit<F>* c, const ProofShape<F>& sh, const uint8_t* bytes, size_t len, ParsedProof<F>& p, CompressedIndex& ix) {
+    typedef typename F::T T;
+    constexpr u32 D = F::D, H = F::H;
+    const u32 nq = sh.nqr, nl = sh.nlayers;
+    ProofReader<F> rd{bytes, len};
+    parse_caps_and_openings(rd, sh, p);
+    ix.stored.resize(nq);
+    for (auto& i : ix.stored) { rd.need(4); u32 v; std::memcpy(&v, rd.p + rd.off, 4); rd.off += 4; i = v; }
+    ix.queries_begin = rd.off;
+    std::vector<u64> idx(ix.stored);
+    std::sort(idx.begin(), idx.end());
+    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
+    ix.initial.resize(idx.size());
+    for (size_t e = 0; e < idx.size(); e++) {
+        CompressedEntry& en = ix.initial[e];
+        en.index = idx[e];
+        for (int o = 0; o < 4; o++) {
+            en.row[o] = canon_span(rd, sh.row_widths[o]);
+            en.siblings[o] = rd.u8();
+            canon_span(rd, (size_t)en.siblings[o] * H);
+        }
+    }
+    ix.steps.resize(nl);
+    for (u32 li = 0; li < nl; li++) {
+        const u32 ab = c->arity_bits[li];
+        for (auto& i : idx) i >>= ab;
+        idx.erase(std::unique(idx.begin(), idx.end()), idx.end());   // (still ascending)
+        ix.steps[li].resize(idx.size());
+        for (size_t e = 0; e < idx.size(); e++) {
+            CompressedEntry& en = ix.steps[li][e];
+            en = CompressedEntry{};
+            en.index = idx[e];
+            en.row[0] = canon_span(rd, (size_t)D * ((1u << ab) - 1));
+            en.siblings[0] = rd.u8();
+            canon_span(rd, (size_t)en.siblings[0] * H);
+        }
+    }
+    ix.queries_end = rd.off;
+    rd.ext_vec(p.final_poly, p.t_final, sh.final_len);
+    p.pow_witness = rd.field_canonical();
+    if ((len - rd.off) % sizeof(T)) vfail(GB_VCHECK_COMPRESSED_TRAILING);
+    if ((len - rd.off) / sizeof(T) != c->cfg.num_public_inputs) vfail(GB_VCHECK_PI_COUNT);  // plonk/validate_shape.rs:22-25 (the compressed form has no count)
+    rd.canon_vec(p.pis, (len - rd.off) / sizeof(T));
+}
+
 // CompressedProofWithPublicInputs::decompress -> bytes of ProofWithPublicInputs
 template <class F>
 std::vector<uint8_t> decompress_impl(Circuit<F>* c, const uint8_t* bytes, size_t len) {
@@ -180,47 +252,39 @@ std::vector<uint8_t> decompress_impl(Circuit<F>* c, const uint8_t* bytes, size_t
     const ProofShape<F> sh(c);
     const u32 nq = sh.nqr, nl = sh.nlayers;
     ParsedProof<F> p;
-    ProofReader<F> rd{bytes, len};
-    parse_caps_and_openings(rd, sh, p);
-    // read_compressed_fri_query_rounds (serialization/mod.rs:1102-1150)
-    std::vector<u64> stored(nq);
-    for (auto& i : stored) { rd.need(4); u32 v; std::memcpy(&v, rd.p + rd.off, 4); rd.off += 4; i = v; }
+    CompressedIndex ix;
+    parse_compressed(c, sh, bytes, len, p, ix);
+    const std::vector<u64>& stored = ix.stored;
     struct Initial { std::vector<T> rows[4], paths[4]; };
     struct Step { std::vector<T> evals, path; };
     std::map<u64, Initial> initial;
     std::vector<std::map<u64, Step>> steps(nl);
     {
-        std::set<u64> idx(stored.begin(), stored.end());
-        for (u64 i : idx) {
-            Initial& e = initial[i];
+        auto words = [&](std::vector<T>& out, size_t at, size_t n) {
+            out.resize(n);
+            if (n) std::memcpy(out.data(), bytes + at, n * sizeof(T));
+        };
+        for (const CompressedEntry& en : ix.initial) {
+            Initial& e = initial[en.index];
             for (int o = 0; o < 4; o++) {
-                rd.canon_vec(e.rows[o], sh.row_widths[o]);
-                rd.canon_vec(e.paths[o], (size_t)rd.u8() * H);
+                words(e.rows[o], en.row[o], sh.row_widths[o]);
+                words(e.paths[o], en.row[o] + sh.row_widths[o] * sizeof(T) + 1, (size_t)en.siblings[o] * H);
             }
         }
         for (u32 li = 0; li < nl; li++) {
-            const u32 ab = c->arity_bits[li];
-            std::set<u64> nxt;
-            for (u64 i : idx) nxt.insert(i >> ab);
-            idx.swap(nxt);
-            for (u64 i : idx) {
-                Step& e = steps[li][i];
-                rd.canon_vec(e.evals, (size_t)D * ((1u << ab) - 1));
-                rd.canon_vec(e.path, (size_t)rd.u8() * H);
+            const size_t ne = (size_t)D * ((1u << c->arity_bits[li]) - 1);
+            for (const CompressedEntry& en : ix.steps[li]) {
+                Step& e = steps[li][en.index];
+                words(e.evals, en.row[0], ne);
+                words(e.path, en.row[0] + ne * sizeof(T) + 1, (size_t)en.siblings[0] * H);
             }
         }
     }
-    rd.ext_vec(p.final_poly, p.t_final, sh.final_len);
-    p.pow_witness = rd.field_canonical();
-    if ((len - rd.off) % sizeof(T)) throw VerifyFail{GB_ERR_INVALID, "trailing bytes in compressed proof"};
-    if ((len - rd.off) / sizeof(T) != c->cfg.num_public_inputs)  // plonk/validate_shape.rs:22-25 (the compressed form has no count)
-        throw VerifyFail{GB_ERR_INVALID, "Number of public inputs doesn't match circuit data."};
-    rd.canon_vec(p.pis, (len - rd.off) / sizeof(T));
 
     Challenges<F> chal;
     get_challenges(c, sh, p, chal);
     const std::vector<u64>& indices = chal.x_indices;
-    if (indices != stored) throw VerifyFail{GB_ERR_VERIFY, "the compressed proof's query indices are not the transcript's"};
+    if (indices != stored) vfail(GB_VCHECK_COMPRESSED_INDICES);
 
     // the inferred elements (get_inferred_elements) and the re-inflated evals, per query
     const FriQueryMath<F> fri(sh, p, chal);

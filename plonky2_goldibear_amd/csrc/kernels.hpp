@@ -508,4 +508,27 @@ void verify_paths(const VerifyLayout& L, const unsigned char* rounds, const unsi
 template <class F>
 void verify_queries(const VerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st);
 
+// ---- gb_verify_compressed_batch (kernels_verify.hip): the same checks on COMPRESSED proofs (verify_compressed.hpp).  A proof's
+// query section - per tree the entries of its distinct indices, as they stand behind the stored indices - lies at
+// rounds + proof * proof_stride, and its record carries a directory behind the caps:
+//   at rec_dir_off: u32 entry[VERIFY_ORACLES + num_layers][nqr]   byte offset, inside the proof's query section, of the entry of
+//                   query round k in tree t: the row (a layer: the coset without its inferred element), one length byte, the
+//                   stored siblings.  The host has checked every entry against the proof's length and its sibling count against
+//                   what the indices demand; the kernels never read past trees[t].path_len siblings, which proof_stride pads for.
+// In L, trees[t].num_words is the full leaf (a layer's re-inflated coset) and row_off / path_off are unused.
+// `inferred` is scratch of num_proofs * num_layers * nqr * D words: verify_compressed_queries leaves there, per layer and query
+// round, the element its coset lacks (canonical) - the layer trees' leaves of verify_compressed_paths, which therefore runs second.
+// A proof's query rounds share one workgroup: nqr <= VERIFY_COMPRESSED_MAX_QUERIES.
+static constexpr u32 VERIFY_COMPRESSED_MAX_QUERIES = 256;
+struct VerifyCompressedLayout {
+    VerifyLayout L;
+    u32 proof_stride, rec_dir_off;
+};
+template <class F>
+void verify_compressed_queries(const VerifyCompressedLayout& C, const unsigned char* rounds, const unsigned char* records,
+                               typename F::T* inferred, u64* keys, hipStream_t st);
+template <class F>
+void verify_compressed_paths(const VerifyCompressedLayout& C, const unsigned char* rounds, const unsigned char* records,
+                             const typename F::T* circuit_cap, const typename F::T* inferred, u64* keys, hipStream_t st);
+
 }  // namespace gbk

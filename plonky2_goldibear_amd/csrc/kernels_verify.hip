@@ -7,8 +7,18 @@
 // Every check runs whether or not an earlier one of its proof failed; the proof's result is the minimum of the failing checks'
 // keys (query round, position in the round), which is the check the host verifier reaches first, whatever the schedule.
 // All offsets come from the circuit's shape (VerifyLayout, kernels.hpp); the proofs' bytes are only ever read as field words.
+//
+// gb_verify_compressed_batch's device stage: the same checks where the query rounds of a proof are no longer independent
+// (verify_compressed.hpp), so one workgroup holds all query rounds of a proof, a lane each, and they advance together through LDS.
+//   k_vc_queries      one workgroup per proof: fri_combine_initial, then layer by layer - the lanes publish their running
+//                     evaluation, every lane finds the first lane of its coset, re-inflates the stored row with that lane's
+//                     evaluation, checks consistency and folds; the final polynomial.  Leaves the inserted elements for:
+//   k_vc_paths        one workgroup per (proof, tree): the leaves' digests, then level by level up to the cap - a lane's sibling
+//                     is the node another lane just computed or the next stored sibling of the first lane with its node
+// The keys are the ones above: "path k leads to the cap" on the decompressed proof is "lane k's node is its cap entry" here.
 #include "kernels.hpp"
 #include "sponge.hpp"
+#include "verify_compressed.hpp"
 #include "verify_query.hpp"
 
 namespace gbk {
@@ -88,6 +98,133 @@ __global__ __launch_bounds__(64) void k_verify_queries(VerifyLayout L, const uns
     if (pos != ~0u) atomicMin(reinterpret_cast<unsigned long long*>(keys + proof), (unsigned long long)vq::fail_key(qr, pos));
 }
 
+template <class F>
+__global__ __launch_bounds__(VERIFY_COMPRESSED_MAX_QUERIES) void k_vc_queries(VerifyCompressedLayout C, const unsigned char* __restrict__ rounds,
+                                                                              const unsigned char* __restrict__ records,
+                                                                              typename F::T* __restrict__ inferred, u64* __restrict__ keys) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    constexpr u32 D = F::D;
+    const VerifyLayout& L = C.L;
+    __shared__ u64 s_x[VERIFY_COMPRESSED_MAX_QUERIES];
+    __shared__ E s_eval[VERIFY_COMPRESSED_MAX_QUERIES];
+    const u32 proof = blockIdx.x, nqr = L.nqr;
+    const bool live = threadIdx.x < nqr;   // lanes past the end follow the last query round: the barriers below need every lane
+    const u32 k = live ? threadIdx.x : nqr - 1;
+    const RecordView<F> rec{records + (size_t)proof * L.rec_bytes, L};
+    const unsigned char* section = rounds + (size_t)proof * C.proof_stride;
+    const u32* dir = reinterpret_cast<const u32*>(rec.p + C.rec_dir_off);
+    const u64 x_index = rec.x_index(k);
+    if (live) s_x[k] = x_index;
+    T x = vq::subgroup_x<F>(L.lgN, x_index);
+    auto poly = [&](u32 b, u32 i) {
+        u32 o = 2;
+        if (b == 0) {
+            o = 0;
+            while (i >= L.widths[o]) { i -= L.widths[o]; o++; }
+        }
+        return vq::load_word<F>(section + dir[o * nqr + k] + (size_t)i * sizeof(T));
+    };
+    E old_eval = vq::combine_initial<F>(2, L.batch_sizes, rec.points(), rec.red_open(), rec.alpha_shift(), rec.fri_alpha(), x, poly);
+    const E* betas = rec.betas();
+    u32 fail = ~0u, shift = 0;
+    u64 xi = x_index;
+    for (u32 li = 0; li < L.num_layers; li++) {
+        const u32 ab = L.arity_bits[li];
+        const u64 mask = ((u64)1 << ab) - 1, within = xi & mask, coset = xi >> ab;
+        if (live) s_eval[k] = old_eval;
+        __syncthreads();
+        const u32 first = vc::first_with(k, [&](u32 j) { return s_x[j] >> (shift + ab); });
+        const u32 at = (u32)((s_x[first] >> shift) & mask);
+        const E ins = s_eval[first];
+        bool consistent;
+        const E next = vc::fold_layer<F>(x, within, ab, betas[li], section + dir[(VERIFY_ORACLES + li) * nqr + k], at, ins, old_eval, &consistent);
+        if (!consistent && fail == ~0u) fail = vq::pos_consistency(VERIFY_ORACLES, li);
+        if (live) {
+            T* out = inferred + (((size_t)proof * L.num_layers + li) * nqr + k) * D;
+            for (u32 d = 0; d < D; d++) out[d] = (T)F::dec(F::coord(ins, d));
+        }
+        __syncthreads();   // every lane has read s_eval before the next layer overwrites it
+        old_eval = next;
+        for (u32 i = 0; i < ab; i++) x = F::mul(x, x);
+        xi = coset;
+        shift += ab;
+    }
+    const E* fin = rec.final_poly();
+    const E end = vq::final_eval<F>(L.final_len, x, [&](u32 i) { return fin[i]; });
+    if (!vq::eeq<F>(end, old_eval) && fail == ~0u) fail = vq::pos_final(VERIFY_ORACLES, L.num_layers);
+    if (live && fail != ~0u) atomicMin(reinterpret_cast<unsigned long long*>(keys + proof), (unsigned long long)vq::fail_key(k, fail));
+}
+
+// blockIdx.y = tree: the lanes of a workgroup share a leaf width and a path length (Sponge<GlF> is wave-wide)
+template <class F>
+__global__ __launch_bounds__(VERIFY_COMPRESSED_MAX_QUERIES) void k_vc_paths(VerifyCompressedLayout C, const unsigned char* __restrict__ rounds,
+                                                                            const unsigned char* __restrict__ records,
+                                                                            const typename F::T* __restrict__ circuit_cap,
+                                                                            const typename F::T* __restrict__ inferred, u64* __restrict__ keys) {
+    typedef typename F::T T;
+    constexpr u32 D = F::D, HW = F::H;
+    constexpr size_t TS = sizeof(T);
+    const VerifyLayout& L = C.L;
+    __shared__ poseidon_gl::v4i sponge_lds[Sponge<F>::LDS_V4];
+    __shared__ u64 s_leaf[VERIFY_COMPRESSED_MAX_QUERIES];
+    __shared__ u32 s_taken[VERIFY_COMPRESSED_MAX_QUERIES];
+    __shared__ T s_node[VERIFY_COMPRESSED_MAX_QUERIES * HW];
+    const u32 t = blockIdx.y, proof = blockIdx.x, nqr = L.nqr;
+    const VerifyTree tr = L.trees[t];
+    const bool live = threadIdx.x < nqr;
+    const u32 k = live ? threadIdx.x : nqr - 1;
+    const RecordView<F> rec{records + (size_t)proof * L.rec_bytes, L};
+    const unsigned char* section = rounds + (size_t)proof * C.proof_stride;
+    const u32* dir = reinterpret_cast<const u32*>(rec.p + C.rec_dir_off) + t * nqr;
+    const T* cap = tr.cap_word == ~0u ? circuit_cap : rec.caps() + tr.cap_word;
+    const u64 leaf = rec.x_index(k) >> tr.shift;
+    if (live) { s_leaf[k] = leaf; s_taken[k] = 0; }
+    Sponge<F> sp;
+    sp.init(sponge_lds);
+    __syncthreads();
+    const unsigned char* entry = section + dir[k];
+    const u32 stored_words = t < VERIFY_ORACLES ? tr.num_words : tr.num_words - D;   // a layer's coset lacks one element
+    T cur[HW];
+    if (t < VERIFY_ORACLES) {
+        vq::leaf_digest<F>(sp, tr.num_words, [entry](u32 i) { return vq::load_word<F>(entry + (size_t)i * TS); }, cur);
+    } else {
+        const u32 li = t - VERIFY_ORACLES, ab = L.arity_bits[li];
+        const u32 first = vc::first_with(k, [&](u32 j) { return s_leaf[j]; });
+        const u32 at = (u32)((rec.x_index(first) >> (tr.shift - ab)) & (((u64)1 << ab) - 1));
+        const T* ins = inferred + (((size_t)proof * L.num_layers + li) * nqr + k) * D;
+        vq::leaf_digest<F>(sp, tr.num_words, [entry, at, ins](u32 i) { return vc::inflated_word<F>(entry, at, ins, i); }, cur);
+    }
+    const size_t path_at = (size_t)stored_words * TS + 1;   // behind the row and the length byte
+    for (u32 level = 0; level < tr.path_len; level++) {
+#pragma unroll
+        for (u32 i = 0; i < HW; i++)
+            if (live) s_node[k * HW + i] = cur[i];
+        __syncthreads();
+        const vc::Source src = vc::sibling_source(nqr, k, [&](u32 j) { return s_leaf[j] >> level; });
+        T sib[HW];
+        if (src.sibling != vc::NO_QUERY) {
+#pragma unroll
+            for (u32 i = 0; i < HW; i++) sib[i] = s_node[src.sibling * HW + i];
+        } else {
+            const u32 nth = min(s_taken[src.first], tr.path_len - 1);   // (the host checked the counts; this keeps the read in the slot)
+            const unsigned char* stored = section + dir[src.first] + path_at + (size_t)nth * HW * TS;
+#pragma unroll
+            for (u32 i = 0; i < HW; i++) sib[i] = vq::load_word<F>(stored + i * TS);
+        }
+        const bool took = src.sibling == vc::NO_QUERY && src.first == k;
+        __syncthreads();   // every lane has read the nodes and the counters of this level
+        vq::two_to_one<F>(sp, cur, [&sib](u32 i) { return sib[i]; }, ((leaf >> level) & 1) != 0);
+        if (live && took) s_taken[k]++;
+    }
+    const u64 cap_index = leaf >> tr.path_len;
+    bool ok = true;
+#pragma unroll
+    for (u32 i = 0; i < HW; i++) ok = ok && cur[i] == cap[cap_index * HW + i];
+    const u32 pos = t < VERIFY_ORACLES ? vq::pos_initial_path(t) : vq::pos_layer_path(VERIFY_ORACLES, t - VERIFY_ORACLES);
+    if (live && !ok) atomicMin(reinterpret_cast<unsigned long long*>(keys + proof), (unsigned long long)vq::fail_key(k, pos));
+}
+
 inline u32 nblk(u64 n, u32 b) { return (u32)((n + b - 1) / b); }
 
 }  // namespace
@@ -107,6 +244,24 @@ void verify_queries(const VerifyLayout& L, const unsigned char* rounds, const un
     hipLaunchKernelGGL(k_verify_queries<F>, dim3(nblk(total, 64)), dim3(64), 0, st, L, rounds, records, keys);
 }
 
+template <class F>
+void verify_compressed_queries(const VerifyCompressedLayout& C, const unsigned char* rounds, const unsigned char* records,
+                               typename F::T* inferred, u64* keys, hipStream_t st) {
+    if (!C.L.num_proofs || !C.L.nqr) return;
+    hipLaunchKernelGGL(k_vc_queries<F>, dim3(C.L.num_proofs), dim3(64 * nblk(C.L.nqr, 64)), 0, st, C, rounds, records, inferred, keys);
+}
+template <class F>
+void verify_compressed_paths(const VerifyCompressedLayout& C, const unsigned char* rounds, const unsigned char* records,
+                             const typename F::T* circuit_cap, const typename F::T* inferred, u64* keys, hipStream_t st) {
+    if (!C.L.num_proofs || !C.L.nqr) return;
+    hipLaunchKernelGGL(k_vc_paths<F>, dim3(C.L.num_proofs, VERIFY_ORACLES + C.L.num_layers), dim3(64 * nblk(C.L.nqr, 64)), 0, st, C, rounds,
+                       records, circuit_cap, inferred, keys);
+}
+
+template void verify_compressed_queries<GlF>(const VerifyCompressedLayout&, const unsigned char*, const unsigned char*, u64*, u64*, hipStream_t);
+template void verify_compressed_queries<BbF>(const VerifyCompressedLayout&, const unsigned char*, const unsigned char*, u32*, u64*, hipStream_t);
+template void verify_compressed_paths<GlF>(const VerifyCompressedLayout&, const unsigned char*, const unsigned char*, const u64*, const u64*, u64*, hipStream_t);
+template void verify_compressed_paths<BbF>(const VerifyCompressedLayout&, const unsigned char*, const unsigned char*, const u32*, const u32*, u64*, hipStream_t);
 template void verify_paths<GlF>(const VerifyLayout&, const unsigned char*, const unsigned char*, const u64*, u64*, hipStream_t);
 template void verify_paths<BbF>(const VerifyLayout&, const unsigned char*, const unsigned char*, const u32*, u64*, hipStream_t);
 template void verify_queries<GlF>(const VerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);

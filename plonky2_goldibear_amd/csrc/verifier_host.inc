@@ -33,6 +33,10 @@ inline const char* vcheck_text(u32 check) {
     case GB_VCHECK_LAYER_PATH_LEN: return "FRI layer Merkle path of the wrong length";
     case GB_VCHECK_LAYER_PATH: return "FRI layer Merkle path does not lead to the cap";
     case GB_VCHECK_FINAL_POLY: return "Final polynomial evaluation is invalid. (fri/verifier.rs:240-247)";
+    // what a compressed proof alone can fail on (compress_host.inc), as gb_verify_compressed words it
+    case GB_VCHECK_COMPRESSED_INDICES: return "the compressed proof's query indices are not the transcript's";
+    case GB_VCHECK_COMPRESSED_MISSING_SIBLING: return "compressed Merkle proof is missing a sibling";
+    case GB_VCHECK_COMPRESSED_TRAILING: return "trailing bytes in compressed proof";
     default: return "";
     }
 }
@@ -40,7 +44,7 @@ inline gb_status vcheck_status(u32 check) {
     switch (check) {
     case GB_VCHECK_NONE: return GB_OK;
     case GB_VCHECK_VANISHING: case GB_VCHECK_POW: case GB_VCHECK_INITIAL_PATH: case GB_VCHECK_CONSISTENCY: case GB_VCHECK_LAYER_PATH:
-    case GB_VCHECK_FINAL_POLY: return GB_ERR_VERIFY;
+    case GB_VCHECK_FINAL_POLY: case GB_VCHECK_COMPRESSED_INDICES: return GB_ERR_VERIFY;
     default: return GB_ERR_INVALID;
     }
 }

@@ -7,6 +7,12 @@
 // page-locked slot; a proof that fails here, or that the host checks whole, takes no place in the slot.  Then one upload and the
 // two kernels of kernels_verify.hip on the context's stream.  There are two slots, so the host stage of chunk k+1 runs while the
 // kernels of chunk k do.  The failure keys of every chunk are read back once, at the end.
+//
+// gb_verify_compressed_batch is the same call over a second plan (CompressedBatchPlan): its host stage reads a compressed proof with
+// compress_host.inc's parser, decides from the query indices alone how many siblings every stored path must hold, and stages the
+// query section as it stands with a directory of its entries; its kernels are the k_vc_ pair of kernels_verify.hip.
+
+#include "verify_compressed.hpp"
 
 namespace {
 
@@ -17,6 +23,8 @@ struct BatchPlan {
     ProofShape<F> sh;
     gbk::VerifyLayout L{};
     size_t head_bytes = 0, query_bytes = 0, tail_fixed_bytes = 0, per_proof_bytes = 0;
+    size_t stride = 0;          // a proof's place among the staged query sections
+    size_t scratch_bytes = 0;   // per proof, on the device alone
     explicit BatchPlan(const Circuit<F>* c) : sh(c) {
         constexpr size_t TS = sizeof(T);
         constexpr u32 D = F::D, H = F::H;
@@ -60,18 +68,70 @@ struct BatchPlan {
         L.rec_x_off = (u32)ext_bytes;
         L.rec_caps_off = (u32)(ext_bytes + 8 * (size_t)sh.nqr);
         L.rec_bytes = (u32)((L.rec_caps_off + (3 + nl) * sh.cap_elems * TS + 15) & ~(size_t)15);
+        stride = query_bytes;
         per_proof_bytes = query_bytes + L.rec_bytes;
+    }
+    static const char* scope(int i) {
+        static const char* const names[4] = {"verify batch: host stage", "verify batch: upload", "verify batch: paths", "verify batch: queries"};
+        return names[i];
+    }
+};
+
+// gb_verify_compressed_batch: the circuit's shape as above (an upper bound of every compressed query section), a directory in
+// each record, the inferred elements as device scratch
+template <class F>
+struct CompressedBatchPlan : BatchPlan<F> {
+    gbk::VerifyCompressedLayout C{};
+    bool device_ok = true;   // a proof's query rounds share a workgroup
+    explicit CompressedBatchPlan(const Circuit<F>* c) : BatchPlan<F>(c) {
+        constexpr size_t TS = sizeof(typename F::T);
+        gbk::VerifyLayout& L = this->L;
+        const u32 ntrees = gbk::VERIFY_ORACLES + L.num_layers;
+        u32 max_path = 0;
+        for (u32 t = 0; t < ntrees; t++) max_path = std::max(max_path, L.trees[t].path_len);
+        // (the kernels bound a path by its tree's height: the padding keeps such a read inside the slot whatever the entry)
+        this->stride = (this->query_bytes + (size_t)max_path * F::H * TS + 15) & ~(size_t)15;
+        C.rec_dir_off = L.rec_bytes;
+        L.rec_bytes = (u32)((L.rec_bytes + 4 * (size_t)ntrees * L.nqr + 15) & ~(size_t)15);
+        this->scratch_bytes = ((size_t)L.num_layers * L.nqr * F::D * TS + 15) & ~(size_t)15;
+        this->per_proof_bytes = this->stride + L.rec_bytes + this->scratch_bytes;
+        device_ok = L.nqr <= gbk::VERIFY_COMPRESSED_MAX_QUERIES && this->stride <= 0x7FFFFFFFu;
+        C.proof_stride = (u32)this->stride;
+    }
+    static const char* scope(int i) {
+        static const char* const names[4] = {"verify compressed batch: host stage", "verify compressed batch: upload",
+                                             "verify compressed batch: queries", "verify compressed batch: paths"};
+        return names[i];
     }
 };
 
 inline gb_verify_result vresult(const VerifyFail& f) { return gb_verify_result{(uint32_t)f.code, f.check, f.query_round, f.index}; }
 
-// The host stage of one proof.  true: its query rounds and record stand at rounds_dst / rec_dst for the device; false: *res is final.
+// a proof's record (kernels.hpp: VerifyLayout)
 template <class F>
-bool verify_host_stage(Circuit<F>* c, const BatchPlan<F>& plan, const uint8_t* bytes, size_t len, gb_verify_result* res,
-                       unsigned char* rounds_dst, unsigned char* rec_dst) {
+void stage_record(const ProofShape<F>& sh, const gbk::VerifyLayout& L, const ParsedProof<F>& pp, const Challenges<F>& chal,
+                  const FriQueryMath<F>& fri, unsigned char* rec_dst) {
     typedef typename F::T T;
     typedef typename F::E E;
+    E* e = reinterpret_cast<E*>(rec_dst);
+    e[0] = chal.fri_alpha;
+    for (u32 b = 0; b < 2; b++) { e[1 + b] = fri.red_open[b]; e[3 + b] = fri.alpha_shift[b]; e[5 + b] = fri.points[b]; }
+    for (u32 li = 0; li < L.num_layers; li++) e[7 + li] = chal.fri_betas[li];
+    for (u32 i = 0; i < L.final_len; i++) e[7 + L.num_layers + i] = pp.final_poly[i];
+    std::memcpy(rec_dst + L.rec_x_off, chal.x_indices.data(), 8 * (size_t)L.nqr);
+    T* caps = reinterpret_cast<T*>(rec_dst + L.rec_caps_off);
+    const size_t ce = sh.cap_elems;
+    std::memcpy(caps, pp.wires_cap.data(), ce * sizeof(T));
+    std::memcpy(caps + ce, pp.zs_cap.data(), ce * sizeof(T));
+    std::memcpy(caps + 2 * ce, pp.quot_cap.data(), ce * sizeof(T));
+    for (u32 li = 0; li < L.num_layers; li++) std::memcpy(caps + (3 + li) * ce, pp.layer_caps[li].data(), ce * sizeof(T));
+}
+
+// The host stage of one proof.  true: its query rounds and record stand at rounds_dst / rec_dst for the device; false: *res is final.
+template <class F>
+bool host_stage(Circuit<F>* c, const BatchPlan<F>& plan, const uint8_t* bytes, size_t len, gb_verify_result* res,
+                unsigned char* rounds_dst, unsigned char* rec_dst) {
+    typedef typename F::T T;
     constexpr u32 H = F::H;
     const ProofShape<F>& sh = plan.sh;
     const gbk::VerifyLayout& L = plan.L;
@@ -96,22 +156,98 @@ bool verify_host_stage(Circuit<F>* c, const BatchPlan<F>& plan, const uint8_t* b
             return false;
         }
         std::memcpy(rounds_dst, bytes + plan.head_bytes, plan.query_bytes);
-        E* e = reinterpret_cast<E*>(rec_dst);
-        e[0] = chal.fri_alpha;
-        for (u32 b = 0; b < 2; b++) { e[1 + b] = fri.red_open[b]; e[3 + b] = fri.alpha_shift[b]; e[5 + b] = fri.points[b]; }
-        for (u32 li = 0; li < L.num_layers; li++) e[7 + li] = chal.fri_betas[li];
-        for (u32 i = 0; i < L.final_len; i++) e[7 + L.num_layers + i] = pp.final_poly[i];
-        std::memcpy(rec_dst + L.rec_x_off, chal.x_indices.data(), 8 * (size_t)L.nqr);
-        T* caps = reinterpret_cast<T*>(rec_dst + L.rec_caps_off);
-        const size_t ce = sh.cap_elems;
-        std::memcpy(caps, pp.wires_cap.data(), ce * sizeof(T));
-        std::memcpy(caps + ce, pp.zs_cap.data(), ce * sizeof(T));
-        std::memcpy(caps + 2 * ce, pp.quot_cap.data(), ce * sizeof(T));
-        for (u32 li = 0; li < L.num_layers; li++) std::memcpy(caps + (3 + li) * ce, pp.layer_caps[li].data(), ce * sizeof(T));
+        stage_record<F>(sh, L, pp, chal, fri, rec_dst);
         return true;
     } catch (const VerifyFail& f) {
         *res = vresult(f);
         return false;
+    }
+}
+
+// The host stage of one COMPRESSED proof: gb_verify_compressed up to the query rounds, in its order.  What decompress_impl finds while
+// it re-inflates the paths - a path that holds too few siblings - follows from the indices (verify_compressed.hpp:
+// sibling_counts), so it is decided here, in front of the vanishing identity as there.
+template <class F>
+bool host_stage(Circuit<F>* c, const CompressedBatchPlan<F>& plan, const uint8_t* bytes, size_t len, gb_verify_result* res,
+                unsigned char* rounds_dst, unsigned char* rec_dst) {
+    const ProofShape<F>& sh = plan.sh;
+    const gbk::VerifyLayout& L = plan.L;
+    *res = gb_verify_result{GB_OK, GB_VCHECK_NONE, UINT32_MAX, UINT32_MAX};
+    try {
+        ParsedProof<F> pp;
+        CompressedIndex ix;
+        parse_compressed(c, sh, bytes, len, pp, ix);
+        Challenges<F> chal;
+        get_challenges(c, sh, pp, chal);
+        if (chal.x_indices != ix.stored) vfail(GB_VCHECK_COMPRESSED_INDICES);
+        // the sibling plan: per tree what every entry must hold against what it holds, and the directory
+        const u32 nqr = L.nqr, ntrees = gbk::VERIFY_ORACLES + L.num_layers;
+        u32* dir = reinterpret_cast<u32*>(rec_dst + plan.C.rec_dir_off);
+        std::vector<u64> leaf(nqr);
+        std::vector<u32> need(nqr), entry_need;
+        bool missing = false, surplus = false;
+        for (u32 t = 0; t < ntrees; t++) {
+            const gbk::VerifyTree& tr = L.trees[t];
+            const std::vector<CompressedEntry>& entries = t < gbk::VERIFY_ORACLES ? ix.initial : ix.steps[t - gbk::VERIFY_ORACLES];
+            const u32 o = t < gbk::VERIFY_ORACLES ? t : 0;
+            for (u32 k = 0; k < nqr; k++) leaf[k] = chal.x_indices[k] >> tr.shift;
+            gbk::vc::sibling_counts(leaf.data(), nqr, tr.path_len, need.data());
+            entry_need.assign(entries.size(), 0);
+            for (u32 k = 0; k < nqr; k++) {
+                const CompressedEntry& en = CompressedIndex::at(entries, leaf[k]);
+                entry_need[&en - entries.data()] += need[k];   // (zero but for the first query round of the entry)
+                dir[(size_t)t * nqr + k] = (u32)(en.row[o] - ix.queries_begin);
+            }
+            for (size_t e = 0; e < entries.size(); e++) {
+                missing = missing || entries[e].siblings[o] < entry_need[e];
+                surplus = surplus || entries[e].siblings[o] > entry_need[e];
+            }
+        }
+        if (missing) vfail(GB_VCHECK_COMPRESSED_MISSING_SIBLING);
+        check_vanishing<F>(c, sh, pp, chal);
+        const FriQueryMath<F> fri(sh, pp, chal);
+        check_pow<F>(c->cfg.proof_of_work_bits, chal);
+        const size_t section = ix.queries_end - ix.queries_begin;
+        if (surplus || !plan.device_ok || section > plan.query_bytes) {
+            // gb_verify_compressed ignores what a path holds beyond its need: its own walk, which is right by construction
+            const std::vector<uint8_t> full = decompress_impl(c, bytes, len);
+            verify_impl(c, full.data(), full.size());
+            return false;
+        }
+        std::memcpy(rounds_dst, bytes + ix.queries_begin, section);
+        stage_record<F>(sh, L, pp, chal, fri, rec_dst);
+        return true;
+    } catch (const VerifyFail& f) {
+        *res = vresult(f);
+        return false;
+    }
+}
+
+template <class F>
+void launch_chunk(gb_ctx* ctx, const BatchPlan<F>& plan, const gbk::VerifyLayout& L, const unsigned char* d_rounds, const unsigned char* d_recs,
+                  const typename F::T* d_cap, unsigned char*, u64* keys) {
+    {
+        Scope sc(ctx, plan.scope(2));
+        gbk::verify_paths<F>(L, d_rounds, d_recs, d_cap, keys, ctx->stream);
+    }
+    {
+        Scope sc(ctx, plan.scope(3));
+        gbk::verify_queries<F>(L, d_rounds, d_recs, keys, ctx->stream);
+    }
+}
+template <class F>
+void launch_chunk(gb_ctx* ctx, const CompressedBatchPlan<F>& plan, const gbk::VerifyLayout& L, const unsigned char* d_rounds,
+                  const unsigned char* d_recs, const typename F::T* d_cap, unsigned char* d_scratch, u64* keys) {
+    gbk::VerifyCompressedLayout C = plan.C;
+    C.L = L;
+    typename F::T* inferred = reinterpret_cast<typename F::T*>(d_scratch);
+    {
+        Scope sc(ctx, plan.scope(2));
+        gbk::verify_compressed_queries<F>(C, d_rounds, d_recs, inferred, keys, ctx->stream);
+    }
+    {
+        Scope sc(ctx, plan.scope(3));
+        gbk::verify_compressed_paths<F>(C, d_rounds, d_recs, d_cap, inferred, keys, ctx->stream);
     }
 }
 
@@ -153,18 +289,20 @@ gb_status verify_stage_ready(gb_ctx* ctx, size_t slot_bytes, size_t key_bytes) {
     return ensure(ctx, ctx->vkeys, key_bytes);
 }
 
-template <class F>
+template <class F, class Plan>
 gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proofs, const size_t* lens, u32 num_proofs, gb_verify_result* results) {
     typedef typename F::T T;
-    const BatchPlan<F> plan(c);
+    const Plan plan(c);
     gbk::VerifyLayout L = plan.L;
     const size_t cap_bytes = ((plan.sh.cap_elems * sizeof(T)) + 15) & ~(size_t)15;
     // proofs per chunk: what "verify_chunk_bytes" holds, at least one; rounds * proofs stays a 32-bit count in the kernels
     size_t per_chunk = std::max<size_t>(1, ctx->verify_chunk_bytes / plan.per_proof_bytes);
     per_chunk = std::min<size_t>(per_chunk, std::min<size_t>(num_proofs, (size_t)0x7FFFFFFF / std::max<u32>(1, L.nqr)));
     // a slot: the circuit's cap, the proofs' query rounds back to back (of any byte length), then - aligned again - their records
-    const size_t rounds_region = (per_chunk * plan.query_bytes + 15) & ~(size_t)15;
-    const size_t slot_bytes = cap_bytes + rounds_region + per_chunk * (size_t)L.rec_bytes;
+    // and, on the device alone, the plan's scratch
+    const size_t rounds_region = (per_chunk * plan.stride + 15) & ~(size_t)15;
+    const size_t recs_region = per_chunk * (size_t)L.rec_bytes;
+    const size_t slot_bytes = cap_bytes + rounds_region + recs_region + per_chunk * plan.scratch_bytes;
     if (gb_status s = verify_stage_ready(ctx, slot_bytes, 8 * (size_t)num_proofs)) return s;
     u64* keys_dev = static_cast<u64*>(ctx->vkeys.p);
     HIP_TRY(ctx, hipMemsetAsync(keys_dev, 0xFF, 8 * (size_t)num_proofs, ctx->stream));
@@ -186,13 +324,13 @@ gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proof
         std::vector<u32> owner(count);
         size_t lo = 0, hi = count;
         {
-            Scope sc(ctx, "verify batch: host stage");
+            Scope sc(ctx, plan.scope(0));
             auto work = [&]() {
                 try {
                     for (size_t i; (i = next.fetch_add(1)) < count;) {   // proof base + i stages into place i
                         const size_t pi = base + i;
-                        act[i] = verify_host_stage<F>(c, plan, static_cast<const uint8_t*>(proofs[pi]), lens[pi], &results[pi],
-                                                      h_rounds + i * plan.query_bytes, h_recs + i * L.rec_bytes);
+                        act[i] = host_stage<F>(c, plan, static_cast<const uint8_t*>(proofs[pi]), lens[pi], &results[pi],
+                                               h_rounds + i * plan.stride, h_recs + i * L.rec_bytes);
                     }
                 } catch (...) {   // (std::bad_alloc: the call fails as a whole)
                     std::lock_guard<std::mutex> g(thrown_lock);
@@ -211,7 +349,7 @@ gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proof
                 while (lo < hi && act[lo]) lo++;
                 while (hi > lo && !act[hi - 1]) hi--;
                 if (lo >= hi) break;
-                std::memcpy(h_rounds + lo * plan.query_bytes, h_rounds + (hi - 1) * plan.query_bytes, plan.query_bytes);
+                std::memcpy(h_rounds + lo * plan.stride, h_rounds + (hi - 1) * plan.stride, plan.stride);
                 std::memcpy(h_recs + lo * L.rec_bytes, h_recs + (hi - 1) * L.rec_bytes, L.rec_bytes);
                 owner[lo] = owner[hi - 1];
                 act[lo] = 1;
@@ -225,20 +363,13 @@ gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proof
         unsigned char* d_rounds = reinterpret_cast<unsigned char*>(dev) + cap_bytes;
         unsigned char* d_recs = d_rounds + rounds_region;
         {
-            Scope sc(ctx, "verify batch: upload");
+            Scope sc(ctx, plan.scope(1));
             std::memcpy(host, c->cap_host.data(), plan.sh.cap_elems * sizeof(T));   // the circuit's cap rides in front of every chunk
-            HIP_TRY(ctx, hipMemcpyAsync(dev, host, cap_bytes + (size_t)active * plan.query_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(dev, host, cap_bytes + (size_t)active * plan.stride, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipMemcpyAsync(d_recs, h_recs, (size_t)active * L.rec_bytes, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipEventRecord(ctx->vstage_read[s], ctx->stream));
         }
-        {
-            Scope sc(ctx, "verify batch: paths");
-            gbk::verify_paths<F>(L, d_rounds, d_recs, reinterpret_cast<const T*>(dev), keys_dev + base, ctx->stream);
-        }
-        {
-            Scope sc(ctx, "verify batch: queries");
-            gbk::verify_queries<F>(L, d_rounds, d_recs, keys_dev + base, ctx->stream);
-        }
+        launch_chunk<F>(ctx, plan, L, d_rounds, d_recs, reinterpret_cast<const T*>(dev), d_recs + recs_region, keys_dev + base);
         HIP_TRY(ctx, hipGetLastError());
     }
     std::vector<u64> keys(num_proofs);
@@ -248,20 +379,31 @@ gb_status verify_batch_impl(gb_ctx* ctx, Circuit<F>* c, const void* const* proof
     return GB_OK;
 }
 
-// GB_CATCH of an entry point that returns text instead of a status: the empty string
-struct TextEntryPoint {};
-const char* unwound(TextEntryPoint, const char*) noexcept { return ""; }
+// gb_verify_compressed_batch without a context: the host stage alone, proof by proof on the calling thread.  What it decides is
+// final; a proof it would hand to the device is answered GB_ERR_INVALID, for there is none.
+template <class F>
+void compressed_host_stage_only(Circuit<F>* c, const void* const* proofs, const size_t* lens, u32 num_proofs, gb_verify_result* results) {
+    const CompressedBatchPlan<F> plan(c);
+    std::vector<unsigned char> rounds(plan.stride), rec(plan.L.rec_bytes);
+    for (u32 i = 0; i < num_proofs; i++)
+        if (!proofs[i] || host_stage<F>(c, plan, static_cast<const uint8_t*>(proofs[i]), lens[i], &results[i], rounds.data(), rec.data()))
+            results[i] = gb_verify_result{GB_ERR_INVALID, GB_VCHECK_NONE, UINT32_MAX, UINT32_MAX};
+}
 
-}  // namespace
-
-extern "C" {
-
-gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
-                          uint32_t flags, void* results) try {
-    if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null ctx");
+// gb_verify_batch and gb_verify_compressed_batch: one call, two plans
+gb_status verify_batch_call(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
+                            uint32_t flags, void* results, bool compressed) {
+    if (!ctx) {
+        if (compressed && c && flags == 0 && num_proofs && proofs && proof_lens && results && !c->arity_pending) {
+            gb_verify_result* res = static_cast<gb_verify_result*>(results);
+            if (c->field == GB_GOLDILOCKS) compressed_host_stage_only(static_cast<Circuit<GlF>*>(c), proofs, proof_lens, num_proofs, res);
+            else compressed_host_stage_only(static_cast<Circuit<BbF>*>(c), proofs, proof_lens, num_proofs, res);
+        }
+        return fail(nullptr, GB_ERR_INVALID, "null ctx");
+    }
     if (!c) return fail(ctx, GB_ERR_INVALID, "null circuit");
     if (c->ctx && c->ctx != ctx) return fail(ctx, GB_ERR_INVALID, "the circuit belongs to a different context");
-    if (flags != 0) return fail(ctx, GB_ERR_INVALID, "gb_verify_batch: flags must be 0");
+    if (flags != 0) return fail(ctx, GB_ERR_INVALID, compressed ? "gb_verify_compressed_batch: flags must be 0" : "gb_verify_batch: flags must be 0");
     if (num_proofs == 0) return GB_OK;
     if (!proofs || !proof_lens || !results) return fail(ctx, GB_ERR_INVALID, "null argument");
     for (uint32_t i = 0; i < num_proofs; i++)
@@ -274,8 +416,15 @@ gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs,
     gb_verify_result* res = static_cast<gb_verify_result*>(results);
     gb_status s;
     try {
-        s = c->field == GB_GOLDILOCKS ? verify_batch_impl<GlF>(ctx, static_cast<Circuit<GlF>*>(c), proofs, proof_lens, num_proofs, res)
-                                      : verify_batch_impl<BbF>(ctx, static_cast<Circuit<BbF>*>(c), proofs, proof_lens, num_proofs, res);
+        if (c->field == GB_GOLDILOCKS) {
+            Circuit<GlF>* cf = static_cast<Circuit<GlF>*>(c);
+            s = compressed ? verify_batch_impl<GlF, CompressedBatchPlan<GlF>>(ctx, cf, proofs, proof_lens, num_proofs, res)
+                           : verify_batch_impl<GlF, BatchPlan<GlF>>(ctx, cf, proofs, proof_lens, num_proofs, res);
+        } else {
+            Circuit<BbF>* cf = static_cast<Circuit<BbF>*>(c);
+            s = compressed ? verify_batch_impl<BbF, CompressedBatchPlan<BbF>>(ctx, cf, proofs, proof_lens, num_proofs, res)
+                           : verify_batch_impl<BbF, BatchPlan<BbF>>(ctx, cf, proofs, proof_lens, num_proofs, res);
+        }
     } catch (...) {
         (void)hipStreamSynchronize(ctx->stream);   // earlier chunks may still read the staging slots
         throw;
@@ -290,6 +439,24 @@ gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs,
     if (!bad) return GB_OK;
     return fail(ctx, GB_ERR_VERIFY, std::to_string(bad) + " of " + std::to_string(num_proofs) + " proofs did not verify; the first is proof " +
                                         std::to_string(first) + ": " + vcheck_text(res[first].check));
+}
+
+// GB_CATCH of an entry point that returns text instead of a status: the empty string
+struct TextEntryPoint {};
+const char* unwound(TextEntryPoint, const char*) noexcept { return ""; }
+
+}  // namespace
+
+extern "C" {
+
+gb_status gb_verify_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens, uint32_t num_proofs,
+                          uint32_t flags, void* results) try {
+    return verify_batch_call(ctx, c, proofs, proof_lens, num_proofs, flags, results, false);
+} GB_CATCH(ctx)
+
+gb_status gb_verify_compressed_batch(gb_ctx* ctx, gb_circuit* c, const void* const* proofs, const size_t* proof_lens,
+                                     uint32_t num_proofs, uint32_t flags, void* results) try {
+    return verify_batch_call(ctx, c, proofs, proof_lens, num_proofs, flags, results, true);
 } GB_CATCH(ctx)
 
 const char* gb_verify_check_text(uint32_t check) try {

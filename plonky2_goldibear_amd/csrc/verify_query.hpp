@@ -50,44 +50,58 @@ GB_HD u64 rev_bits(u64 x, u32 bits) {
     return r;
 }
 
-// verify_merkle_proof_to_cap (hash/merkle_proofs.rs:54-76): hash_or_noop of the leaf (plonk/config.rs:70-84), two_to_one
-// (hash/hashing.rs:76-96) up `path_len` siblings, then the cap entry that is left of the index.
-template <class F, class H>
-GB_HD bool merkle_path_ok(H& h, const unsigned char* leaf, u32 num_words, u64 index, const unsigned char* siblings, u32 path_len,
-                          const typename F::T* cap) {
+// hash_or_noop of a leaf (plonk/config.rs:70-84) into cur[HW]; word(i): the leaf's i-th canonical word
+template <class F, class H, class WordAt>
+GB_HD void leaf_digest(H& h, u32 num_words, WordAt word, typename F::T* cur) {
     typedef typename F::T T;
     constexpr u32 HW = F::H, W = F::SPONGE_W;
-    constexpr size_t TS = sizeof(T);
-    T cur[HW];
     if (num_words <= HW) {
 #pragma unroll
-        for (u32 i = 0; i < HW; i++) cur[i] = i < num_words ? load_word<F>(leaf + i * TS) : (T)0;
+        for (u32 i = 0; i < HW; i++) cur[i] = i < num_words ? word(i) : (T)0;
     } else {   // hash_no_pad: overwrite mode, rate 8
 #pragma unroll
         for (u32 i = 0; i < W; i++) h.set_canonical((int)i, (T)0);
         for (u32 k0 = 0; k0 < num_words; k0 += 8) {
 #pragma unroll
             for (u32 k = 0; k < 8; k++)
-                if (k0 + k < num_words) h.set_canonical((int)k, load_word<F>(leaf + (size_t)(k0 + k) * TS));
+                if (k0 + k < num_words) h.set_canonical((int)k, word(k0 + k));
             h.permute();
         }
 #pragma unroll
         for (u32 i = 0; i < HW; i++) cur[i] = h.out((int)i);
     }
+}
+// two_to_one (hash/hashing.rs:76-96) of cur and its sibling into cur; right: cur is the right child.  sibling(i): canonical word i
+template <class F, class H, class SiblingAt>
+GB_HD void two_to_one(H& h, typename F::T* cur, SiblingAt sibling, bool right) {
+    typedef typename F::T T;
+    constexpr u32 HW = F::H, W = F::SPONGE_W;
+#pragma unroll
+    for (u32 i = 0; i < HW; i++) {
+        const T s = sibling(i);
+        h.set_canonical((int)i, right ? s : cur[i]);
+        h.set_canonical((int)(HW + i), right ? cur[i] : s);
+    }
+#pragma unroll
+    for (u32 i = 2 * HW; i < W; i++) h.set_canonical((int)i, (T)0);
+    h.permute();
+#pragma unroll
+    for (u32 i = 0; i < HW; i++) cur[i] = h.out((int)i);
+}
+
+// verify_merkle_proof_to_cap (hash/merkle_proofs.rs:54-76): hash_or_noop of the leaf, two_to_one up `path_len` siblings, then the
+// cap entry that is left of the index.
+template <class F, class H>
+GB_HD bool merkle_path_ok(H& h, const unsigned char* leaf, u32 num_words, u64 index, const unsigned char* siblings, u32 path_len,
+                          const typename F::T* cap) {
+    typedef typename F::T T;
+    constexpr u32 HW = F::H;
+    constexpr size_t TS = sizeof(T);
+    T cur[HW];
+    leaf_digest<F>(h, num_words, [leaf](u32 i) { return load_word<F>(leaf + (size_t)i * TS); }, cur);
     for (u32 l = 0; l < path_len; l++) {
         const unsigned char* sib = siblings + (size_t)l * HW * TS;
-        const bool right = index & 1;   // the running digest is the right child
-#pragma unroll
-        for (u32 i = 0; i < HW; i++) {
-            const T s = load_word<F>(sib + i * TS);
-            h.set_canonical((int)i, right ? s : cur[i]);
-            h.set_canonical((int)(HW + i), right ? cur[i] : s);
-        }
-#pragma unroll
-        for (u32 i = 2 * HW; i < W; i++) h.set_canonical((int)i, (T)0);
-        h.permute();
-#pragma unroll
-        for (u32 i = 0; i < HW; i++) cur[i] = h.out((int)i);
+        two_to_one<F>(h, cur, [sib](u32 i) { return load_word<F>(sib + i * TS); }, (index & 1) != 0);   // odd: cur is the right child
         index >>= 1;
     }
     bool ok = true;

@@ -23,6 +23,8 @@ GB_VIOLATION_GATE, GB_VIOLATION_SELECTOR, GB_VIOLATION_COPY = 1, 2, 3
 (GB_VCHECK_NONE, GB_VCHECK_TRUNCATED, GB_VCHECK_NON_CANONICAL, GB_VCHECK_PI_IMPLAUSIBLE, GB_VCHECK_PI_COUNT, GB_VCHECK_TRAILING,
  GB_VCHECK_VANISHING, GB_VCHECK_POW, GB_VCHECK_INITIAL_PATH_LEN, GB_VCHECK_INITIAL_PATH, GB_VCHECK_CONSISTENCY,
  GB_VCHECK_LAYER_PATH_LEN, GB_VCHECK_LAYER_PATH, GB_VCHECK_FINAL_POLY) = range(14)
+# what a compressed proof alone can fail on (gb_verify_compressed_batch)
+GB_VCHECK_COMPRESSED_INDICES, GB_VCHECK_COMPRESSED_MISSING_SIBLING, GB_VCHECK_COMPRESSED_TRAILING = 16, 17, 18
 GB_GOLDILOCKS, GB_BABYBEAR = 0, 1
 GB_INPUT_HOST, GB_INPUT_DEVICE = 0, 1
 GB_INPUT_P3_REPR = 2   # host elements are the reference's field types as they lie in memory (p3 words), not canonical values
@@ -68,6 +70,7 @@ SIGNATURES = {
     "gb_verify": (_i32, [_vp, _vp, _sz]),
     "gb_verify_batch": (_i32, [_vp, _vp, _cols, C.POINTER(_sz), _u32, _u32, _vp]),
     "gb_verify_check_text": (C.c_char_p, [_u32]),
+    "gb_verify_compressed_batch": (_i32, [_vp, _vp, _cols, C.POINTER(_sz), _u32, _u32, _vp]),
     "gb_proof_compress": (_i32, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_proof_decompress": (_i32, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_verify_compressed": (_i32, [_vp, _vp, _sz]),
@@ -234,7 +237,7 @@ class VerifyResult:
             self.ok, self.status, self.check, self.text, self.query_round, self.index)
 
 
-def verify_batch(ctx_handle, circuit_handle, proofs):
+def verify_batch(ctx_handle, circuit_handle, proofs, entry="gb_verify_batch"):
     """gb_verify_batch on a list of proof byte strings -> [VerifyResult]; a failing proof is reported, not raised - malformed
     arguments (and HIP / memory errors) still raise"""
     import numpy as np
@@ -249,11 +252,17 @@ def verify_batch(ctx_handle, circuit_handle, proofs):
             ptrs[i] = empty.ctypes.data
     lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
     res = (gb_verify_result * max(n, 1))()
-    st = lib.gb_verify_batch(ctx_handle, circuit_handle, ptrs, lens, n, 0, C.cast(res, C.c_void_p))
+    st = getattr(lib, entry)(ctx_handle, circuit_handle, ptrs, lens, n, 0, C.cast(res, C.c_void_p))
     if st not in (GB_OK, GB_ERR_VERIFY):
         check(st, ctx_handle)
     return [VerifyResult(r.status, r.check, (lib.gb_verify_check_text(r.check) or b"").decode(), r.query_round, r.index)
             for r in res[:n]]
+
+
+def verify_compressed_batch(ctx_handle, circuit_handle, proofs):
+    """gb_verify_compressed_batch on a list of CompressedProofWithPublicInputs byte strings -> [VerifyResult]: status and text are
+    gb_verify_compressed's, query_round / index what verify_batch reports on the decompressed proof"""
+    return verify_batch(ctx_handle, circuit_handle, proofs, entry="gb_verify_compressed_batch")
 
 
 class gb_sigma_info(C.Structure):

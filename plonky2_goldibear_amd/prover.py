@@ -583,6 +583,11 @@ class CircuitData(_ProofBytesOps, _FriParamsOps):
         native.VerifyResult, one per proof - status and text are verify()'s; a failing proof is reported, not raised."""
         return N.verify_batch(self.ctx.handle, self.handle, proofs)
 
+    def verify_compressed_batch(self, proofs):
+        """verify_compressed() of many compressed proofs of this circuit at once, checked as they stand on the device
+        (gb_verify_compressed_batch): a list of native.VerifyResult, one per proof - status and text are verify_compressed()'s."""
+        return N.verify_compressed_batch(self.ctx.handle, self.handle, proofs)
+
     def free(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self._lib.gb_circuit_free(self.handle)
@@ -642,6 +647,11 @@ class VerifierCircuitData(_ProofBytesOps, _FriParamsOps):
         """verify() of many proofs at once on the device of `ctx` (a GpuContext; the object itself has none): a list of
         native.VerifyResult, one per proof - a failing proof is reported, not raised."""
         return N.verify_batch(getattr(ctx, "handle", None), self.handle, proofs)
+
+    def verify_compressed_batch(self, ctx, proofs):
+        """gb_verify_compressed_batch with this verifier object as the circuit and `ctx`'s device: a list of native.VerifyResult,
+        one per compressed proof - a failing proof is reported, not raised."""
+        return N.verify_compressed_batch(getattr(ctx, "handle", None), self.handle, proofs)
 
     def free(self):
         if getattr(self, "handle", None):
