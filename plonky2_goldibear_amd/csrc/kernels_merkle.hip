@@ -243,10 +243,14 @@ __global__ __launch_bounds__(256, POSEIDON_OCC) void k_gl_poseidon_permute(const
 
 static inline u32 blocks_for(u64 n, u32 bs) { return (u32)((n + bs - 1) / bs); }
 
-// Below this many states a lone wave's ~56 us per lane-per-state permutation dominates; the cooperative form does ~3.6x the
-// instructions in total but its dependent chain is ~4x shorter (crossover between 2^14 and 2^15 states on 1024 SIMDs).
-static constexpr u64 COOP_MAX_STATES = 16384;  // measured: 2048 / 8192 / 16384 / 32768 -> 5.41 / 5.14 / 5.00 / 5.50 ms per 2^12-row proof;
-                                               // separate thresholds for levels and leaves (same-box sweeps, both fields) are within noise of this
+// Below this many states a lone wave's ~40 us per lane-per-state permutation dominates; the cooperative form issues several
+// times the instructions in total (sixteen lanes per state) but its dependent chain is ~2.5x shorter.  The durations cross
+// between 2^14 and 2^15 states for all three kernel pairs (one kernel trace, cooperative / lane-per-state, us;
+// profiles/coop_plain_rounds.txt):
+//   levels       2^13: 20.8 / 39.5   2^14: 33.7 / 41.2   2^15: 60.4 / 44.4
+//   leaves x 135 2^13:  317 /  600   2^14:  516 /  613   2^15:  957 /  631
+//   FRI leaves   2^13: 90.4 / 166.5  2^14: 137.9 / 166.4 2^15: 213.9 / 170.2   (arity 16)
+static constexpr u64 COOP_MAX_STATES = 16384;
 
 void gl_merkle_leaves(const u64* cols, size_t col_stride, u32 width, u64 num_leaves, u64* out, hipStream_t stream) {
     if (width > 4 && num_leaves <= COOP_MAX_STATES) {
