@@ -110,6 +110,9 @@ struct gb_ctx {
     size_t vstage_bytes = 0;
     hipEvent_t vstage_read[2] = {nullptr, nullptr};         // recorded behind the uploads out of a slot
     DeviceBuf vkeys;
+    // include/goldibear_gpu_test_hooks.h: gb_test_force_gate_fallback / gb_test_gate_fallback_launches (kernels.hpp GateLaunchOptions)
+    bool test_force_gate_fallback = false;
+    u64 test_gate_fallback_launches = 0;
 };
 static void drop_all_retry_state(gb_ctx* ctx);              // prover_host.inc
 static void drop_all_check_state(gb_ctx* ctx);              // prover_host.inc: what gb_check_witness keeps with the circuits

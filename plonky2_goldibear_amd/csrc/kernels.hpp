@@ -274,10 +274,16 @@ template <class F>
 bool quotient_values(const QuotientParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* zs,
                      const typename F::T* uniforms, typename F::T* qv, hipStream_t st);
 bool quotient_shape_supported(u32 field, u32 chunk, u32 num_challenges);
+// what the test hooks of include/goldibear_gpu_test_hooks.h ask of gate_constraints' dispatch (host side only: no kernel reads it)
+struct GateLaunchOptions {
+    bool force_fallback = false;        // take the lane-per-point LIGHT_GATES launch even when a tiled plan exists
+    u64* fallback_launches = nullptr;   // incremented per lane-per-point LIGHT_GATES launch, forced or not
+};
 // qv <- the alpha-folded gate constraints of a general gate set (kernels_gates.hip), any num_challenges <= MAX_CHALLENGES (slices)
 template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs = nullptr);
+                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs = nullptr,
+                      const GateLaunchOptions& opt = GateLaunchOptions());
 // ---- the witness check (kernels_check.hip's launchers; witness_check.hpp has the row logic).  hv: the selector and constant
 // columns as values on H, [num_selectors + num_constants][n], natural order, device form; wit: [num_wires][n] canonical words.
 // counts[MAX_LISTS] and offsets[MAX_LISTS + 1]: rows per list (a list per gate, then the rows with a selector violation) and

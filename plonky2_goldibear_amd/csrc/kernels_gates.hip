@@ -8,6 +8,7 @@
 // circuit with constraint programs (GB_GATE_PROGRAM) gets a third, the interpreter k_gate_programs.
 #include <algorithm>
 #include <utility>
+#include "fold_acc.hpp"
 #include "gates.hpp"
 #include "kernels.hpp"
 
@@ -16,42 +17,6 @@ namespace gbk {
 namespace {
 __device__ __forceinline__ u32 brev32g(u32 x, u32 bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
 
-// sum_i c_i * a_i of one gate's constraints against the powers of alpha, kept UNREDUCED until the gate is done: a term is a
-// product plus carry adds instead of a modular multiplication and a modular addition (Goldilocks 15 instructions against 29,
-// BabyBear 3 against 9 - and BabyBear folds against 6..10 challenges).  At most a few hundred terms per gate.
-template <class F>
-struct FoldAcc;
-template <>
-struct FoldAcc<GlF> {  // 160-bit sum of 128-bit products; fewer than 2^31 terms (gl::fold160)
-    u32 l0 = 0, l1 = 0, l2 = 0, l3 = 0, l4 = 0;
-    __device__ __forceinline__ void acc(u64 c, u64 a) {
-        u32 p0, p1, p2, p3, k0, k1, k2, k3;
-        gl::mul_limbs(c, a, p0, p1, p2, p3);
-        l0 = __builtin_addc(l0, p0, 0u, &k0);
-        l1 = __builtin_addc(l1, p1, k0, &k1);
-        l2 = __builtin_addc(l2, p2, k1, &k2);
-        l3 = __builtin_addc(l3, p3, k2, &k3);
-        l4 += k3;
-    }
-    __device__ __forceinline__ u64 finish() const { return gl::canon(gl::fold160(l0, l1, l2, l3, l4)); }
-};
-template <>
-struct FoldAcc<BbF> {  // Montgomery words: the sum S of (c R)(a R) is brought back with one reduction, S R^-1 = (sum c a) R
-    u64 lo = 0;
-    u32 hi = 0;
-    __device__ __forceinline__ void acc(u32 c, u32 a) {
-        const u64 p = (u64)c * a, s = lo + p;
-        hi += s < p;
-        lo = s;
-    }
-    // S = w0 + 2^32 w1 + 2^64 hi:  S 2^-32 = w0 2^-32 + w1 + hi 2^32  (mod p)
-    __device__ __forceinline__ u32 finish() const {
-        u32 w1 = (u32)(lo >> 32);  // < 2^32 < 3 p
-        w1 = w1 >= bb::P ? w1 - bb::P : w1;
-        w1 = w1 >= bb::P ? w1 - bb::P : w1;
-        return bb::add(bb::add(bb::reduce((u64)(u32)lo), w1), bb::mul(hi, bb::R2));
-    }
-};
 }  // namespace
 
 // SUBSET = LIGHT_GATES writes qv, HEAVY_GATES (the in-circuit hash gate, when the set has one) adds to it.
@@ -272,12 +237,14 @@ static bool has_heavy(const gates::GateSet& gs) {
     do {                                                                                                                      \
         TiledPlan plan;                                                                                                       \
         size_t smem = 0;                                                                                                      \
-        if (make_tiled_plan<FF>(p, &plan, &smem) &&                                                                           \
+        if (!opt.force_fallback && make_tiled_plan<FF>(p, &plan, &smem) &&                                                    \
             hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gate_constraints_tiled<FF, CC>),                             \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess)                         \
             hipLaunchKernelGGL((k_gate_constraints_tiled<FF, CC>), dim3((u32)(N / 64)), dim3(64 * TILED_WAVES), smem, st, p, plan, cs, wires, apow, pi_hash, qv); \
-        else                                                                                                                  \
+        else {                                                                                                                \
             hipLaunchKernelGGL((k_gate_constraints<FF, CC, gates::LIGHT_GATES>), grid, block, 0, st, p, cs, wires, apow, pi_hash, qv); \
+            if (opt.fallback_launches) ++*opt.fallback_launches;                                                              \
+        }                                                                                                                     \
         if (has_heavy(p.gs))                                                                                                  \
             hipLaunchKernelGGL((k_gate_constraints<FF, CC, gates::HEAVY_GATES>), grid, block, 0, st, p, cs, wires, apow, pi_hash, qv); \
         if (programs && programs->ps.num_programs)                                                                            \
@@ -289,7 +256,8 @@ static bool has_heavy(const gates::GateSet& gs) {
 // and the qv block of challenge k0 - the gate kernels index both relative to their first challenge
 template <class F>
 static bool gate_slice(GateParams<F> p, u32 k0, u32 width, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs) {
+                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs,
+                       const GateLaunchOptions& opt) {
     const size_t N = (size_t)1 << (p.log_n + p.rate_bits);   // points of the quotient domain
     const dim3 grid((u32)((N + 255) / 256)), block(256);
     apow += (size_t)k0 * p.nterms;
@@ -318,18 +286,19 @@ static bool gate_slice(GateParams<F> p, u32 k0, u32 width, const typename F::T* 
 }
 template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
-                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs) {
+                      const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs,
+                      const GateLaunchOptions& opt) {
     u32 widths[MAX_CHALLENGES];
     const u32 ns = challenge_slices(F::TAG, 4, p.num_challenges, widths);
     if (!ns) return false;
     for (u32 i = 0, k0 = 0; i < ns; k0 += widths[i], i++)
-        if (!gate_slice<F>(p, k0, widths[i], cs, wires, apow, pi_hash, qv, st, programs)) return false;
+        if (!gate_slice<F>(p, k0, widths[i], cs, wires, apow, pi_hash, qv, st, programs, opt)) return false;
     return true;
 }
 template bool gate_constraints<GlF>(const GateParams<GlF>&, const u64*, const u64*, const u64*, const u64*, u64*, hipStream_t,
-                                    const ProgramParams<GlF>*);
+                                    const ProgramParams<GlF>*, const GateLaunchOptions&);
 template bool gate_constraints<BbF>(const GateParams<BbF>&, const u32*, const u32*, const u32*, const u32*, u32*, hipStream_t,
-                                    const ProgramParams<BbF>*);
+                                    const ProgramParams<BbF>*, const GateLaunchOptions&);
 #undef GB_G
 
 }  // namespace gbk

@@ -743,7 +743,8 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
         const T* pi_dev = apow_dev + (size_t)nch * nterms + 2 * ((size_t)1 << qb);
         const gbk::ProgramParams<F> pp{c->programs, c->prog_instrs_dev, c->prog_lits_dev};
         if (!gbk::gate_constraints<F>(gp, (const T*)c->cs->lde, (const T*)wires->lde, apow_dev, pi_dev, qv, st,
-                                      c->programs.num_programs ? &pp : nullptr))
+                                      c->programs.num_programs ? &pp : nullptr,
+                                      gbk::GateLaunchOptions{ctx->test_force_gate_fallback, &ctx->test_gate_fallback_launches}))
             return fail(ctx, GB_ERR_UNSUPPORTED, "no gate-constraint kernel for this num_challenges");
     }
     if (!gbk::quotient_values<F>(qp, (const T*)c->cs->lde, (const T*)wires->lde, (const T*)zs->lde, uni_dev, qv, st))
@@ -1921,6 +1922,9 @@ static gb_status check_circuit_cfg(gb_ctx* ctx, const gb_circuit_config* cfg, Co
         return fail(ctx, GB_ERR_UNSUPPORTED,
                     "quotient kernel: degree factor 2, 4, 8 or 16; BabyBear num_challenges >= 4");
     if (cfg->num_routed_wires > cfg->num_wires || cfg->num_routed_wires == 0) return fail(ctx, GB_ERR_INVALID, "bad wire counts");
+    // as gb_verifier_create: no proof of a wider circuit verifies, and a gate's constraint count (<= its wires) stays where the
+    // unreduced fold sums of the gate kernels were checked (fold_acc.hpp FOLD_ACC_MAX_TERMS)
+    if (cfg->num_wires > 4096) return fail(ctx, GB_ERR_INVALID, "bad wire counts: more than 4096 wires");
     const u32 nchunks = (cfg->num_routed_wires + cfg->max_quotient_degree_factor - 1) / cfg->max_quotient_degree_factor;
     if (nchunks > gbk::MAX_CHUNKS) return fail(ctx, GB_ERR_UNSUPPORTED, "too many partial products");
     // no size cap below the two-adicity (plonk/prover.rs:228-447, field/src/fft.rs:168-205); what does not fit the device is GB_ERR_OOM
@@ -2152,6 +2156,21 @@ gb_status gb_test_arm_perm_arg_failure(gb_circuit* c) try {
     c->test_fail_next_perm_arg = true;
     return GB_OK;
 } GB_CATCH_CIRCUIT(c)
+
+// test hooks (include/goldibear_gpu_test_hooks.h): the dispatch of kernels_gates.hip's short-gate launch on this context, and how
+// often it took the lane-per-point kernel
+gb_status gb_test_force_gate_fallback(gb_ctx* ctx, int on) try {
+    if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null context");
+    ctx->test_force_gate_fallback = on != 0;
+    return GB_OK;
+} GB_CATCH(ctx)
+
+gb_status gb_test_gate_fallback_launches(gb_ctx* ctx, uint64_t* count) try {
+    if (!ctx) return fail(nullptr, GB_ERR_INVALID, "null context");
+    if (!count) return fail(ctx, GB_ERR_INVALID, "null argument");
+    *count = ctx->test_gate_fallback_launches;
+    return GB_OK;
+} GB_CATCH(ctx)
 
 static gb_status stage_guard(gb_circuit* c) {
     if (!c) return fail(nullptr, GB_ERR_INVALID, "null circuit");

@@ -151,6 +151,8 @@ def gadget_records(kind, param, targets):
 # include/goldibear_gpu_test_hooks.h: exports for the test suite, outside the product ABI
 TEST_HOOK_SIGNATURES = {
     "gb_test_arm_perm_arg_failure": (_i32, [_vp]),
+    "gb_test_force_gate_fallback": (_i32, [_vp, C.c_int]),
+    "gb_test_gate_fallback_launches": (_i32, [_vp, C.POINTER(_u64)]),
 }
 
 _lib = None

@@ -36,7 +36,8 @@ def test_test_hooks_live_in_their_own_header():
     hooks = open(os.path.join(ROOT, "include", "goldibear_gpu_test_hooks.h")).read()
     hooks = re.sub(r"/\*.*?\*/", "", hooks, flags=re.S)
     names = set(re.findall(r"\b(gb_[a-z0-9_]+)\s*\(", hooks))
-    assert names == set(native.TEST_HOOK_SIGNATURES) == {"gb_test_arm_perm_arg_failure"}
+    assert names == set(native.TEST_HOOK_SIGNATURES) == {"gb_test_arm_perm_arg_failure", "gb_test_force_gate_fallback",
+                                                         "gb_test_gate_fallback_launches"}
     product = open(os.path.join(ROOT, "include", "goldibear_gpu.h")).read()
     assert "gb_test_" not in product and "GB_PROVE_FAIL_PERM_ARG" not in product
     lib = native.load()
