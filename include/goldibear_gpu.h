@@ -501,6 +501,14 @@ gb_status gb_expand_partition(gb_circuit* c, const void* values, uint32_t flags,
  *   5 INV_OR_ZERO         reg[dst] = a.try_inverse().unwrap_or(ZERO)
  *   6 IS_ZERO             reg[dst] = 1 if a = 0, else 0
  *   7 SQRT                reg[dst] = a square root of a; SQRT(0) = 0; a non-residue is an error (sqrt(x).unwrap() on None)
+ *   16 IDIV               reg[dst] = floor(a / b) of the canonical representatives; b = 0 is the error "attempt to divide by zero"
+ *   17 IREM               reg[dst] = a mod b of the canonical representatives; b = 0 is the same error
+ *   18 SHR                reg[dst] = floor(a / 2^b); 0 when b >= 64 (the amount is a value like any other, not an immediate)
+ *   19 AND                reg[dst] = a & b, bitwise on the canonical representatives
+ *   20 LT                 reg[dst] = 1 if a < b as integers, else 0
+ * The integer operations 16-20 read both operands as integers in [0, p); every result is <= a or is 0 or 1, a field element as
+ * it stands.  With them a generator reads a target as an integer: u32 multiply-add with a carry, a borrow, a comparison,
+ * range-check limbs, div_rem.  OR and XOR can leave [0, p) and are no operations.  8 .. 15 and 21 .. 63 are no opcodes.
  * The unary operations 4-7 have b zero.  With IS_ZERO and INV_OR_ZERO the generators that branch (Equality, NonzeroTest) are
  * written branch-free.  SQRT is Tonelli-Shanks step for step as examples/square_root.rs:185-219 writes it, with
  * z = two_adic_generator(TWO_ADICITY) (the example passes F::bits(), which exceeds the two-adicity).  Nothing in the reference
@@ -579,8 +587,9 @@ gb_status gb_circuit_set_generators(gb_circuit* c, const void* generators, uint6
  * built on the old ones; num_programs = 0 clears them; gb_circuit_set_partition drops them with the schedule.  GB_ERR_INVALID,
  * naming the program and the instruction: a header over the limits or with bits above num_out / num_instrs, a length that does
  * not match the header, more constants than the circuit has, a register read before it is written, a register, dependency,
- * constant or literal index out of range, a literal >= p, a count of OUT other than num_out, an unknown opcode, non-zero bits
- * 60-63, a non-zero b or (for OUT) dst in a unary operation.  Nothing is read past program_offsets[num_programs] words. */
+ * constant or literal index out of range - in either operand of the binary operations 0-2 and 16-20 - a literal >= p, a count of
+ * OUT other than num_out, an unknown opcode (8 .. 15, 21 .. 63), non-zero bits 60-63, a non-zero b or (for OUT) dst in OUT or a
+ * unary operation 4-7.  Nothing is read past program_offsets[num_programs] words. */
 gb_status gb_circuit_set_generator_programs(gb_circuit* c, const uint64_t* program_words, const uint32_t* program_offsets,
                                             uint32_t num_programs);
 /* what the schedule looks like; any out pointer may be NULL */
@@ -596,7 +605,8 @@ gb_status gb_circuit_generator_classes(gb_circuit* c, uint64_t* class_targets_ou
  * >= p ("non-canonical witness element"); two inputs, or an input and a generator, or two generators that set one class to
  * different values ("Partition containing .. was set twice with different values"); a PoseidonGate / Poseidon2BabyBearGate row
  * whose swap wire is not 0 or 1; a RandomAccessGate access index >= 2^bits; a BaseSumGate value that does not fit its limbs; a
- * QuotientGeneratorExtension with a zero denominator ("Tried to invert zero"); a BaseSumGenerator limb that is neither 0 nor 1
+ * QuotientGeneratorExtension with a zero denominator ("Tried to invert zero"); a generator program's IDIV or IREM by zero
+ * ("attempt to divide by zero"); a BaseSumGenerator limb that is neither 0 nor 1
  * (get_bool_target: "not a bool"); a SplitGenerator / WireSplitGenerator value that does not fit its bits ("Integer too large
  * .." - the reference checks this one with debug_assert_eq!, that is in debug builds only; here it is always checked) - the
  * reference's assert!s, with the record index in gb_last_error.  Nothing faults and the circuit stays usable. */

@@ -18,3 +18,4 @@ from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriPar
 from .fri import prove_openings, verify_fri_proof  # noqa: F401
 from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401
 from .generator_program import GeneratorProgram, ProgramGenerator, pack_generator_programs  # noqa: F401
+from .integer_gadgets import div_rem, is_less_than, mul_add_split_gate  # noqa: F401

@@ -81,8 +81,9 @@ enum Error : uint32_t {
     ERR_DIVIDE_BY_ZERO = 5,    // QuotientGeneratorExtension: num / dem with dem == 0 ("Tried to invert zero")
     ERR_NOT_BOOLEAN = 6,       // BaseSumGenerator: get_bool_target, "not a bool"
     ERR_NO_SQUARE_ROOT = 7,    // a generator program's SQRT of a non-residue (examples/square_root.rs: sqrt(x).unwrap() on None)
-    ERR_NO_PROGRAM_TABLES = 8  // a GEN_PROGRAM op met by run_op without its `programs`: the caller's mistake.  Host builds report it;
-                               // for the kernels generator_schedule.hpp device_schedule() refuses such a schedule on the host
+    ERR_NO_PROGRAM_TABLES = 8,  // a GEN_PROGRAM op met by run_op without its `programs`: the caller's mistake.  Host builds report it;
+                                // for the kernels generator_schedule.hpp device_schedule() refuses such a schedule on the host
+    ERR_INTEGER_DIVIDE_BY_ZERO = 9   // a generator program's IDIV or IREM by zero ("attempt to divide by zero")
 };
 constexpr uint32_t ERROR_WORDS = 4;   // code, record, class, 0
 
@@ -94,11 +95,17 @@ struct Launch {
 
 // Generator programs (include/goldibear_gpu.h, "generator programs"): a witness generator as a straight-line program in the
 // word layout of the constraint programs (gates.hpp run_program).  The opcode is (w & 3) | ((w >> 56) & 0xF) << 2: ADD, SUB and
-// MUL as there, OUT in EMIT's place, and the unary operations reg[dst] = op(a) above them.  generator_programs.hpp checks the
-// words; the decoded headers, the instruction words and the literals of all programs lie in three flat tables.
+// MUL as there, OUT in EMIT's place, and the unary operations reg[dst] = op(a) above them.  From 16 on, the integer operations:
+// binary, on the canonical representatives of a and b in [0, p) - quotient, remainder, right shift by a value, bitwise and, less
+// than.  8 .. 15 and everything from GP_NUM_OPCODES on are no opcodes.  generator_programs.hpp checks the words; the decoded
+// headers, the instruction words and the literals of all programs lie in three flat tables.
 enum ProgramOpcode : uint32_t {
-    GP_ADD = 0, GP_SUB = 1, GP_MUL = 2, GP_OUT = 3, GP_INV = 4, GP_INV_OR_ZERO = 5, GP_IS_ZERO = 6, GP_SQRT = 7, GP_NUM_OPCODES = 8
+    GP_ADD = 0, GP_SUB = 1, GP_MUL = 2, GP_OUT = 3, GP_INV = 4, GP_INV_OR_ZERO = 5, GP_IS_ZERO = 6, GP_SQRT = 7,
+    GP_FIELD_END = 8,   // one past the field operations
+    GP_IDIV = 16, GP_IREM = 17, GP_SHR = 18, GP_AND = 19, GP_LT = 20, GP_NUM_OPCODES = 21
 };
+constexpr bool gen_program_is_opcode(uint32_t op) { return op < GP_FIELD_END || (op >= GP_IDIV && op < GP_NUM_OPCODES); }
+constexpr bool gen_program_is_binary(uint32_t op) { return op < GP_OUT || (op >= GP_IDIV && op < GP_NUM_OPCODES); }   // reads operand b
 constexpr uint32_t MAX_GENERATOR_PROGRAMS = 256, MAX_PROGRAM_TARGETS = 1024;
 constexpr uint32_t gen_program_opcode(uint64_t w) { return ((uint32_t)w & 3) | (((uint32_t)(w >> 56) & 0xF) << 2); }
 struct ProgramHeader {

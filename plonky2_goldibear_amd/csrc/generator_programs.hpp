@@ -1,7 +1,8 @@
 // The generator programs of gb_circuit_set_generator_programs (include/goldibear_gpu.h gives the words and the list of what is
 // refused), decoded and checked.  This is the code that reads the untrusted words: every length is checked against the offsets
 // before a word is read, and after it returns gen_program (generators.hpp) needs no check of its own - every register, dependency,
-// constant and literal index is in range, no register is read before it is written and the OUTs number num_out.
+// constant and literal index is in range - of both operands of a binary operation, the integer operations among them - no
+// register is read before it is written and the OUTs number num_out.
 //
 // Host code without HIP or field dependencies (literals stay canonical here; the caller converts them to the device form once):
 // tests/sanitize/generator_programs.cpp compiles it alone with the sanitizers.
@@ -88,9 +89,9 @@ inline bool parse_generator_programs(const uint64_t* words, const uint32_t* offs
             const std::string at = name + " instruction " + std::to_string(pc);
             if (iw >> 60) return refuse(at + ": bits 60-63 are not zero");
             const uint32_t op = gen_program_opcode(iw), dst = ((uint32_t)iw >> 2) & 63;
-            if (op >= GP_NUM_OPCODES) return refuse(at + ": unknown opcode " + std::to_string(op));
+            if (!gen_program_is_opcode(op)) return refuse(at + ": unknown opcode " + std::to_string(op));
             const uint32_t operand[2] = {(uint32_t)(iw >> 8) & 0xFFFFFF, (uint32_t)(iw >> 32) & 0xFFFFFF};
-            const bool unary = op >= GP_OUT;   // OUT and the unary operations read a alone
+            const bool unary = !gen_program_is_binary(op);   // OUT and the unary operations (3 .. 7) read a alone
             if (unary && operand[1] != 0) return refuse(at + ": a second operand in OUT or a unary operation");
             for (uint32_t k = 0; k < (unary ? 1u : 2u); k++) {
                 const uint32_t idx = operand[k] >> 2;

@@ -391,6 +391,33 @@ struct Programs {
     R regs;
 };
 
+// the integer operations GP_IDIV .. GP_LT on the canonical representatives a, b in [0, p) of two device-form values.  Every
+// result is <= a or is 0 or 1, so it is canonical as it stands and F::enc takes it without a reduction.  BabyBear's
+// representatives are below 2^31 and stay in 32-bit words; Goldilocks' 64-bit quotient is the compiler's expansion (gfx950 has no
+// 64-bit divide), the remainder a - q * b.  false: IDIV or IREM by zero, and nothing was divided.
+template <class F>
+GB_HD bool gen_integer_op(u32 opcode, typename F::T x, typename F::T y, typename F::T* res) {
+    typedef typename std::conditional<sizeof(typename F::T) == 4, u32, u64>::type W;
+    const W a = (W)F::dec(x), b = (W)F::dec(y);
+    W r;
+    switch (opcode) {
+        case GP_IDIV:
+        case GP_IREM: {
+            if (b == 0) return false;
+            const W q = a / b;
+            r = opcode == GP_IDIV ? q : a - q * b;
+            break;
+        }
+        // a shift by the word's width or more is no C++ shift: a < 2^(8 sizeof(W)), so the result is 0 from there on (for
+        // BabyBear from 32 on, which holds the 64 of the definition)
+        case GP_SHR: r = b >= 8 * sizeof(W) ? 0 : a >> b; break;
+        case GP_AND: r = a & b; break;
+        default: r = a < b ? 1 : 0; break;   // GP_LT
+    }
+    *res = F::enc((u64)r);
+    return true;
+}
+
 // the interpreter: the operand decode of gates::run_program; space 1 is the dependencies, space 2 the row's constants, OUT ends in
 // io.put, so store-or-compare and OUT_SKIP are those of every other generator.  An error ends the program: its outputs stay as
 // they are and the error word ends the proof.  (A program's error names no class: OUT_SKIP in the class word.)
@@ -415,7 +442,18 @@ GB_HD void gen_program(const Io<F>& io, const Programs<R>& pr) {
         const u64 w = ins[pc];
         const T a = load(gates::prog_operand(w, 0));
         T res = a;
-        switch (gen_program_opcode(w)) {
+        const u32 opcode = gen_program_opcode(w);
+        switch (opcode) {
+            case GP_IDIV:
+            case GP_IREM:
+            case GP_SHR:
+            case GP_AND:
+            case GP_LT:
+                if (!gen_integer_op<F>(opcode, a, load(gates::prog_operand(w, 1)), &res)) {
+                    report(io.err, ERR_INTEGER_DIVIDE_BY_ZERO, io.op.record, OUT_SKIP);
+                    return;
+                }
+                break;
             case GP_ADD: res = F::add(a, load(gates::prog_operand(w, 1))); break;
             case GP_SUB: res = F::sub(a, load(gates::prog_operand(w, 1))); break;
             case GP_MUL: res = F::mul(a, load(gates::prog_operand(w, 1))); break;

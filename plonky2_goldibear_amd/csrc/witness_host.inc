@@ -172,6 +172,8 @@ static gb_status generate_stage(Circuit<F>* c, TmpAlloc& tmp, const void* input_
                 return fail(ctx, GB_ERR_INVALID, rec + "Tried to invert zero (the denominator at target " + target + ")");
             case GN::ERR_NO_SQUARE_ROOT:
                 return fail(ctx, GB_ERR_INVALID, rec + "SQRT of a non-residue in a generator program (called `Option::unwrap()` on a `None` value)");
+            case GN::ERR_INTEGER_DIVIDE_BY_ZERO:
+                return fail(ctx, GB_ERR_INVALID, rec + "attempt to divide by zero (IDIV / IREM in a generator program)");
             case GN::ERR_NOT_BOOLEAN:
                 return fail(ctx, GB_ERR_INVALID, rec + "not a bool (target " + target + ")");
             case GN::ERR_NO_PROGRAM_TABLES:   // the schedule always sets program_regs with a program generator: not reachable from the ABI

@@ -11,6 +11,11 @@ kernels (csrc/generators.hpp gen_program), so that a circuit with such generator
     gate = ProgramGate("MulAddThreeGate", constraints, generators=lambda row, consts: [
         ProgramGenerator("MulAddThreeGenerator", prog, [wire(row, 0), wire(row, 1)], [wire(row, 2)], row=row)])
 
+A generator that reads a target as an integer - a u32 multiply-add's low and high halves, a borrow, a comparison, range-check
+limbs, div_rem - uses the integer operations ops.idiv / irem / shr / and_ / lt (opcodes 16 .. 20, on the canonical
+representatives; integer_gadgets.py builds gates and gadgets on them), and ops.ext spells extension arithmetic out in base
+operations.
+
 `from_function` traces the callable on the DAG of gate_program.py (hash-consed, registers allocated by last use); `evaluate`
 runs the packed words on Python integers, and is what ProgramGenerator.run calls: the host path prove(pw) and the device path
 prove_inputs(pw) share one definition.  Not the GPU hot path.
@@ -23,8 +28,11 @@ from .gate_program import (HEADER_WORDS, MAX_INSTRS, MAX_LITERALS, MAX_REGS, SPA
 
 MAX_GENERATOR_PROGRAMS, MAX_TARGETS = 256, 1024
 OP_ADD, OP_SUB, OP_MUL, OP_OUT, OP_INV, OP_INV_OR_ZERO, OP_IS_ZERO, OP_SQRT = range(8)
+OP_IDIV, OP_IREM, OP_SHR, OP_AND, OP_LT = range(16, 21)   # on the canonical representatives, as integers; 8 .. 15 are no opcodes
 SPACE_DEP = SPACE_WIRE   # space 1 indexes the dependencies
-_BINARY = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}
+_INTEGER = {"idiv": OP_IDIV, "irem": OP_IREM, "shr": OP_SHR, "and": OP_AND, "lt": OP_LT}
+_BINARY = dict({"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}, **_INTEGER)
+EXT_W = {N.GB_GOLDILOCKS: (2, 7), N.GB_BABYBEAR: (4, 11)}   # the extension x^D - W: (D, W)
 _UNARY = {"inv": OP_INV, "inv_or_zero": OP_INV_OR_ZERO, "is_zero": OP_IS_ZERO, "sqrt": OP_SQRT}
 TWO_ADICITY = {N.GB_GOLDILOCKS: 32, N.GB_BABYBEAR: 27}
 TWO_ADIC_GENERATOR = {N.GB_GOLDILOCKS: 1753635133440165772, N.GB_BABYBEAR: 0x1a427a41}   # csrc/gl_field.hpp, csrc/bb_field.hpp
@@ -36,6 +44,21 @@ class InvertZeroError(ArithmeticError):
 
 class NoSquareRootError(ArithmeticError):
     """SQRT of a non-residue: examples/square_root.rs sqrt(x).unwrap() on None"""
+
+
+class IntegerDivideByZeroError(ArithmeticError):
+    """IDIV or IREM by zero: Rust's panic, "attempt to divide by zero\""""
+
+
+def integer_op(op, a, b):
+    """IDIV / IREM / SHR / AND / LT on two canonical representatives; every result is <= a or 0 or 1, so canonical"""
+    if op in (OP_IDIV, OP_IREM):
+        if b == 0:
+            raise IntegerDivideByZeroError("attempt to divide by zero (IDIV / IREM in a generator program)")
+        return a // b if op == OP_IDIV else a % b
+    if op == OP_SHR:
+        return 0 if b >= 64 else a >> b
+    return a & b if op == OP_AND else int(a < b)
 
 
 def encode_opcode(op):
@@ -76,11 +99,120 @@ def field_sqrt(x, field):
     return x
 
 
-class _Ops:
-    """the unary operations of a generator program, on the expressions of one trace"""
+class Ext:
+    """An extension element over x^D - W as its D coordinate expressions (`coords`), spelled out in base operations: + - *,
+    scaling by a base expression or integer, inv() and /.  The inverse goes through the norm down to the base field - one INV,
+    which raises on zero what INV raises."""
 
-    def __init__(self, dag):
-        self._dag = dag
+    def __init__(self, ops, coords):
+        self._ops, self.coords = ops, [ops._dag.coerce(c) for c in coords]
+        if len(self.coords) != ops.ext_degree:
+            raise ValueError("%d coordinates for an extension of degree %d" % (len(self.coords), ops.ext_degree))
+
+    def _same(self, o):
+        return isinstance(o, Ext) and o._ops is self._ops
+
+    def _new(self, coords):
+        return Ext(self._ops, coords)
+
+    def _lift(self, o):
+        return o if self._same(o) else self._new([o] + [0] * (len(self.coords) - 1))
+
+    def __add__(self, o):
+        return self._new([a + b for a, b in zip(self.coords, self._lift(o).coords)])
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        return self._new([a - b for a, b in zip(self.coords, self._lift(o).coords)])
+
+    def __rsub__(self, o):
+        return self._lift(o) - self
+
+    def __neg__(self):
+        return self._new([0 - a for a in self.coords])
+
+    def __mul__(self, o):
+        if not self._same(o):   # a base expression or an integer scales
+            return self._new([a * o for a in self.coords])
+        d, w = len(self.coords), self._ops.ext_w
+        out = [0] * d
+        for i, a in enumerate(self.coords):
+            for j, b in enumerate(o.coords):
+                out[(i + j) % d] = out[(i + j) % d] + (a * b if i + j < d else a * b * w)
+        return self._new(out)
+
+    __rmul__ = __mul__
+
+    def inv(self):
+        w, c = self._ops.ext_w, self.coords
+        if len(c) == 2:      # (a0 + a1 x)(a0 - a1 x) = a0^2 - W a1^2
+            conj, norm = [c[0], 0 - c[1]], c[0] * c[0] - c[1] * c[1] * w
+        else:                # a = A + B x over y = x^2, y^2 = W: a (A - B x) = A^2 - y B^2 = n0 + n1 y, whose norm is n0^2 - W n1^2
+            n0 = c[0] * c[0] + c[2] * c[2] * w - 2 * w * (c[1] * c[3])
+            n1 = 2 * (c[0] * c[2]) - c[1] * c[1] - c[3] * c[3] * w
+            half = self._new([c[0], 0 - c[1], c[2], 0 - c[3]]) * self._new([n0, 0, 0 - n1, 0])
+            conj, norm = half.coords, n0 * n0 - n1 * n1 * w
+        ninv = self._ops.inv(norm)
+        return self._new([x * ninv for x in conj])
+
+    def __truediv__(self, o):
+        return self * self._lift(o).inv()
+
+    def __rtruediv__(self, o):
+        return self._lift(o) * self.inv()
+
+
+class _Ops:
+    """the operations of a generator program beyond + - *, on the expressions of one trace: the unary field operations, the
+    binary integer operations (no folding: two integer arguments become two literals) and what is spelled out in those"""
+
+    def __init__(self, dag, field=None):
+        self._dag, self.field = dag, field
+        self.ext_degree, self.ext_w = EXT_W.get(field, (0, 0))
+
+    def _integer(self, kind, x, y):
+        return self._dag.node((kind, self._dag.coerce(x).i, self._dag.coerce(y).i))
+
+    def idiv(self, x, y):
+        """floor(x / y) of the canonical representatives; y = 0 is an error"""
+        return self._integer("idiv", x, y)
+
+    def irem(self, x, y):
+        """x mod y of the canonical representatives; y = 0 is an error"""
+        return self._integer("irem", x, y)
+
+    def shr(self, x, amount):
+        """floor(x / 2^amount); the amount is a value like any other, 0 from 64 on"""
+        return self._integer("shr", x, amount)
+
+    def and_(self, x, y):
+        return self._integer("and", x, y)
+
+    def lt(self, x, y):
+        """1 if x < y as integers, else 0"""
+        return self._integer("lt", x, y)
+
+    def low_bits(self, x, n):
+        """x mod 2^n (n an integer with 2^n - 1 below the field's order)"""
+        if not 0 <= n or (1 << n) - 1 >= self._dag.p:
+            raise ValueError("2^%d - 1 is no field element" % n)
+        return self.and_(x, (1 << n) - 1)
+
+    def bit(self, x, i):
+        return self.and_(x if isinstance(i, int) and i == 0 else self.shr(x, i), 1)
+
+    def bits(self, x, n):
+        """the n low bits of x, least significant first"""
+        return [self.bit(x, i) for i in range(n)]
+
+    def select(self, c, x, y):
+        """x where c is 1, y where c is 0"""
+        return c * (x - y) + y
+
+    def ext(self, coords):
+        """D expressions as one extension element (Ext)"""
+        return Ext(self, coords)
 
     def _unary(self, kind, x):
         return self._dag.node((kind, self._dag.coerce(x).i))
@@ -120,11 +252,12 @@ class GeneratorProgram:
     @classmethod
     def from_function(cls, fn, num_in, num_out, num_constants, field):
         """fn(deps, consts, ops) -> the num_out outputs in order, built from deps[i], consts[i] and integers with + - * and
-        ops.inv / ops.inv_or_zero / ops.is_zero / ops.sqrt"""
+        ops.inv / ops.inv_or_zero / ops.is_zero / ops.sqrt, the integer operations ops.idiv / ops.irem / ops.shr / ops.and_ /
+        ops.lt with ops.low_bits / ops.bit / ops.bits / ops.select built from them, and ops.ext"""
         if num_in + num_out > MAX_TARGETS:
             raise ValueError("%d dependencies and %d outputs, together at most %d" % (num_in, num_out, MAX_TARGETS))
         dag = _Dag(field_order(field))
-        outs = [dag.coerce(e) for e in fn(_Column(dag, "w", num_in), _Column(dag, "c", num_constants), _Ops(dag))]
+        outs = [dag.coerce(e) for e in fn(_Column(dag, "w", num_in), _Column(dag, "c", num_constants), _Ops(dag, field))]
         if len(outs) != num_out:
             raise ValueError("the function returned %d outputs, not %d" % (len(outs), num_out))
         nodes = dag.nodes
@@ -214,6 +347,8 @@ class GeneratorProgram:
             elif op in (OP_ADD, OP_SUB, OP_MUL):
                 b = load((word >> 32) & 0xFFFFFF)
                 regs[dst] = (a + b) % p if op == OP_ADD else (a - b) % p if op == OP_SUB else a * b % p
+            elif op in _INTEGER.values():
+                regs[dst] = integer_op(op, a, load((word >> 32) & 0xFFFFFF))
             elif op == OP_INV:
                 if a == 0:
                     raise InvertZeroError("Tried to invert zero")
