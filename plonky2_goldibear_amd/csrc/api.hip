@@ -433,7 +433,7 @@ gb_status tables_for(gb_ctx* ctx, u32 log_n, const typename TableCache<F>::Table
         for (u32 j = 0; j < 256; j++) top[j] = F::pow(w, (u64)bitrev32(j, 8) << (log_m - 8));
         if ((s = upload(ctx, top, &set.t.tw_top_fwd, set.owned))) return s;
     }
-    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins of kernels_ntt16.hip
+    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins the register-radix passes read (inv16_tables, lde_tables)
         set.t.tw4096_fwd_m = tc.tw4096_fwd_m;
         set.t.tw4096_inv_m = tc.tw4096_inv_m;
         if ((s = upload(ctx, times_r(vlo_f), &set.t.tw_lo_fwd_m, set.owned))) return s;
@@ -519,7 +519,7 @@ gb_status cosets_for(gb_ctx* ctx, u32 log_n, u32 rate_bits, typename F::T shift,
             if ((s = cosets_for<F>(ctx, 20, rate_bits + 2, shift, false, &set.t.fine, tmp))) return s;
     if ((s = upload(ctx, lo, &set.t.pow_lo, set.owned, pooled))) return s;
     if ((s = upload(ctx, hi, &set.t.pow_hi, set.owned, pooled))) return s;
-    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins of kernels_ntt16.hip
+    if constexpr (is_goldilocks<F>) {   // Goldilocks: the Montgomery twins the register-radix passes read (inv16_tables, lde_tables)
         if ((s = upload(ctx, times_r(lo), &set.t.pow_lo_m, set.owned, pooled))) return s;
         if ((s = upload(ctx, times_r(hi), &set.t.pow_hi_m, set.owned, pooled))) return s;
     }

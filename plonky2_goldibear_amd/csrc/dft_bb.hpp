@@ -128,6 +128,8 @@ struct Dft<BbF> {
     static __device__ __forceinline__ void dft_small(u32 (&x)[16]) { gbk::dft_small<INV, K>(x); }
     template <bool INV, int H, int O>
     static __device__ __forceinline__ void layer64(u32* x) { gbk::layer64<INV, H, O>(x); }
+    template <bool INV>
+    static __device__ __forceinline__ void dft32(u32 (&x)[32]) { gbk::dft32<INV>(x); }
 };
 
 }  // namespace gbk

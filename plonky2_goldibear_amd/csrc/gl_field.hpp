@@ -171,7 +171,7 @@ __device__ __forceinline__ u64 fold160(u32 r0, u32 r1, u32 hl, u32 hh, u32 r4) {
 //   register pair that is already in place - and the one carry that sum can produce (weight 2^96) comes out in the mad's scalar carry
 //   operand and enters the top limb through a v_addc: 4 mads + 3 plain.
 // FIVE = true (rounds 2-3): four mads for the partial products and a fifth as an ADDER - the second carry word enters the top
-//   product as x * 1 + acc.  The strided LDE pass (k_gl_lde_pa16x2, k_gl_lde_pa32) measured 3 % faster with this form: its
+//   product as x * 1 + acc.  The strided LDE pass (k_lde_pa16x2<GlF>, k_lde_pa32<GlF, K>: LdeTune<GlF>::mulc_big) measured 3 % faster with this form: its
 //   140-register body loses more to the extra scalar carry pair than it gains from the mad.
 template <bool FIVE = false>
 __host__ __device__ __forceinline__ void mul_limbs(u64 a, u64 b, u32& r0, u32& r1, u32& hl, u32& hh) {

@@ -29,7 +29,7 @@ struct GlNttTables {
     const u64* tw_lo_inv;    // same for w_n^-1
     const u64* tw_hi_inv;
     u64 n_inv;               // n^-1 mod p
-    // the same tables times R = 2^64 mod p (Montgomery form) for the register-radix kernels of kernels_ntt16.hip, whose
+    // the same tables times R = 2^64 mod p (Montgomery form) for the register-radix passes (ntt_passes.hpp, lde_passes.hpp, kernels_ntt16.hip), whose
     // multiplications by table values then end in the 7-instruction Montgomery fold (gl::mul_mont: mont_fold_flags) instead of fold128's 11;
     // tw4096_fwd_m is [8192]: the powers, then the same powers in k_gl_lde_pb16's stage-1 order [slot][tid]
     const u64 *tw4096_fwd_m, *tw4096_inv_m, *tw_lo_fwd_m, *tw_hi_fwd_m, *tw_lo_inv_m, *tw_hi_inv_m;
@@ -53,7 +53,7 @@ struct GlCosetTables {
     u32 rate_bits;
     const u64* pow_lo;  // [2^r][min(n,4096)]
     const u64* pow_hi;  // [2^r][max(1, n/4096)]
-    const u64 *pow_lo_m, *pow_hi_m;  // the same times R (Montgomery form), for kernels_ntt16.hip's LDE passes
+    const u64 *pow_lo_m, *pow_hi_m;  // the same times R (Montgomery form), for the strided LDE passes (lde_passes.hpp)
     // log_n > 22 (ntt_outer.hpp): the coset tables of the sub-transforms (shift^R) and the context's work buffer of this level - the
     // ADDRESS of the context's pointer / size, read at the call: the block moves when it grows
     const GlCosetTables* sub;
@@ -86,7 +86,7 @@ using NttTables = std::conditional_t<std::is_same<F, GlF>::value, GlNttTables, B
 template <class F>
 using CosetTables = std::conditional_t<std::is_same<F, GlF>::value, GlCosetTables, BbCosetTables>;
 
-// ---------------------------------------------------------------- NTT / LDE (ntt_passes.hpp; instantiated in kernels_ntt16.hip, kernels_bb16.hip)
+// ---------------------------------------------------------------- NTT / LDE (ntt_passes.hpp, lde_passes.hpp; instantiated in kernels_ntt16.hip, kernels_bb16.hip)
 // Templated on the field traits; element pointers are in the field's device form.
 
 // Columns per group of the inverse transform's passes from 2^18 rows up, in 8-byte words (BabyBear: twice as many columns): the

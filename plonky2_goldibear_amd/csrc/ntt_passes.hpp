@@ -1,6 +1,7 @@
 // The NTT passes and their dispatch, written once against the field traits (GlF: canonical u64 words; BbF: 32-bit Montgomery words).
-// Included by kernels_ntt16.hip and kernels_bb16.hip, which define what stays per field - the register DFTs (Dft<F>, below) and the
-// LDE radix-16 passes with their dispatchers lde_pa_r16 / lde_pb_r16 - and instantiate the templates declared in kernels.hpp.
+// Included by kernels_ntt16.hip and kernels_bb16.hip, which define what stays per field - the register DFTs (Dft<F>, below), the
+// LDE's contiguous pass (lde_pb_r16) and its strided pass of 2^22 rows - and instantiate the templates declared in kernels.hpp.
+// The LDE's strided passes and their dispatcher lde_pa_r16 are in lde_passes.hpp.
 //
 // Data stays column-major [col][n]; every pass moves tiles HBM -> LDS / registers -> HBM with >= 64-byte contiguous row segments.
 //  inverse (values -> coefficients, natural -> natural), n = 2^L:
@@ -12,7 +13,7 @@
 //                        P1 (8 bits strided), P2 (LB bits, none at 2^16 rows), P3 (8 bits, transposed write)
 //  LDE (coefficients -> leaf-order evaluations on the 2^r cosets 7 w_N^bitrev(c) H_n):
 //     L <= 12:         one LDS tile per (column, coset) (k_lde_pb)
-//     12 < L <= 22:    per field: PA (L - 12 bits strided, per-coset loop), PB (12 bits contiguous, natural -> leaf order)
+//     12 < L <= 22:    PA (L - 12 bits strided, per-coset loop; lde_passes.hpp), PB (12 bits contiguous, natural -> leaf order; per field)
 //  L > 22: one outer radix step (ntt_outer.hpp) around transforms of 2^22 rows and fewer.
 #pragma once
 #include <algorithm>
@@ -26,8 +27,9 @@ static constexpr int THREADS = 256;
 static constexpr int TILE = 4096;
 
 // Per field (kernels_ntt16.hip, kernels_bb16.hip): the in-register DFTs of the radix-16 passes, natural input order, X[k] in slot
-// brev(k) - static members template <bool INV> dft16(T (&)[16]), template <bool INV, int K> dft_small(T (&)[16]) (2^K points, K = 1..3)
-// and template <bool INV, int H, int O> layer64(T*) (one DIF layer of half-size H on x[O .. O + 2H), twiddles w_64^(+-j)).
+// brev(k) - static members template <bool INV> dft16(T (&)[16]), template <bool INV, int K> dft_small(T (&)[16]) (2^K points, K = 1..3),
+// template <bool INV> dft32(T (&)[32]) and template <bool INV, int H, int O> layer64(T*) (one DIF layer of half-size H on
+// x[O .. O + 2H), twiddles w_64^(+-j)).
 template <class F>
 struct Dft;
 
@@ -392,10 +394,11 @@ __global__ __launch_bounds__(256) void k_reduce_words(typename F::T* __restrict_
 
 static inline u32 nblk(size_t n, u32 bs) { return (u32)((n + bs - 1) / bs); }
 
-// per field (kernels_ntt16.hip, kernels_bb16.hip): the LDE's strided pass for 12 < log_n <= 22, and its contiguous pass over
-// `ntiles` 4096-point tiles of `lde`, in place
-void lde_pa_r16(const u64* coeffs, u64* lde, size_t ncols, const GlNttTables& t, const GlCosetTables& ct, hipStream_t stream);
-void lde_pa_r16(const u32* coeffs, u32* lde, size_t ncols, const BbNttTables& t, const BbCosetTables& ct, hipStream_t stream);
+// the LDE's strided pass for 12 < log_n <= 22 (lde_passes.hpp)
+template <class F>
+void lde_pa_r16(const typename F::T* coeffs, typename F::T* lde, size_t ncols, const NttTables<F>& t, const CosetTables<F>& ct,
+                hipStream_t stream);
+// per field (kernels_ntt16.hip, kernels_bb16.hip): its contiguous pass over `ntiles` 4096-point tiles of `lde`, in place
 void lde_pb_r16(u64* lde, size_t ntiles, const GlNttTables& t, hipStream_t stream);
 void lde_pb_r16(u32* lde, size_t ntiles, const BbNttTables& t, hipStream_t stream);
 
@@ -491,7 +494,7 @@ void lde_columns(const typename F::T* coeffs, typename F::T* lde, size_t ncols, 
     }
     // both passes over all columns per launch: they are bound by VALU issue, not by HBM (column groups sized for the Infinity Cache
     // measured slower in every setting, HISTORY.md round 3)
-    lde_pa_r16(coeffs, lde, ncols, t, ct, stream);
+    lde_pa_r16<F>(coeffs, lde, ncols, t, ct, stream);
     lde_pb_r16(lde, ncols << (r + L - 12), t, stream);
 }
 

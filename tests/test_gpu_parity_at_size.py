@@ -9,7 +9,7 @@
   2^21 rows.
 * PolynomialBatch::from_values (fri/oracle.rs:68-123) at n = 2^20, N = 2^23: EVERY coefficient, EVERY leaf of every
   column, EVERY digest and the cap against the oracle's batch - this is the only size that runs the 2^20-row NTT kernels
-  (k_gl_lde_pa16x2 / k_bb_lde_pa16x2), so a sampled check is not enough there.
+  (k_lde_pa16x2<F>), so a sampled check is not enough there.
 The oracle needs about a minute per 2^20-row proof on the GPU box's 16 host cores."""
 import numpy as np
 import pytest
@@ -43,9 +43,9 @@ def _gpu_circuit(ctx, circ, tag):
 
 
 @pytest.mark.parametrize("field_name,degree_bits,num_challenges", [
-    ("goldilocks", 14, 2), ("babybear", 15, 7),      # 2^14 / 2^15 rows: k_*_lde_pa_small<K>, the LDS radix-2 inverse transform
+    ("goldilocks", 14, 2), ("babybear", 15, 7),      # 2^14 / 2^15 rows: k_lde_pa_small<F, K>, the LDS radix-2 inverse transform
     ("goldilocks", 16, 3), ("babybear", 16, 7),
-    ("goldilocks", 17, 3), ("babybear", 17, 8),      # 2^17 / 2^19 rows: the mixed radix-2/4/8 middle passes, k_*_lde_pa16xs<K>
+    ("goldilocks", 17, 3), ("babybear", 17, 8),      # 2^17 / 2^19 rows: the mixed radix-2/4/8 middle passes, k_lde_pa16xs<F, K>
     ("goldilocks", 18, 3), ("babybear", 19, 9),      # (2^18 BabyBear and 2^19 Goldilocks: the same kernels; from_values parity in test_gpu_parity.py)
 ])
 def test_proof_bytes_match_oracle_at_size(ctx, field_name, degree_bits, num_challenges):
@@ -119,7 +119,7 @@ def test_full_batch_2pow20_every_leaf_and_digest(ctx, field_name):
 
 @pytest.mark.parametrize("field_name,rate_bits", [("goldilocks", 1), ("goldilocks", 2), ("babybear", 1), ("babybear", 2)])
 def test_2pow20_rows_at_other_rates(ctx, field_name, rate_bits):
-    """The 2^20-row passes (k_*_lde_pa16x2's coset loop, pb16, the 16-column inverse-transform groups) at rate_bits 1 and 2 - every
+    """The 2^20-row passes (k_lde_pa16x2<F>'s coset loop, pb16, the 16-column inverse-transform groups) at rate_bits 1 and 2 - every
     stock configuration uses 3, so nothing else runs them with fewer cosets: 3 columns, the whole batch against the
     oracle.  Also the place where a non-canonical word stored by the twiddle chains (mul_mont on a lazy operand) would show."""
     log_n, ncols = 20, 3

@@ -1,5 +1,5 @@
 """The case table of tests/test_gpu_transform_dispatch.py against the sources: every transform launch site of ntt_passes.hpp,
-kernels_ntt16.hip, kernels_bb16.hip and ntt_outer.hpp (hipLaunchKernelGGL's kernel with its literal template arguments, GB_PAS(KK)
+lde_passes.hpp, kernels_ntt16.hip, kernels_bb16.hip and ntt_outer.hpp (hipLaunchKernelGGL's kernel with its literal template arguments, GB_PAS(KK)
 expanded by its call sites) is named by a case of tests/transform_cases.py or sits in its allow-list - a new launch site without a
 case fails here.  And the GPU test's reference helper (leaves = bit-reversed coset_fft of the padded coefficients) against the
 oracle's own PolynomialBatch.from_coeffs, so that the large comparisons rest on a layout that has itself been checked.  CPU only."""
@@ -13,7 +13,7 @@ import transform_cases as T
 from oracle.fields import BB, GL
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "plonky2_goldibear_amd", "csrc")
-SOURCES = ("ntt_passes.hpp", "kernels_ntt16.hip", "kernels_bb16.hip", "ntt_outer.hpp")
+SOURCES = ("ntt_passes.hpp", "lde_passes.hpp", "kernels_ntt16.hip", "kernels_bb16.hip", "ntt_outer.hpp")
 
 
 def _kernel_arg(text, i):
@@ -70,8 +70,13 @@ def source_sites():
 
 
 def _field_of(site):
-    """the field a launch site runs in: k_gl_* / k_bb_* one, the templates over F both"""
-    return {T.GL} if site.startswith("k_gl_") else {T.BB} if site.startswith("k_bb_") else {T.GL, T.BB}
+    """the field a launch site runs in: k_gl_* / k_bb_* and the templates written with GlF / BbF one, the templates over F both"""
+    args = re.findall(r"\b(GlF|BbF)\b", site)
+    if site.startswith("k_gl_") or "GlF" in args:
+        return {T.GL}
+    if site.startswith("k_bb_") or "BbF" in args:
+        return {T.BB}
+    return {T.GL, T.BB}
 
 
 def test_every_launch_site_has_a_case():
@@ -89,15 +94,17 @@ def test_every_launch_site_has_a_case():
 
 
 def test_extraction_finds_the_known_shapes():
-    """the extractor itself: GB_PAS expanded for 2^17 .. 2^19 rows in both fields, the outer step's launch switches for K = 1 .. 4"""
+    """the extractor itself: GB_PAS expanded for 2^17 .. 2^19 rows, the outer step's launch switches for K = 1 .. 4, the field of a
+    site that names one in its template arguments"""
     src = source_sites()
-    for f in ("gl", "bb"):
-        for kk in (1, 2, 3):
-            assert "k_%s_lde_pa16xs<%d>" % (f, kk) in src
+    for kk in (1, 2, 3):
+        assert "k_lde_pa16xs<F, %d>" % kk in src
     for k in ("k_deinterleave", "k_intt_combine", "k_lde_combine"):
         for K in range(1, T.OUTER_MAX_BITS + 1):
             assert "%s<F, %d>" % (k, K) in src
-    assert "k_intt16_p1<F, WB>" in src and "k_bb_lde_pa16x2w<2>" in src
+    assert "k_intt16_p1<F, WB>" in src and "k_bb_lde_pa16x2w" in src
+    assert _field_of("k_lde_pa32<GlF, 2>") == {T.GL} and _field_of("k_lde_pa32<F, 1>") == {T.GL, T.BB}
+    assert _field_of("k_bb_lde_pa16x2w") == {T.BB} and "k_lde_pa32<GlF, 2>" in src
     assert len(src) == len(set(src))
     assert not [s for s in src if "KK" in s or "hipLaunch" in s]
 

@@ -1,5 +1,5 @@
 """The cases of tests/test_gpu_transform_dispatch.py: one row per commitment, with the transform launch sites it reaches (written as
-in csrc/ntt_passes.hpp, kernels_ntt16.hip, kernels_bb16.hip and ntt_outer.hpp) and why it is there.  tests/test_transform_dispatch_table.py
+in csrc/ntt_passes.hpp, lde_passes.hpp, kernels_ntt16.hip, kernels_bb16.hip and ntt_outer.hpp) and why it is there.  tests/test_transform_dispatch_table.py
 extracts the launch sites from those sources and fails when one of them is named by no case (or by the allow-list below).
 
 Plain data plus the reference helper both tests use (lde_leaves_ref: the CPU oracle's transforms, no GPU code).
@@ -35,13 +35,13 @@ _INV = {   # intt_group / intt_columns_r16 (ntt_passes.hpp), both fields
     21: ("k_intt16_p1<F, WB>", "k_intt16_p2w<F, 5>", "k_intt16_p3<F>"),
     22: ("k_intt16_p1<F, WB>", "k_intt16_p2w<F, 6>", "k_intt16_p3<F>"),
 }
-_PA = {   # lde_pa_r16 (kernels_ntt16.hip / kernels_bb16.hip), then lde_pb_r16
-    GL: {13: "k_gl_lde_pa_small<1>", 14: "k_gl_lde_pa_small<2>", 15: "k_gl_lde_pa_small<3>", 16: "k_gl_lde_pa16x1",
-         17: "k_gl_lde_pa16xs<1>", 18: "k_gl_lde_pa16xs<2>", 19: "k_gl_lde_pa16xs<3>", 20: "k_gl_lde_pa16x2",
-         21: "k_gl_lde_pa32<1>", 22: "k_gl_lde_pa32<2>"},
-    BB: {13: "k_bb_lde_pa_small<1>", 14: "k_bb_lde_pa_small<2>", 15: "k_bb_lde_pa_small<3>", 16: "k_bb_lde_pa16x1",
-         17: "k_bb_lde_pa16xs<1>", 18: "k_bb_lde_pa16xs<2>", 19: "k_bb_lde_pa16xs<3>", 20: "k_bb_lde_pa16x2<32>",
-         21: "k_bb_lde_pa32<1>", 22: "k_bb_lde_pa16x2w<2>"},
+_PA_F = {   # lde_pa_r16 (lde_passes.hpp), both fields; then lde_pb_r16
+    13: "k_lde_pa_small<F, 1>", 14: "k_lde_pa_small<F, 2>", 15: "k_lde_pa_small<F, 3>", 16: "k_lde_pa_small<F, 4>",
+    17: "k_lde_pa16xs<F, 1>", 18: "k_lde_pa16xs<F, 2>", 19: "k_lde_pa16xs<F, 3>", 20: "k_lde_pa16x2<F>", 21: "k_lde_pa32<F, 1>",
+}
+_PA = {   # 2^22 rows: lde_pa_rows22, per field (kernels_ntt16.hip / kernels_bb16.hip)
+    GL: {**_PA_F, 22: "k_lde_pa32<GlF, 2>"},
+    BB: {**_PA_F, 22: "k_bb_lde_pa16x2w"},
 }
 _PB = {GL: "k_gl_lde_pb16", BB: "k_bb_lde_pb16"}
 NATIVE_LOG, OUTER_MAX_BITS = 22, 4   # kernels.hpp: NTT_NATIVE_LOG, NTT_OUTER_MAX_BITS
@@ -100,7 +100,7 @@ for _lg, (_rg, _rb) in sorted(_RATES.items()):
         _add("%s-coeffs-2^%d-r%d" % (_f, _lg, _r), _f, _lg, _r, _nc1, "coeffs", "rate", lde_sites(_f, _lg),
              "rate %d: %d cosets of pow_lo / pow_hi" % (_r, 1 << _r))
 _add("babybear-coeffs-2^22-r5", BB, 22, 5, 1, "coeffs", "sampled", lde_sites(BB, 22),
-     "BabyBear's two-adicity edge (2^27 points); k_bb_lde_pa16x2w<2> reads the 2^20-row cosets of rate 7")
+     "BabyBear's two-adicity edge (2^27 points); k_bb_lde_pa16x2w reads the 2^20-row cosets of rate 7")
 
 # ---- from_values below the outer step: the inverse passes of every size class not reached by the group cases
 _add("goldilocks-values-2^13-r1-host", GL, 13, 1, 2, "host", "values", values_sites(GL, 13), "LDS radix-2 inverse passes")
