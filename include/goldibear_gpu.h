@@ -939,6 +939,54 @@ gb_status gb_fri_verify(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, uint3
                         const void* initial_caps, const uint32_t* reduction_arity_bits, uint32_t num_layers,
                         uint32_t proof_of_work_bits, uint32_t num_query_rounds, const gb_challenger_state* challenger,
                         const void* fri_proof, size_t fri_proof_len);
+/* gb_fri_verify of `num_items` proofs that share ONE instance shape, the query rounds - every Merkle path, fri_combine_initial and
+ * the folding checks - on the device of `ctx`, as gb_verify_batch runs them for the proofs of one PLONK circuit.  The shape is the
+ * field, degree_bits, rate_bits, cap_height, hiding, oracle_num_polys, oracle_blinding, batch_sizes, polynomials,
+ * reduction_arity_bits, proof_of_work_bits and num_query_rounds: the same flat arrays with the same meaning as gb_fri_verify.
+ * Proofs of several shapes: group them by shape, one call per group.  Per item i, tables of HOST pointers / arrays:
+ *   points[i]        [num_batches][D]          every proof has its own zeta
+ *   openings[i]      [sum of batch_sizes][D]
+ *   initial_caps[i]  [num_oracles][2^cap_height][H]; the pointers may alias (a cap all items share is passed once)
+ *   challengers[i]   the transcript after the openings were observed, by value: never advanced
+ *   fri_proofs[i], fri_proof_lens[i]           FriProof bytes
+ *   flags   0 (anything else: GB_ERR_INVALID);  results: gb_verify_result[num_items], host
+ * For every i, results[i].status is what gb_fri_verify returns for that item alone and gb_verify_check_text(results[i].check) the
+ * text it leaves in gb_last_error for the checks that have a GB_VCHECK_ code (truncated, trailing, the two path lengths, the proof
+ * of work, initial path, consistency, layer path, final polynomial); a word >= p in the item's points, openings, caps or proof
+ * bytes is GB_ERR_INVALID with GB_VCHECK_NON_CANONICAL, a challenger state gb_fri_verify refuses GB_ERR_INVALID with check 0.
+ * query_round and index follow gb_verify_batch (oracle index for initial paths, layer index for consistency and layer paths, else
+ * UINT32_MAX); of several failing checks the one gb_fri_verify reaches first is named.
+ * Returns GB_OK: every item verified; GB_ERR_VERIFY: the call completed and at least one item did not verify (GB_ERR_INVALID items
+ * included); anything else: the call did not complete and results is unspecified.  num_items == 0: GB_OK.  An error of the shared
+ * shape is no verdict: it fails the call with gb_fri_verify's status and message; a NULL table or a NULL entry is GB_ERR_INVALID.
+ * The host stage (on the context's "copy_threads", in gb_fri_verify's order) checks the item's words, parses the proof, replays the
+ * transcript, reduces the openings and checks the proof of work; an item whose length or whose path-length bytes are not the
+ * shape's is walked on the host, every other item's query section is uploaded as it stands with a record of its challenges and
+ * caps - no device offset is derived from proof content.  Chunks, the two staging slots and "verify_chunk_bytes" are
+ * gb_verify_batch's.  Limits of the device path (a shape beyond them is no error: every item is walked on the host, over the copy
+ * threads, with the same results): GB_FRI_VERIFY_BATCH_MAX_ORACLES oracles, GB_FRI_VERIFY_BATCH_MAX_BATCHES batches,
+ * GB_FRI_VERIFY_BATCH_MAX_POLYNOMIALS entries of `polynomials`, GB_MAX_FRI_LAYERS layers, GB_MAX_FRI_QUERY_ROUNDS query rounds,
+ * num_oracles + 2 * num_layers + 1 < 2^16, and a proof's query section and its record together at most
+ * GB_FRI_VERIFY_BATCH_MAX_ITEM_BYTES (64 MiB: a page-locked staging slot holds at least one item, whatever "verify_chunk_bytes" says).
+ * ctx NULL is GB_ERR_INVALID; where the other arguments are in order the host stage has still run, on the calling thread and
+ * touching no device, and results holds its verdicts - GB_ERR_INVALID with check 0 for every item that only a device could decide.
+ * Timing scopes: "fri verify batch: host stage", "fri verify batch: upload", "fri verify batch: paths", "fri verify batch: queries". */
+#define GB_FRI_VERIFY_BATCH_MAX_ORACLES 64
+#define GB_FRI_VERIFY_BATCH_MAX_BATCHES 64
+#define GB_FRI_VERIFY_BATCH_MAX_POLYNOMIALS 65536
+#define GB_FRI_VERIFY_BATCH_MAX_ITEM_BYTES 67108864
+gb_status gb_fri_verify_batch(gb_ctx* ctx, uint32_t field, uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t hiding,
+                              const uint32_t* oracle_num_polys, const uint32_t* oracle_blinding, uint32_t num_oracles,
+                              const uint32_t* batch_sizes, uint32_t num_batches, const uint32_t* polynomials,
+                              const uint32_t* reduction_arity_bits, uint32_t num_layers, uint32_t proof_of_work_bits,
+                              uint32_t num_query_rounds, const void* const* points, const void* const* openings,
+                              const void* const* initial_caps, const gb_challenger_state* challengers, const void* const* fri_proofs,
+                              const size_t* fri_proof_lens, uint32_t num_items, uint32_t flags,
+                              void* results /* gb_verify_result[num_items] */);
+/* gb_fri_verify_batch on `ctx` since it was created: *device_items = the items whose query rounds the kernels decided,
+ * *host_items = every other item of a completed call (decided by the host stage, or walked on the host: an irregular item, a shape
+ * beyond the device path's limits).  How a caller - and the test suite - sees that a shape left the device path. */
+gb_status gb_fri_verify_batch_counts(gb_ctx* ctx, uint64_t* device_items, uint64_t* host_items);
 
 /* fri_proof_of_work (fri/prover.rs:136-188) on its own, for a host that keeps the Challenger: sponge_state is the
  * duplex state with the pending input buffer already written over lanes 0..witness_pos-1 (`duplex_intermediate_state`,

@@ -373,6 +373,14 @@ extern "C" {
                      batch_sizes: *const u32, num_batches: u32, polynomials: *const u32, openings: *const c_void,
                      initial_caps: *const c_void, reduction_arity_bits: *const u32, num_layers: u32, proof_of_work_bits: u32,
                      num_query_rounds: u32, challenger: *const gb_challenger_state, fri_proof: *const c_void, fri_proof_len: usize) -> i32;
+    fn gb_fri_verify_batch(ctx: *mut gb_ctx, field: u32, degree_bits: u32, rate_bits: u32, cap_height: u32, hiding: u32,
+                           oracle_num_polys: *const u32, oracle_blinding: *const u32, num_oracles: u32, batch_sizes: *const u32,
+                           num_batches: u32, polynomials: *const u32, reduction_arity_bits: *const u32, num_layers: u32,
+                           proof_of_work_bits: u32, num_query_rounds: u32, points: *const *const c_void, openings: *const *const c_void,
+                           initial_caps: *const *const c_void, challengers: *const gb_challenger_state,
+                           fri_proofs: *const *const c_void, fri_proof_lens: *const usize, num_items: u32, flags: u32,
+                           results: *mut c_void) -> i32;
+    fn gb_fri_verify_batch_counts(ctx: *mut gb_ctx, device_items: *mut u64, host_items: *mut u64) -> i32;
     fn gb_circuit_create_gates(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
                                constants_sigmas: *const c_void, k_is: *const c_void, flags: u32, out: *mut *mut gb_circuit) -> i32;
     fn gb_prove_retry(c: *mut gb_circuit, witness: *const c_void, flags: u32, wire: u32, row: u64, public_inputs: *const u64,
@@ -870,6 +878,64 @@ pub fn fri_verify<W: Copy + Default>(instance: &FriInstance<W>, openings: &[W], 
     }
     check(ptr::null(), st)?;
     Ok(true)
+}
+/// One proof of `fri_verify_batch`: what `fri_verify` takes beside the shape.  `points`: [num_batches][D]; `openings` and
+/// `initial_caps` laid end to end as for `fri_verify`; `challenger`: the transcript after the openings were observed (not advanced).
+pub struct FriBatchItem<'a, W> {
+    pub points: &'a [W],
+    pub openings: &'a [W],
+    pub initial_caps: &'a [W],
+    pub challenger: gb_challenger_state,
+    pub fri_proof: &'a [u8],
+}
+/// `fri_verify` of many proofs on ONE instance shape, the query rounds on the device (`gb_fri_verify_batch`): one
+/// `gb_verify_result` per item (its `status` is what `fri_verify` would answer); Err only when the call itself did not complete.
+/// `shape` gives the oracles and the lists (its own `points` are not read: every item brings its points); proofs of several
+/// shapes are grouped by the caller, one call per shape.
+pub fn fri_verify_batch<W: Copy + Default>(ctx: &GpuContext, shape: &FriInstance<W>, params: &FriParams, items: &[FriBatchItem<W>])
+                                           -> Result<Vec<gb_verify_result>, GpuError> {
+    let (d, h) = if std::mem::size_of::<W>() == 8 { (2, 4) } else { (4, 8) };
+    let mut sizes = Vec::with_capacity(shape.polynomials.len());
+    let mut polys = Vec::new();
+    for batch in shape.polynomials {
+        sizes.push(batch.len() as u32);
+        for &(o, k) in batch.iter() {
+            polys.push(o as u32);
+            polys.push(k as u32);
+        }
+    }
+    for it in items {
+        need("points", it.points.len(), sizes.len() * d)?;
+        need("openings", it.openings.len(), polys.len() / 2 * d)?;
+        need("initial_caps", it.initial_caps.len(), shape.oracles.len() * (h << params.cap_height))?;
+    }
+    let num_polys: Vec<u32> = shape.oracles.iter().map(|o| o.0 as u32).collect();
+    let blinding: Vec<u32> = shape.oracles.iter().map(|o| o.1 as u32).collect();
+    let arity: Vec<u32> = params.reduction_arity_bits.iter().map(|&b| b as u32).collect();
+    let points: Vec<*const c_void> = items.iter().map(|it| it.points.as_ptr() as *const c_void).collect();
+    let openings: Vec<*const c_void> = items.iter().map(|it| it.openings.as_ptr() as *const c_void).collect();
+    let caps: Vec<*const c_void> = items.iter().map(|it| it.initial_caps.as_ptr() as *const c_void).collect();
+    let proofs: Vec<*const c_void> = items.iter().map(|it| it.fri_proof.as_ptr() as *const c_void).collect();
+    let lens: Vec<usize> = items.iter().map(|it| it.fri_proof.len()).collect();
+    let challengers: Vec<gb_challenger_state> = items.iter().map(|it| it.challenger).collect();
+    let mut res = vec![gb_verify_result::default(); items.len()];
+    let st = unsafe {
+        gb_fri_verify_batch(ctx.0, field_tag::<W>(), params.degree_bits, params.rate_bits, params.cap_height, params.hiding as u32,
+                            num_polys.as_ptr(), blinding.as_ptr(), num_polys.len() as u32, sizes.as_ptr(), sizes.len() as u32,
+                            polys.as_ptr(), arity.as_ptr(), arity.len() as u32, params.proof_of_work_bits, params.num_query_rounds,
+                            points.as_ptr(), openings.as_ptr(), caps.as_ptr(), challengers.as_ptr(), proofs.as_ptr(), lens.as_ptr(),
+                            items.len() as u32, 0, res.as_mut_ptr() as *mut c_void)
+    };
+    if st != GB_ERR_VERIFY {
+        check(ctx.0, st)?;
+    }
+    Ok(res)
+}
+/// (device_items, host_items) of `fri_verify_batch` on `ctx` since it was created (`gb_fri_verify_batch_counts`)
+pub fn fri_verify_batch_counts(ctx: &GpuContext) -> Result<(u64, u64), GpuError> {
+    let (mut dev, mut host) = (0u64, 0u64);
+    check(ctx.0, unsafe { gb_fri_verify_batch_counts(ctx.0, &mut dev, &mut host) })?;
+    Ok((dev, host))
 }
 
 /// What `CircuitBuilder::build()` leaves for the prover, resident on the GPU (circuit_builder.rs:1214-1312).

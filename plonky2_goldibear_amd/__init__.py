@@ -3,7 +3,7 @@
 csrc/      hand-written HIP kernels + the C ABI declared in include/goldibear_gpu.h
 native     ctypes binding of that ABI (no fallback: raises if the library is missing)
 polynomial_batch  host-side mirror of PolynomialBatch / MerkleTree (fri/oracle.rs, hash/merkle_tree.rs)
-fri         the polynomial commitment scheme on its own: prove_openings on any FriInstanceInfo, verify_fri_proof (fri/oracle.rs, fri/verifier.rs)
+fri         the polynomial commitment scheme on its own: prove_openings on any FriInstanceInfo, verify_fri_proof, verify_fri_proofs (fri/oracle.rs, fri/verifier.rs)
 polynomial  the transforms on their own: fft / ifft / coset_fft / coset_ifft / lde / lde_onto_coset (field/src/polynomial/mod.rs)
 wiring      copy constraints -> sigma columns and representative map on the device: sigma_polys (plonk/permutation_argument.rs)
 """
@@ -15,7 +15,7 @@ from .polynomial import coset_fft, coset_ifft, fft, ifft, lde, lde_onto_coset  #
 from .prover import CircuitData, SigmaInfo, VerifierCircuitData  # noqa: F401
 from .wiring import WiringInfo, sigma_polys  # noqa: F401
 from .fri import FriBatchInfo, FriConfig, FriInstanceInfo, FriOracleInfo, FriParams, FriPolynomialInfo  # noqa: F401
-from .fri import prove_openings, verify_fri_proof  # noqa: F401
+from .fri import prove_openings, verify_fri_proof, verify_fri_proofs  # noqa: F401
 from .gate_program import GateProgram, ProgramGate, pack_programs  # noqa: F401
 from .generator_program import GeneratorProgram, ProgramGenerator, pack_generator_programs  # noqa: F401
 from .integer_gadgets import div_rem, is_less_than, mul_add_split_gate  # noqa: F401

@@ -110,6 +110,8 @@ struct gb_ctx {
     size_t vstage_bytes = 0;
     hipEvent_t vstage_read[2] = {nullptr, nullptr};         // recorded behind the uploads out of a slot
     DeviceBuf vkeys;
+    DeviceBuf vshape;                                       // gb_fri_verify_batch: the shape's tables (kernels.hpp FriVerifyLayout), resident for a call
+    u64 fri_batch_device_items = 0, fri_batch_host_items = 0;   // gb_fri_verify_batch_counts
     // include/goldibear_gpu_test_hooks.h: gb_test_force_gate_fallback / gb_test_gate_fallback_launches (kernels.hpp GateLaunchOptions)
     bool test_force_gate_fallback = false;
     u64 test_gate_fallback_launches = 0;
@@ -1166,6 +1168,7 @@ gb_status gb_ctx_destroy(gb_ctx* ctx) try {
         if (ctx->vstage_read[s]) (void)hipEventDestroy(ctx->vstage_read[s]);
     }
     if (ctx->vkeys.p) (void)hipFree(ctx->vkeys.p);
+    if (ctx->vshape.p) (void)hipFree(ctx->vshape.p);
     if (ctx->xfer_up) (void)hipHostFree(ctx->xfer_up);
     if (ctx->xfer_down) (void)hipHostFree(ctx->xfer_down);
     hipStreamDestroy(ctx->stream);

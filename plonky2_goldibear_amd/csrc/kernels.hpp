@@ -514,6 +514,30 @@ void verify_paths(const VerifyLayout& L, const unsigned char* rounds, const unsi
 template <class F>
 void verify_queries(const VerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st);
 
+// ---- gb_fri_verify_batch (kernels_verify.hip): the same two kernels over ANY FriInstanceInfo.  What the layout above holds as
+// arrays of fixed size lives in device memory here - uploaded once per call, resident for all of its chunks:
+//   trees[num_oracles + num_layers]   VerifyTree as above; every tree's cap is in the item's record (cap_word is never ~0u), and an
+//                                     oracle's num_words counts its salts (hiding && blinding), which are hashed and never combined
+//   arity_bits[num_layers], batch_sizes[num_batches]
+//   batch_base[num_batches]           the first entry of batch b in poly_off (the prefix sums of batch_sizes)
+//   poly_off[sum of batch_sizes]      per entry of `polynomials`: the byte offset inside a query round of that polynomial's word -
+//                                     (oracle_index, polynomial_index) resolved by the host, once
+// `rounds` is as above.  An item's record:
+//   E section: fri_alpha, red_open[num_batches], alpha_shift[num_batches], points[num_batches], betas[num_layers],
+//              final_poly[final_len]                                                                        (device form)
+//   at rec_x_off:    u64 x_indices[nqr]
+//   at rec_caps_off: T initial caps [num_oracles], layer_caps[num_layers], each H << cap_height canonical words
+// Keys as above, with num_oracles in the positions (verify_query.hpp): num_oracles + 2 * num_layers + 1 < 2^POS_BITS.
+struct FriVerifyLayout {
+    u32 num_proofs, nqr, lgN, num_oracles, num_batches, num_layers, final_len, round_bytes, rec_bytes, rec_x_off, rec_caps_off;
+    const VerifyTree* trees;
+    const u32 *arity_bits, *batch_sizes, *batch_base, *poly_off;
+};
+template <class F>
+void fri_verify_paths(const FriVerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st);
+template <class F>
+void fri_verify_queries(const FriVerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st);
+
 // ---- gb_verify_compressed_batch (kernels_verify.hip): the same checks on COMPRESSED proofs (verify_compressed.hpp).  A proof's
 // query section - per tree the entries of its distinct indices, as they stand behind the stored indices - lies at
 // rounds + proof * proof_stride, and its record carries a directory behind the caps:

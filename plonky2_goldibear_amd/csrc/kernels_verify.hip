@@ -8,6 +8,9 @@
 // keys (query round, position in the round), which is the check the host verifier reaches first, whatever the schedule.
 // All offsets come from the circuit's shape (VerifyLayout, kernels.hpp); the proofs' bytes are only ever read as field words.
 //
+// gb_fri_verify_batch's device stage: the same two kernels over any FriInstanceInfo (k_fri_verify_paths, k_fri_verify_queries) - the
+// shape's tables live in device memory (FriVerifyLayout, kernels.hpp) instead of the launch argument, every cap in the item's record.
+//
 // gb_verify_compressed_batch's device stage: the same checks where the query rounds of a proof are no longer independent
 // (verify_compressed.hpp), so one workgroup holds all query rounds of a proof, a lane each, and they advance together through LDS.
 //   k_vc_queries      one workgroup per proof: fri_combine_initial, then layer by layer - the lanes publish their running
@@ -96,6 +99,75 @@ __global__ __launch_bounds__(64) void k_verify_queries(VerifyLayout L, const uns
         [&](u32 li) { return round + L.trees[VERIFY_ORACLES + li].row_off; }, [&](u32 li) { return betas[li]; },
         [&](u32 i) { return fin[i]; }, [](u32, u64) { return true; });   // (the layers' paths: k_verify_paths)
     if (pos != ~0u) atomicMin(reinterpret_cast<unsigned long long*>(keys + proof), (unsigned long long)vq::fail_key(qr, pos));
+}
+
+// gb_fri_verify_batch: the two kernels above over a FriVerifyLayout (kernels.hpp) - any number of oracles and batches, the shape's
+// tables in device memory.  An item's record, as RecordView reads the PLONK one:
+template <class F>
+struct FriRecordView {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    const unsigned char* p;
+    const FriVerifyLayout& L;
+    __device__ __forceinline__ const E* ext() const { return reinterpret_cast<const E*>(p); }
+    __device__ __forceinline__ E fri_alpha() const { return ext()[0]; }
+    __device__ __forceinline__ const E* red_open() const { return ext() + 1; }
+    __device__ __forceinline__ const E* alpha_shift() const { return ext() + 1 + L.num_batches; }
+    __device__ __forceinline__ const E* points() const { return ext() + 1 + 2 * L.num_batches; }
+    __device__ __forceinline__ const E* betas() const { return ext() + 1 + 3 * L.num_batches; }
+    __device__ __forceinline__ const E* final_poly() const { return betas() + L.num_layers; }
+    __device__ __forceinline__ u64 x_index(u32 qr) const { return reinterpret_cast<const u64*>(p + L.rec_x_off)[qr]; }
+    __device__ __forceinline__ const T* caps() const { return reinterpret_cast<const T*>(p + L.rec_caps_off); }
+};
+
+// blockIdx.y = tree, as k_verify_paths: the lanes of a wave share (num_words, path_len), lanes past the end clamp their index.
+// Every tree's cap - the initial ones too - comes from the item's record.
+template <class F>
+__global__ __launch_bounds__(256) void k_fri_verify_paths(FriVerifyLayout L, const unsigned char* __restrict__ rounds,
+                                                          const unsigned char* __restrict__ records, u64* __restrict__ keys) {
+    const VerifyTree tr = L.trees[blockIdx.y];
+    const u32 total = L.num_proofs * L.nqr;
+    const u32 g0 = blockIdx.x * 256 + threadIdx.x;
+    const bool live = g0 < total;
+    const u32 g = live ? g0 : total - 1;
+    const u32 item = g / L.nqr, qr = g % L.nqr;
+    const FriRecordView<F> rec{records + (size_t)item * L.rec_bytes, L};
+    const unsigned char* round = rounds + ((size_t)item * L.nqr + qr) * L.round_bytes;
+    __shared__ poseidon_gl::v4i sponge_lds[Sponge<F>::LDS_V4];
+    Sponge<F> sp;
+    sp.init(sponge_lds);
+    const bool ok = vq::merkle_path_ok<F>(sp, round + tr.row_off, tr.num_words, rec.x_index(qr) >> tr.shift, round + tr.path_off,
+                                          tr.path_len, rec.caps() + tr.cap_word);
+    const u32 pos = blockIdx.y < L.num_oracles ? vq::pos_initial_path(blockIdx.y) : vq::pos_layer_path(L.num_oracles, blockIdx.y - L.num_oracles);
+    if (live && !ok) atomicMin(reinterpret_cast<unsigned long long*>(keys + item), (unsigned long long)vq::fail_key(qr, pos));
+}
+
+// one lane per (item, query round).  poly(b, i) reads the word at the tabled offset: the index batch_base[b] + i is the same in
+// every lane, so the table is read through the scalar unit and only the word itself is a per-lane load.
+template <class F>
+__global__ __launch_bounds__(64) void k_fri_verify_queries(FriVerifyLayout L, const unsigned char* __restrict__ rounds,
+                                                           const unsigned char* __restrict__ records, u64* __restrict__ keys) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    const u32 g = blockIdx.x * 64 + threadIdx.x;
+    if (g >= L.num_proofs * L.nqr) return;
+    const u32 item = g / L.nqr, qr = g % L.nqr;
+    const FriRecordView<F> rec{records + (size_t)item * L.rec_bytes, L};
+    const unsigned char* round = rounds + ((size_t)item * L.nqr + qr) * L.round_bytes;
+    const u64 x_index = rec.x_index(qr);
+    const T x = vq::subgroup_x<F>(L.lgN, x_index);
+    const u32* __restrict__ poly_off = L.poly_off;
+    const u32* __restrict__ batch_base = L.batch_base;
+    auto poly = [&](u32 b, u32 i) { return vq::load_word<F>(round + poly_off[batch_base[b] + i]); };
+    const E old_eval = vq::combine_initial<F>(L.num_batches, L.batch_sizes, rec.points(), rec.red_open(), rec.alpha_shift(), rec.fri_alpha(), x, poly);
+    const E* betas = rec.betas();
+    const E* fin = rec.final_poly();
+    const VerifyTree* layer_trees = L.trees + L.num_oracles;
+    const u32 pos = vq::fold_checks<F>(
+        L.num_oracles, L.num_layers, L.arity_bits, x_index, x, old_eval, L.final_len,
+        [&](u32 li) { return round + layer_trees[li].row_off; }, [&](u32 li) { return betas[li]; },
+        [&](u32 i) { return fin[i]; }, [](u32, u64) { return true; });   // (the layers' paths: k_fri_verify_paths)
+    if (pos != ~0u) atomicMin(reinterpret_cast<unsigned long long*>(keys + item), (unsigned long long)vq::fail_key(qr, pos));
 }
 
 template <class F>
@@ -245,6 +317,19 @@ void verify_queries(const VerifyLayout& L, const unsigned char* rounds, const un
 }
 
 template <class F>
+void fri_verify_paths(const FriVerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st) {
+    const u64 total = (u64)L.num_proofs * L.nqr;
+    if (!total) return;
+    hipLaunchKernelGGL(k_fri_verify_paths<F>, dim3(nblk(total, 256), L.num_oracles + L.num_layers), dim3(256), 0, st, L, rounds, records, keys);
+}
+template <class F>
+void fri_verify_queries(const FriVerifyLayout& L, const unsigned char* rounds, const unsigned char* records, u64* keys, hipStream_t st) {
+    const u64 total = (u64)L.num_proofs * L.nqr;
+    if (!total) return;
+    hipLaunchKernelGGL(k_fri_verify_queries<F>, dim3(nblk(total, 64)), dim3(64), 0, st, L, rounds, records, keys);
+}
+
+template <class F>
 void verify_compressed_queries(const VerifyCompressedLayout& C, const unsigned char* rounds, const unsigned char* records,
                                typename F::T* inferred, u64* keys, hipStream_t st) {
     if (!C.L.num_proofs || !C.L.nqr) return;
@@ -266,5 +351,9 @@ template void verify_paths<GlF>(const VerifyLayout&, const unsigned char*, const
 template void verify_paths<BbF>(const VerifyLayout&, const unsigned char*, const unsigned char*, const u32*, u64*, hipStream_t);
 template void verify_queries<GlF>(const VerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
 template void verify_queries<BbF>(const VerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
+template void fri_verify_paths<GlF>(const FriVerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
+template void fri_verify_paths<BbF>(const FriVerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
+template void fri_verify_queries<GlF>(const FriVerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
+template void fri_verify_queries<BbF>(const FriVerifyLayout&, const unsigned char*, const unsigned char*, u64*, hipStream_t);
 
 }  // namespace gbk

@@ -541,8 +541,75 @@ void verify_impl(Circuit<F>* c, const uint8_t* bytes, size_t len) {
     verify_parsed(c, sh, pp);
 }
 
-// verify_fri_proof (fri/verifier.rs:67-250) on an instance described by flat arrays (include/goldibear_gpu.h); the lists have been
-// checked, `ch` is the caller's transcript by value
+// An instance described by flat arrays (include/goldibear_gpu.h), for gb_fri_verify and gb_fri_verify_batch's host stage alike - the
+// two must answer alike, so what they do to an item is written once:
+//   fri_shape_instance   the shape (the lists have been checked) as a FriInstance whose points are still zero
+//   fri_read_item        an item's points, openings and caps: canonical checks in gb_fri_verify's order, device form; a word >= p
+//                        goes to bad(what), which throws
+//   fri_read_proof       the FriProof bytes and the challenges drawn from `ch`; bytes left over go to trailing(), which throws
+template <class F>
+FriInstance<F> fri_shape_instance(u32 degree_bits, u32 rate_bits, u32 cap_height, bool hiding, const uint32_t* num_polys,
+                                  const uint32_t* blinding, u32 num_oracles, const uint32_t* batch_sizes, u32 num_batches,
+                                  const uint32_t* polynomials) {
+    FriInstance<F> in;
+    in.lg = degree_bits; in.r = rate_bits; in.capH = cap_height; in.lgN = degree_bits + rate_bits;
+    for (u32 o = 0; o < num_oracles; o++) {
+        in.widths.push_back(num_polys[o]);
+        in.row_widths.push_back(num_polys[o] + (hiding && blinding[o] ? (size_t)GB_SALT_SIZE : 0));   // salted = hiding && blinding
+    }
+    in.batches.resize(num_batches);
+    size_t at = 0;
+    for (u32 b = 0; b < num_batches; b++) {
+        in.batches[b].point = F::ezero();
+        for (u32 j = 0; j < batch_sizes[b]; j++, at++) in.batches[b].polys.emplace_back(polynomials[2 * at], polynomials[2 * at + 1]);
+    }
+    return in;
+}
+template <class F, class Bad>
+void fri_read_item(FriInstance<F>& in, const void* points, const void* openings, const void* caps, size_t cap_elems,
+                   std::vector<std::vector<typename F::E>>& open, std::vector<const typename F::T*>& cap_ptrs, Bad bad) {
+    typedef typename F::T T;
+    typedef typename F::E E;
+    auto ext_at = [&bad](const void* base, size_t i, const char* what) {
+        E e = F::ezero();
+        for (u32 k = 0; k < F::D; k++) {
+            const T w = static_cast<const T*>(base)[i * F::D + k];
+            if ((u64)w >= F::ORDER) bad(what);
+            F::set_coord(e, k, F::enc(w));
+        }
+        return e;
+    };
+    open.assign(in.batches.size(), {});
+    size_t at = 0;
+    for (size_t b = 0; b < in.batches.size(); b++) {
+        in.batches[b].point = ext_at(points, b, "the points");
+        for (size_t j = 0; j < in.batches[b].polys.size(); j++, at++) open[b].push_back(ext_at(openings, at, "the openings"));
+    }
+    cap_ptrs.resize(in.widths.size());
+    for (size_t o = 0; o < in.widths.size(); o++) {
+        cap_ptrs[o] = static_cast<const T*>(caps) + o * cap_elems;
+        for (size_t i = 0; i < cap_elems; i++)
+            if ((u64)cap_ptrs[o][i] >= F::ORDER) bad("the initial caps");
+    }
+}
+template <class F, class Trailing>
+void fri_read_proof(const FriInstance<F>& in, const std::vector<uint32_t>& arity_bits, u32 nqr, size_t cap_elems, size_t final_len,
+                    typename Host<F>::Challenger& ch, const uint8_t* bytes, size_t len, ParsedProof<F>& pp, Challenges<F>& chal,
+                    Trailing trailing) {
+    ProofReader<F> rd{bytes, len};
+    parse_fri_caps(rd, (u32)arity_bits.size(), cap_elems, pp);
+    parse_fri_queries(rd, in.row_widths.data(), (u32)in.widths.size(), arity_bits, nqr, final_len, pp);
+    if (rd.off != len) trailing();
+    get_fri_challenges<F>(ch, pp, nqr, (u64)1 << in.lgN, chal);
+}
+inline size_t fri_final_len(u32 degree_bits, const std::vector<uint32_t>& arity_bits) {
+    u32 total_arity = 0;
+    for (u32 ab : arity_bits) total_arity += ab;
+    return (size_t)1 << (degree_bits - total_arity);
+}
+
+// verify_fri_proof (fri/verifier.rs:67-250) on an instance described by flat arrays; the lists have been checked, `ch` is the
+// caller's transcript by value
 template <class F>
 void fri_verify_impl(u32 degree_bits, u32 rate_bits, u32 cap_height, bool hiding, const uint32_t* num_polys, const uint32_t* blinding,
                      u32 num_oracles, const void* points, const uint32_t* batch_sizes, u32 num_batches, const uint32_t* polynomials,
@@ -550,48 +617,18 @@ void fri_verify_impl(u32 degree_bits, u32 rate_bits, u32 cap_height, bool hiding
                      typename Host<F>::Challenger ch, const uint8_t* bytes, size_t len) {
     typedef typename F::T T;
     typedef typename F::E E;
-    constexpr u32 D = F::D;
-    FriInstance<F> in;
-    in.lg = degree_bits; in.r = rate_bits; in.capH = cap_height; in.lgN = degree_bits + rate_bits;
-    for (u32 o = 0; o < num_oracles; o++) {
-        in.widths.push_back(num_polys[o]);
-        in.row_widths.push_back(num_polys[o] + (hiding && blinding[o] ? (size_t)GB_SALT_SIZE : 0));   // salted = hiding && blinding
-    }
-    auto ext_at = [](const void* base, size_t i, const char* what) {
-        E e = F::ezero();
-        for (u32 k = 0; k < D; k++) {
-            const T w = static_cast<const T*>(base)[i * D + k];
-            if ((u64)w >= F::ORDER) throw VerifyFail{GB_ERR_INVALID, std::string("non-canonical field element in ") + what};
-            F::set_coord(e, k, F::enc(w));
-        }
-        return e;
-    };
-    std::vector<std::vector<E>> open(num_batches);
-    in.batches.resize(num_batches);
-    size_t at = 0;
-    for (u32 b = 0; b < num_batches; b++) {
-        in.batches[b].point = ext_at(points, b, "the points");
-        for (u32 j = 0; j < batch_sizes[b]; j++, at++) {
-            in.batches[b].polys.emplace_back(polynomials[2 * at], polynomials[2 * at + 1]);
-            open[b].push_back(ext_at(openings, at, "the openings"));
-        }
-    }
+    FriInstance<F> in = fri_shape_instance<F>(degree_bits, rate_bits, cap_height, hiding, num_polys, blinding, num_oracles, batch_sizes,
+                                              num_batches, polynomials);
     const size_t cap_elems = (size_t)F::H << cap_height;
-    std::vector<const T*> cap_ptrs(num_oracles);
-    for (u32 o = 0; o < num_oracles; o++) {
-        cap_ptrs[o] = static_cast<const T*>(caps) + o * cap_elems;
-        for (size_t i = 0; i < cap_elems; i++)
-            if ((u64)cap_ptrs[o][i] >= F::ORDER) throw VerifyFail{GB_ERR_INVALID, "non-canonical field element in the initial caps"};
-    }
-    u32 total_arity = 0;
-    for (u32 ab : arity_bits) total_arity += ab;
+    std::vector<std::vector<E>> open;
+    std::vector<const T*> cap_ptrs;
+    fri_read_item<F>(in, points, openings, caps, cap_elems, open, cap_ptrs, [](const char* what) {
+        throw VerifyFail{GB_ERR_INVALID, std::string("non-canonical field element in ") + what};
+    });
     ParsedProof<F> pp;
-    ProofReader<F> rd{bytes, len};
-    parse_fri_caps(rd, (u32)arity_bits.size(), cap_elems, pp);
-    parse_fri_queries(rd, in.row_widths.data(), num_oracles, arity_bits, nqr, (size_t)1 << (degree_bits - total_arity), pp);
-    if (rd.off != len) throw VerifyFail{GB_ERR_INVALID, "trailing bytes in proof"};
     Challenges<F> chal;
-    get_fri_challenges<F>(ch, pp, nqr, (u64)1 << in.lgN, chal);
+    fri_read_proof<F>(in, arity_bits, nqr, cap_elems, fri_final_len(degree_bits, arity_bits), ch, bytes, len, pp, chal,
+                      [] { throw VerifyFail{GB_ERR_INVALID, "trailing bytes in proof"}; });
     const FriQueryMath<F> fri(std::move(in), open, chal.fri_alpha);
     verify_fri_parsed<F>(fri, cap_ptrs.data(), arity_bits, proof_of_work_bits, pp, chal);
 }

@@ -138,13 +138,15 @@ GB_HD typename F::E combine_initial(u32 num_batches, const u32* sizes, const typ
 // barycentric weight of x_i is 1 / (arity x_i^(arity-1)) = x_i / (arity c^arity):
 //   P(beta) = (beta^arity - c^arity) / (arity c^arity) * sum_i eval(rev i) x_i / (beta - x_i)
 // - arity inversions' worth of work instead of the arity^2 products of interpolate(); field arithmetic is exact, so the value
-// is the same.  The denominators are inverted eight at a time (one inversion and 21 products per group).  beta on the coset
+// is the same.  The denominators are inverted G at a time (one inversion and 3 (G - 1) products per group).  beta on the coset
 // (no inverse) returns that point's value.
 template <class F, class EvalAt>
 GB_HD typename F::E compute_evaluation(typename F::T x, u64 within, u32 arity_bits, typename F::E beta, EvalAt eval) {
     typedef typename F::T T;
     typedef typename F::E E;
-    constexpr u32 G = 8;
+    // (the quartic extension in groups of four: at eight the unrolled group outgrows the compiler's full-unroll budget, the loops
+    // stay rolled and d / pre go to scratch - 272 bytes a lane in every BabyBear queries kernel)
+    constexpr u32 G = F::D > 2 ? 4 : 8;
     const u32 arity = 1u << arity_bits;
     const E one = F::efrom(F::one());
     const T g = F::two_adic_generator(arity_bits);

@@ -196,4 +196,78 @@ def verify_fri_proof(instance, openings, challenger, initial_merkle_caps, proof,
     return True
 
 
+def _shape_of(instance):
+    """what the items of verify_fri_proofs must share: everything of the instance but its points"""
+    return ([(int(o.num_polys), bool(o.blinding)) for o in instance.oracles],
+            [[(int(p.oracle_index), int(p.polynomial_index)) for p in b.polynomials] for b in instance.batches])
+
+
+def verify_fri_proofs(ctx, items, params, field=N.GB_GOLDILOCKS):
+    """gb_fri_verify_batch: verify_fri_proof of many proofs on ONE instance shape, the query rounds on the device of `ctx` ->
+    [native.VerifyResult], one per item.  items: (instance, openings, challenger, initial_merkle_caps, proof) as verify_fri_proof
+    takes them; the instances must agree in everything but their points (ShapeError names the first item that differs - group
+    proofs of several shapes by shape).  A failing proof is reported, not raised, as in verify_batch; malformed arguments raise."""
+    fld = field
+    d = 2 if fld == N.GB_GOLDILOCKS else 4
+    hh = 4 if fld == N.GB_GOLDILOCKS else 8
+    dt = _dtype(fld)
+    items = list(items)
+    n = len(items)
+    if not n:
+        return []
+    first = items[0][0]
+    shape = _shape_of(first)
+    _, sizes, polys = _flatten(first, fld)
+    cap_h = params.config.cap_height
+    keep = []   # the arrays the pointer tables name
+    pts_t, op_t, cap_t, proof_t = ((C.c_void_p * n)() for _ in range(4))
+    lens = (C.c_size_t * n)()
+    chs = (gb_challenger_state * n)()
+    empty = np.zeros(1, dtype=np.uint8)
+    for i, (instance, openings, challenger, caps, proof) in enumerate(items):
+        if i and _shape_of(instance) != shape:
+            raise N.ShapeError(N.GB_ERR_INVALID, "item %d: its instance differs from item 0's in more than the points" % i)
+        pts, _, _ = _flatten(instance, fld)
+        if len(openings) != len(instance.batches):
+            raise N.ShapeError(N.GB_ERR_INVALID, "item %d: one list of openings per batch is expected" % i)
+        flat = []
+        for b, (vals, batch) in enumerate(zip(openings, instance.batches)):
+            v = np.ascontiguousarray(vals, dtype=dt).reshape(-1, d)
+            if v.shape[0] != len(batch.polynomials):
+                raise N.ShapeError(N.GB_ERR_INVALID, "item %d, batch %d: %d openings for %d polynomials" % (i, b, v.shape[0], len(batch.polynomials)))
+            flat.append(v)
+        op = np.ascontiguousarray(np.concatenate(flat))
+        if len(caps) != len(instance.oracles):
+            raise N.ShapeError(N.GB_ERR_INVALID, "item %d: one Merkle cap per oracle is expected" % i)
+        cp = np.ascontiguousarray(np.stack([np.ascontiguousarray(c, dtype=dt).reshape(-1, hh) for c in caps]))
+        if cp.shape[1] != 1 << cap_h:
+            raise N.ShapeError(N.GB_ERR_INVALID, "item %d: a Merkle cap has 2^cap_height digests" % i)
+        buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+        keep.append((pts, op, cp, buf))
+        pts_t[i], op_t[i], cap_t[i] = pts.ctypes.data, op.ctypes.data, cp.ctypes.data
+        proof_t[i] = buf.ctypes.data if buf.size else empty.ctypes.data   # (an empty proof is a truncated one, not a missing argument)
+        lens[i] = buf.size
+        chs[i] = _challenger_state(challenger, fld)[0]
+    nump = np.array([o.num_polys for o in first.oracles], dtype=np.uint32)
+    blind = np.array([1 if o.blinding else 0 for o in first.oracles], dtype=np.uint32)
+    arity = np.array(list(params.reduction_arity_bits), dtype=np.uint32)
+    res = (N.gb_verify_result * n)()
+    lib = N.load()
+    h = ctx.handle if ctx is not None else None
+    st = lib.gb_fri_verify_batch(h, fld, params.degree_bits, params.config.rate_bits, cap_h, int(bool(params.hiding)), _u32p(nump),
+                                 _u32p(blind), len(nump), _u32p(sizes), len(sizes), _u32p(polys), _u32p(arity), len(arity),
+                                 params.config.proof_of_work_bits, params.config.num_query_rounds, pts_t, op_t, cap_t,
+                                 C.cast(chs, C.c_void_p), proof_t, lens, n, 0, C.cast(res, C.c_void_p))
+    if st not in (N.GB_OK, N.GB_ERR_VERIFY):
+        N.check(st, h)
+    return [N.VerifyResult(r.status, r.check, (lib.gb_verify_check_text(r.check) or b"").decode(), r.query_round, r.index) for r in res]
+
+
+def fri_verify_batch_counts(ctx):
+    """gb_fri_verify_batch_counts -> (device_items, host_items) of verify_fri_proofs on `ctx` since it was created"""
+    dev, host = C.c_uint64(), C.c_uint64()
+    N.check(N.load().gb_fri_verify_batch_counts(ctx.handle, C.byref(dev), C.byref(host)), ctx.handle)
+    return dev.value, host.value
+
+
 PolynomialBatch.prove_openings = staticmethod(prove_openings)

@@ -97,6 +97,10 @@ SIGNATURES = {
                                      _sz, C.POINTER(_sz)]),
     "gb_fri_verify": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, _vp, C.POINTER(_u32), _u32,
                              C.POINTER(_u32), _vp, _vp, C.POINTER(_u32), _u32, _u32, _u32, _vp, _vp, _sz]),
+    "gb_fri_verify_batch": (_i32, [_vp, _u32, _u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _u32, C.POINTER(_u32), _u32,
+                                   C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _u32, _cols, _cols, _cols, _vp, _cols, C.POINTER(_sz), _u32,
+                                   _u32, _vp]),
+    "gb_fri_verify_batch_counts": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "gb_prove": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_circuit_drop_retry": (_i32, [_vp]),
