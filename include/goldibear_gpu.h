@@ -988,6 +988,66 @@ gb_status gb_fri_verify_batch(gb_ctx* ctx, uint32_t field, uint32_t degree_bits,
  * beyond the device path's limits).  How a caller - and the test suite - sees that a shape left the device path. */
 gb_status gb_fri_verify_batch_counts(gb_ctx* ctx, uint64_t* device_items, uint64_t* host_items);
 
+/* ---- constraint systems over committed oracles ---------------------------------------------------------------------------------
+ * The quotient stage for a host that proves with gb_commit_* / gb_fri_prove_openings and constraints of its own - a circuit with
+ * lookup terms, a STARK over this FRI: the constraints are straight-line programs over CELLS (oracle, polynomial, rows ahead) of
+ * the committed oracles, numbered 0, 1, 2, ... by the EMITs of program 0, then program 1, and so on; challenge c folds them as
+ * sum_i alphas[c]^i * constraint_i, and the folded sum is divided by Z_H = X^n - 1 on a coset.
+ * The table is that of the constraint programs above (program_words, program_offsets, at most GB_MAX_PROGRAMS; instruction words,
+ * registers, literals and their limits unchanged) with two differences:
+ *   word 0   num_cells | num_inputs << 32         num_inputs = 3 + num_params
+ *   after the num_literals literals come num_cells CELL words (at most GB_MAX_PROGRAM_CELLS), then the instructions:
+ *     bits 0-15   oracle_index
+ *     bits 16-47  polynomial_index (salt columns are not polynomials)
+ *     bits 48-63  row_offset: rows ahead, modulo n (0 this row, 1 the next row, n - 1 the row before)
+ *   operand space 1 indexes the program's cell table instead of a wire column;
+ *   operand space 2 indexes the INPUTS: 0 is X (the point), 1 is L_first(X) = L_0, 2 is L_last(X) = L_(n-1), 3 + k is params[k] -
+ *   canonical base-field words for the caller's challenges and public values (plonky2's beta, gamma, delta are base-field elements).
+ * Degree bounds, in gb_circuit_create_programs' units: literal and param 0; cell, X, L_first, L_last 1; ADD / SUB the maximum, MUL
+ * the sum.  A constraint's bound is at most the header's `degree`, and `degree` at most 2^quotient_degree_bits + 1, so that the
+ * quotient has fewer than n * 2^quotient_degree_bits coefficients.
+ *
+ * gb_constraint_quotient: oracles[num_oracles] (at most GB_MAX_CONSTRAINT_ORACLES) are commitments made on ctx with one degree_bits
+ * and rate_bits; the constraints are evaluated on the first 2^quotient_degree_bits coset blocks of their LDEs (every
+ * 2^(rate_bits - quotient_degree_bits)-th point of g * H_N, as compute_quotient_polys does), one thread per point
+ * (k_constraint_quotient, the interpreter of k_gate_programs), followed by the coset inverse transform.  params: [num_params],
+ * alphas: [num_challenges], host pointers, canonical.  chunks_out: [num_challenges * 2^quotient_degree_bits][n] COEFFICIENTS,
+ * canonical, ready for gb_commit_coeffs: quotient_c(X) = sum_i X^(n i) chunk_(c,i)(X).  flags (GB_INPUT_HOST / GB_INPUT_DEVICE)
+ * names the memory space of chunks_out, as for gb_quotient_polys.  quotient_degree_bits 1 .. 4 and at most rate_bits;
+ * num_challenges 1 .. 16 (widths 1 .. 4 are compiled, other counts run as slices); num_params at most GB_MAX_CONSTRAINT_PARAMS.
+ * A trace that does not satisfy its constraints is no error: the call returns GB_OK and the chunks of a polynomial for which
+ * the identity below fails.
+ * GB_ERR_INVALID (the message names the program and the instruction or cell; everything is checked on the host before an index
+ * is used as an address): every malformation gb_circuit_create_programs refuses; an oracle_index >= num_oracles; a
+ * polynomial_index not below that oracle's polynomial count; a row_offset >= n; num_inputs != 3 + num_params; a param or alpha
+ * >= p; a NULL oracle, one from another context or field, or a stand-alone Merkle tree; oracles that differ in degree_bits or
+ * rate_bits; num_oracles of zero or above the limit; quotient_degree_bits or num_challenges out of range; other flag bits.
+ * Timing scopes: "constraint quotient: values", "constraint quotient: IFFT".
+ *
+ * gb_constraint_eval: the same words over the extension field at one point - the verifier's side, host only, ctx may be NULL
+ * (it only receives the error message).  cell_values: the opened values of the cells in cell-table order, program after
+ * program ([total cells][D]; a cell with row_offset k is the polynomial's opening at zeta * w_n^k); X = zeta,
+ * L_first(zeta) = Z_H(zeta) / (n (zeta - 1)), L_last(zeta) = L_first(zeta * w_n).  folded_out[c] = sum_i alphas[c]^i *
+ * constraint_i(zeta), NOT divided by Z_H: a verifier checks folded_c == Z_H(zeta) * sum_i zeta^(n i) * chunk_(c,i)(zeta), as
+ * plonk/verifier.rs:60-95 does.  oracle_index is checked against GB_MAX_CONSTRAINT_ORACLES and polynomial_index not at all (no
+ * oracle is at hand; neither is read); no degree is checked.  GB_ERR_INVALID besides the table's: an unknown field,
+ * degree_bits above the field's two-adicity, a coordinate of zeta or of cell_values >= p.  zeta inside the subgroup H_n, where
+ * L_first has no value, is GB_ERR_OPENING_IN_SUBGROUP, as for gb_prove_openings. */
+#define GB_MAX_CONSTRAINT_ORACLES 16
+#define GB_MAX_PROGRAM_CELLS 4096
+#define GB_MAX_CONSTRAINT_PARAMS 4096
+/* quotient of the alpha-folded constraints of `programs` over the LDEs of `oracles`, as degree-n coefficient chunks */
+gb_status gb_constraint_quotient(gb_ctx* ctx, gb_batch* const* oracles, uint32_t num_oracles,
+                                 const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                                 const void* params, uint32_t num_params, const void* alphas, uint32_t num_challenges,
+                                 uint32_t quotient_degree_bits, uint32_t flags, void* chunks_out);
+/* the same constraints at one extension point, from opened values: the verifier's side; host only, ctx may be NULL */
+gb_status gb_constraint_eval(gb_ctx* ctx, uint32_t field, uint32_t degree_bits,
+                             const uint64_t* program_words, const uint32_t* program_offsets, uint32_t num_programs,
+                             const void* cell_values /* [total cells][D] */, const void* params, uint32_t num_params,
+                             const void* zeta /* [D] */, const void* alphas, uint32_t num_challenges,
+                             void* folded_out /* [num_challenges][D] */);
+
 /* fri_proof_of_work (fri/prover.rs:136-188) on its own, for a host that keeps the Challenger: sponge_state is the
  * duplex state with the pending input buffer already written over lanes 0..witness_pos-1 (`duplex_intermediate_state`,
  * :165-167; [12] u64 / [16] u32 canonical), witness_pos = input_buffer.len().  Returns the MINIMUM candidate whose

@@ -381,6 +381,13 @@ extern "C" {
                            fri_proofs: *const *const c_void, fri_proof_lens: *const usize, num_items: u32, flags: u32,
                            results: *mut c_void) -> i32;
     fn gb_fri_verify_batch_counts(ctx: *mut gb_ctx, device_items: *mut u64, host_items: *mut u64) -> i32;
+    fn gb_constraint_quotient(ctx: *mut gb_ctx, oracles: *const *mut gb_batch, num_oracles: u32, program_words: *const u64,
+                              program_offsets: *const u32, num_programs: u32, params: *const c_void, num_params: u32,
+                              alphas: *const c_void, num_challenges: u32, quotient_degree_bits: u32, flags: u32,
+                              chunks_out: *mut c_void) -> i32;
+    fn gb_constraint_eval(ctx: *mut gb_ctx, field: u32, degree_bits: u32, program_words: *const u64, program_offsets: *const u32,
+                          num_programs: u32, cell_values: *const c_void, params: *const c_void, num_params: u32,
+                          zeta: *const c_void, alphas: *const c_void, num_challenges: u32, folded_out: *mut c_void) -> i32;
     fn gb_circuit_create_gates(ctx: *mut gb_ctx, cfg: *const gb_circuit_config, gates: *const gb_gate, num_gates: u32,
                                constants_sigmas: *const c_void, k_is: *const c_void, flags: u32, out: *mut *mut gb_circuit) -> i32;
     fn gb_prove_retry(c: *mut gb_circuit, witness: *const c_void, flags: u32, wire: u32, row: u64, public_inputs: *const u64,

@@ -1527,3 +1527,4 @@ gb_status gb_random_elements(gb_ctx* ctx, uint32_t field, const uint8_t* seed, c
 #include "verifier_host.inc"
 #include "compress_host.inc"
 #include "verify_batch_host.inc"
+#include "constraint_host.inc"

@@ -11,6 +11,7 @@
 #include "gate_set.hpp"
 #include "generator_ops.hpp"
 #include "challenge_slices.hpp"
+#include "constraint_system.hpp"
 #include "random_stream.hpp"
 #include "sigma_decode.hpp"
 #include "wiring.hpp"
@@ -284,6 +285,28 @@ template <class F>
 bool gate_constraints(const GateParams<F>& p, const typename F::T* cs, const typename F::T* wires, const typename F::T* apow,
                       const typename F::T* pi_hash, typename F::T* qv, hipStream_t st, const ProgramParams<F>* programs = nullptr,
                       const GateLaunchOptions& opt = GateLaunchOptions());
+// ---- gb_constraint_quotient (kernels_constraints.hip): the checked programs of constraint_system.hpp, headers and the oracles'
+// LDE blocks by value, the flat tables on the device.  rate_bits is that of the quotient domain, stride_bits the log2 of a column's
+// length in every oracle's LDE (log_n + the oracles' rate_bits).
+template <class F>
+struct ConstraintParams {
+    u32 log_n, rate_bits, stride_bits, num_programs, nterms /* constraints of all programs: the length of one challenge's alpha powers */;
+    PowTab<F> w_N;                       // powers of the quotient domain's generator
+    const typename F::T* l0;             // [n 2^rate_bits] L_0 on the quotient domain, leaf order (l0_table); null when no program reads it
+    const typename F::T* lde[constraints::MAX_ORACLES];   // [ncols + salt][2^stride_bits] each, leaf order
+    constraints::ProgramInfo p[gates::MAX_PROGRAMS];
+    u32 max_regs;
+    const u64* instrs;                   // instruction words of all programs (ProgramInfo::instr_off)
+    const u64* cells;                    // cell words of all programs (ProgramInfo::cell_off)
+    const typename F::T* lits;           // literals of all programs, device form (ProgramInfo::lit_off)
+    const typename F::T* params;         // [num_inputs - 3] device form
+};
+// qv[(k 2^rate_bits + coset) n + il] <- sum_i alpha_k^i constraint_i / Z_H for num_challenges <= MAX_CHALLENGES challenges (slices of
+// widths 1 .. 4); apow: [num_challenges][nterms] alpha powers, zh_inv: [2^rate_bits], both device form
+template <class F>
+bool constraint_quotient_values(const ConstraintParams<F>& p, u32 num_challenges, const typename F::T* apow, const typename F::T* zh_inv,
+                                typename F::T* qv, hipStream_t st);
+
 // ---- the witness check (kernels_check.hip's launchers; witness_check.hpp has the row logic).  hv: the selector and constant
 // columns as values on H, [num_selectors + num_constants][n], natural order, device form; wit: [num_wires][n] canonical words.
 // counts[MAX_LISTS] and offsets[MAX_LISTS + 1]: rows per list (a list per gate, then the rows with a selector violation) and

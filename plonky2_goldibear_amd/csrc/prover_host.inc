@@ -495,6 +495,31 @@ gb_status read_cap(gb_batch* b, std::vector<typename F::T>& cap) {
     return gb_batch_cap(b, cap.data());
 }
 
+// What a quotient on the first 2^qb coset blocks of size-n LDEs needs, in device form (circuit_create for the PLONK quotient,
+// gb_constraint_quotient for any other): Z_H and 1 / Z_H on the cosets, and the combine matrix of the coset_ifft's last step.
+template <class F>
+void quotient_domain_tables(u32 lg, u32 qb, std::vector<typename F::T>* zh, std::vector<typename F::T>* zh_inv, std::vector<typename F::T>* mat) {
+    typedef typename F::T T;
+    // ZeroPolyOnCoset::new(degree_bits, quotient_degree_bits): Z_H(g w_Q^i) = g^n w_R^(i mod R) - 1, R = 2^qb
+    const u32 R = 1u << qb;
+    const size_t n = (size_t)1 << lg;
+    T g_pow_n = F::pow(F::generator(), n), wR = F::two_adic_generator(qb), x = F::one();
+    for (u32 i = 0; i < R; i++) {
+        T v = F::sub(F::mul(g_pow_n, x), F::one());
+        zh->push_back(v);
+        zh_inv->push_back(F::inv(v));
+        x = F::mul(x, wR);
+    }
+    // combine matrix: mat[m][c] = g^(-n m) / R * zeta_c^(-m), zeta_c = w_R^bitrev_r(c)
+    mat->assign((size_t)R * R, F::zero());
+    T g_inv = F::inv(g_pow_n), r_inv = F::inv(F::enc(R));
+    for (u32 m = 0; m < R; m++)
+        for (u32 cc = 0; cc < R; cc++) {
+            T zeta = F::pow(wR, bitrev32(cc, qb));
+            (*mat)[m * R + cc] = F::mul(F::mul(F::pow(g_inv, m), r_inv), F::pow(F::inv(zeta), m));
+        }
+}
+
 // ---------------------------------------------------------------------------------------------- build()
 template <class F>
 gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::gates::GateSet& gset, bool general,
@@ -574,24 +599,9 @@ gb_status circuit_create(gb_ctx* ctx, const gb_circuit_config* cfg, const gbk::g
         if ((s = upload_owned(ctx, fpowers<F>(wN, 4096), &c->wN_lo, &c->owned))) return cleanup(s);
         if ((s = upload_owned(ctx, fpowers<F>(F::pow(wN, 4096), nhi_N), &c->wN_hi, &c->owned))) return cleanup(s);
     }
-    // ZeroPolyOnCoset::new(degree_bits, quotient_degree_bits): Z_H(g w_Q^i) = g^n w_R^(i mod R) - 1, R = 2^qb
-    const u32 R = 1u << qb;
     {
-        T g_pow_n = F::pow(F::generator(), n), wR = F::two_adic_generator(qb), x = F::one();
-        for (u32 i = 0; i < R; i++) {
-            T v = F::sub(F::mul(g_pow_n, x), F::one());
-            c->zh.push_back(v);
-            c->zh_inv.push_back(F::inv(v));
-            x = F::mul(x, wR);
-        }
-        // combine matrix: mat[m][c] = g^(-n m) / R * zeta_c^(-m), zeta_c = w_R^bitrev_r(c)
-        std::vector<T> mat(R * R);
-        T g_inv = F::inv(g_pow_n), r_inv = F::inv(F::enc(R));
-        for (u32 m = 0; m < R; m++)
-            for (u32 cc = 0; cc < R; cc++) {
-                T zeta = F::pow(wR, bitrev32(cc, qb));
-                mat[m * R + cc] = F::mul(F::mul(F::pow(g_inv, m), r_inv), F::pow(F::inv(zeta), m));
-            }
+        std::vector<T> mat;
+        quotient_domain_tables<F>(lg, qb, &c->zh, &c->zh_inv, &mat);
         if ((s = upload_owned(ctx, mat, &c->combine_mat, &c->owned))) return cleanup(s);
         // L_0 table for the quotient kernel
         T* zh_dev;
@@ -693,6 +703,29 @@ gb_status stage_zs_partial_products(Circuit<F>* c, TmpAlloc& tmp, const typename
     return defer_check ? GB_OK : perm_arg_check<F>(c, nullptr, 0, nullptr);
 }
 
+// The tail of a quotient stage: coset_ifft of size n 2^qb (prover.rs:921-925) = per-coset size-n inverse NTTs + radix-2^qb combine,
+// which leaves the degree-n chunks.  qv: [nch 2^qb][n] quotient values as the quotient kernels store them; qc: workspace of the same
+// size; combine_mat: quotient_domain_tables' matrix on the device; `scope`: the timing scope of the transforms (a scope of its
+// own: not a commitment's transform).
+template <class F>
+gb_status quotient_coset_ifft(gb_ctx* ctx, u32 lg, u32 qb, u32 nch, const typename F::T* qv, typename F::T* qc,
+                              const typename F::T* combine_mat, typename F::T* chunks, const char* scope) {
+    typedef typename F::T T;
+    typedef Host<F> HF;
+    const size_t n = (size_t)1 << lg, nq = (size_t)nch << qb;
+    hipStream_t st = ctx->stream;
+    gb_status s;
+    const typename HF::Tables* tabs;
+    const typename HF::Cosets* inv_cos;
+    if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
+    if ((s = cosets_for<F>(ctx, lg, qb, F::generator(), true, &inv_cos))) return s;
+    if ((s = ensure(ctx, ctx->scratch, nq * n * sizeof(T)))) return s;
+    { Scope sq(ctx, scope); gbk::intt_columns<F>(qv, qc, (T*)ctx->scratch.p, nq, *tabs, st); }
+    gbk::CosetPow<F> ip{inv_cos->pow_lo, inv_cos->pow_hi, (u32)(n < 4096 ? n : 4096), (u32)(n > 4096 ? n / 4096 : 1)};
+    gbk::quotient_combine<F>(lg, qb, nch, qc, combine_mat, ip, chunks, st);
+    return GB_OK;
+}
+
 // compute_quotient_polys (plonk/prover.rs:712-926) and the split into degree-n chunks (:345-376): out = [nch * qdf][n] chunk
 // COEFFICIENTS in device form.  pi_hash: canonical [H]; betas_d / gammas_d: device form; alphas: canonical.
 template <class F>
@@ -700,7 +733,6 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
                                const std::vector<typename F::T>& betas_d, const std::vector<typename F::T>& gammas_d,
                                const std::vector<typename F::T>& alphas, typename F::T** chunks_out) {
     typedef typename F::T T;
-    typedef Host<F> HF;
     constexpr u32 H = F::H;
     gb_ctx* ctx = c->ctx;
     const gb_circuit_config& cfg = c->cfg;
@@ -749,15 +781,7 @@ gb_status stage_quotient_polys(Circuit<F>* c, TmpAlloc& tmp, gb_batch* wires, gb
     }
     if (!gbk::quotient_values<F>(qp, (const T*)c->cs->lde, (const T*)wires->lde, (const T*)zs->lde, uni_dev, qv, st))
         return fail(ctx, GB_ERR_UNSUPPORTED, "no quotient kernel for this (degree factor, num_challenges)");
-    // coset_ifft of size n 2^qb (prover.rs:921-925) = per-coset size-n inverse NTTs + radix-2^qb combine
-    const typename HF::Tables* tabs;
-    const typename HF::Cosets* inv_cos;
-    if ((s = tables_for<F>(ctx, lg, &tabs))) return s;
-    if ((s = cosets_for<F>(ctx, lg, qb, F::generator(), true, &inv_cos))) return s;
-    if ((s = ensure(ctx, ctx->scratch, nq * n * sizeof(T)))) return s;
-    { Scope sq(ctx, "quotient IFFT"); gbk::intt_columns<F>(qv, qc, (T*)ctx->scratch.p, nq, *tabs, st); }   // (a scope of its own: not a commitment's transform)
-    gbk::CosetPow<F> ip{inv_cos->pow_lo, inv_cos->pow_hi, (u32)(n < 4096 ? n : 4096), (u32)(n > 4096 ? n / 4096 : 1)};
-    gbk::quotient_combine<F>(lg, qb, nch, qc, c->combine_mat, ip, chunks, st);
+    if ((s = quotient_coset_ifft<F>(ctx, lg, qb, nch, qv, qc, c->combine_mat, chunks, "quotient IFFT"))) return s;
     *chunks_out = chunks;
     return GB_OK;
 }

@@ -147,103 +147,117 @@ class GateProgram:
         degree: Gate::degree() when it is to be declared higher than the bound of the constraints."""
         dag = _Dag(field_order(field))
         outs = [dag.coerce(e) for e in fn(_Column(dag, "w", num_wires), _Column(dag, "c", num_constants))]
-        if len(outs) > MAX_CONSTRAINTS:
-            raise ValueError("%d constraints, at most %d" % (len(outs), MAX_CONSTRAINTS))
-        nodes = dag.nodes
-        # degree bounds: literal 0, wire and constant 1, add / sub the maximum, mul the sum
-        deg = [0] * len(nodes)
-        for i, k in enumerate(nodes):    # operands are created before the node that uses them
-            deg[i] = 0 if k[0] == "lit" else 1 if k[0] in "wc" else deg[k[1]] + deg[k[2]] if k[0] == "mul" else max(deg[k[1]], deg[k[2]])
-        bound = max([deg[e.i] for e in outs] or [0])
-        if degree is None:
-            degree = bound
-        if bound > degree:
-            raise ValueError("a constraint has degree bound %d, above the declared degree %d" % (bound, degree))
-        # schedule: the operations each constraint needs, operands first, in the order of the constraints
-        stream, seen = [], set()
-        for e in outs:
-            stack = [(e.i, False)]
-            while stack:
-                i, done = stack.pop()
-                if nodes[i][0] not in _OPS:
-                    continue
-                if done:
-                    stream.append(("op", i))
-                elif i not in seen:
-                    seen.add(i)
-                    stack += [(i, True), (nodes[i][2], False), (nodes[i][1], False)]
-            stream.append(("emit", e.i))
-        # last use of every operation's value: a position in the stream of operations and EMITs
-        last = {}
-        for pos, (what, i) in enumerate(stream):
-            for j in (nodes[i][1:] if what == "op" else (i,)):
-                if nodes[j][0] in _OPS:
-                    last[j] = pos
-        lits, lit_index = [], {}
-
-        def operand(j):
-            k = nodes[j]
-            if k[0] == "w":
-                return _operand(SPACE_WIRE, k[1])
-            if k[0] == "c":
-                return _operand(SPACE_CONST, k[1])
-            if k[0] == "lit":
-                if k[1] not in lit_index:
-                    lit_index[k[1]] = len(lits)
-                    lits.append(k[1])
-                return _operand(SPACE_LIT, lit_index[k[1]])
-            return _operand(SPACE_REG, reg[j])
-
-        reg, free, num_regs, instrs = {}, [], 0, []
-        for pos, (what, i) in enumerate(stream):
-            if what == "emit":
-                instrs.append(OP_EMIT | operand(i) << 8)
-                users = (i,)
-            else:
-                kind, a, b = nodes[i]
-                oa, ob = operand(a), operand(b)
-                users = (a, b)
-            for j in set(users):     # registers whose value dies here are free for the destination (operands are read first)
-                if j in reg and last.get(j) == pos:
-                    free.append(reg.pop(j))
-            if what == "op":
-                if free:
-                    free.sort(reverse=True)
-                    r = free.pop()
-                else:
-                    r, num_regs = num_regs, num_regs + 1
-                    if num_regs > MAX_REGS:
-                        raise ValueError("more than %d registers live at once; emit constraints earlier or split the gate" % MAX_REGS)
-                reg[i] = r
-                instrs.append(_OPS[kind] | r << 2 | oa << 8 | ob << 32)
-        if len(instrs) > MAX_INSTRS:
-            raise ValueError("%d instructions, at most %d" % (len(instrs), MAX_INSTRS))
-        if len(lits) > MAX_LITERALS:
-            raise ValueError("%d literals, at most %d" % (len(lits), MAX_LITERALS))
+        degree, num_regs, lits, instrs = assemble(dag, outs, degree)
         header = [num_wires | num_constants << 32, len(outs) | degree << 32, num_regs | len(lits) << 32, len(instrs)]
         prog = cls(header + lits + instrs, field)
         return prog
 
     def evaluate(self, wires, constants=()):
         """The constraints of one row on Python integers: the packed words, decoded and run."""
-        p, lits, regs, out = self.p, self.literals, [None] * self.num_regs, []
+        return run_words(self.p, self.literals, self.num_regs, self.instructions, wires, constants)
 
-        def load(o):
-            space, idx = o & 3, o >> 2
-            v = regs[idx] if space == SPACE_REG else int(wires[idx]) if space == SPACE_WIRE else \
-                int(constants[idx]) if space == SPACE_CONST else lits[idx]
-            if v is None:
-                raise ValueError("register %d read before it is written" % idx)
-            return v
 
-        for word in self.instructions:
-            op, dst, a = word & 3, (word >> 2) & 63, load((word >> 8) & 0xFFFFFF)
-            if op == OP_EMIT:
-                out.append(a % p)
+def assemble(dag, outs, degree=None, leaf_degree=lambda key: 1):
+    """The constraints `outs` of one DAG as a program: schedule, registers, literals -> (degree, num_regs, literals, instruction
+    words).  Leaves are ("w", i) (operand space 1) and ("c", i) (operand space 2) nodes; leaf_degree(key) is the degree bound of one
+    (wires and constants: 1)."""
+    if len(outs) > MAX_CONSTRAINTS:
+        raise ValueError("%d constraints, at most %d" % (len(outs), MAX_CONSTRAINTS))
+    nodes = dag.nodes
+    # degree bounds: literal 0, wire and constant 1, add / sub the maximum, mul the sum
+    deg = [0] * len(nodes)
+    for i, k in enumerate(nodes):    # operands are created before the node that uses them
+        deg[i] = 0 if k[0] == "lit" else leaf_degree(k) if k[0] in "wc" else deg[k[1]] + deg[k[2]] if k[0] == "mul" else max(deg[k[1]], deg[k[2]])
+    bound = max([deg[e.i] for e in outs] or [0])
+    if degree is None:
+        degree = bound
+    if bound > degree:
+        raise ValueError("a constraint has degree bound %d, above the declared degree %d" % (bound, degree))
+    # schedule: the operations each constraint needs, operands first, in the order of the constraints
+    stream, seen = [], set()
+    for e in outs:
+        stack = [(e.i, False)]
+        while stack:
+            i, done = stack.pop()
+            if nodes[i][0] not in _OPS:
                 continue
-            b = load((word >> 32) & 0xFFFFFF)
-            regs[dst] = (a + b) % p if op == OP_ADD else (a - b) % p if op == OP_SUB else a * b % p
-        return out
+            if done:
+                stream.append(("op", i))
+            elif i not in seen:
+                seen.add(i)
+                stack += [(i, True), (nodes[i][2], False), (nodes[i][1], False)]
+        stream.append(("emit", e.i))
+    # last use of every operation's value: a position in the stream of operations and EMITs
+    last = {}
+    for pos, (what, i) in enumerate(stream):
+        for j in (nodes[i][1:] if what == "op" else (i,)):
+            if nodes[j][0] in _OPS:
+                last[j] = pos
+    lits, lit_index = [], {}
+
+    def operand(j):
+        k = nodes[j]
+        if k[0] == "w":
+            return _operand(SPACE_WIRE, k[1])
+        if k[0] == "c":
+            return _operand(SPACE_CONST, k[1])
+        if k[0] == "lit":
+            if k[1] not in lit_index:
+                lit_index[k[1]] = len(lits)
+                lits.append(k[1])
+            return _operand(SPACE_LIT, lit_index[k[1]])
+        return _operand(SPACE_REG, reg[j])
+
+    reg, free, num_regs, instrs = {}, [], 0, []
+    for pos, (what, i) in enumerate(stream):
+        if what == "emit":
+            instrs.append(OP_EMIT | operand(i) << 8)
+            users = (i,)
+        else:
+            kind, a, b = nodes[i]
+            oa, ob = operand(a), operand(b)
+            users = (a, b)
+        for j in set(users):     # registers whose value dies here are free for the destination (operands are read first)
+            if j in reg and last.get(j) == pos:
+                free.append(reg.pop(j))
+        if what == "op":
+            if free:
+                free.sort(reverse=True)
+                r = free.pop()
+            else:
+                r, num_regs = num_regs, num_regs + 1
+                if num_regs > MAX_REGS:
+                    raise ValueError("more than %d registers live at once; emit constraints earlier or split the gate" % MAX_REGS)
+            reg[i] = r
+            instrs.append(_OPS[kind] | r << 2 | oa << 8 | ob << 32)
+    if len(instrs) > MAX_INSTRS:
+        raise ValueError("%d instructions, at most %d" % (len(instrs), MAX_INSTRS))
+    if len(lits) > MAX_LITERALS:
+        raise ValueError("%d literals, at most %d" % (len(lits), MAX_LITERALS))
+    return degree, num_regs, lits, instrs
+
+
+def run_words(p, lits, num_regs, instructions, wires, constants=(), coerce=int):
+    """Instruction words on Python integers: operand space 1 reads `wires`, space 2 `constants` -> the emitted values.  coerce: what
+    an operand is made of (int; the identity runs the words on any values that have + - * and % p)"""
+    regs, out = [None] * num_regs, []
+
+    def load(o):
+        space, idx = o & 3, o >> 2
+        v = regs[idx] if space == SPACE_REG else coerce(wires[idx]) if space == SPACE_WIRE else \
+            coerce(constants[idx]) if space == SPACE_CONST else lits[idx]
+        if v is None:
+            raise ValueError("register %d read before it is written" % idx)
+        return v
+
+    for word in instructions:
+        op, dst, a = word & 3, (word >> 2) & 63, load((word >> 8) & 0xFFFFFF)
+        if op == OP_EMIT:
+            out.append(a % p)
+            continue
+        b = load((word >> 32) & 0xFFFFFF)
+        regs[dst] = (a + b) % p if op == OP_ADD else (a - b) % p if op == OP_SUB else a * b % p
+    return out
 
 
 def pack_programs(programs):

@@ -101,6 +101,8 @@ SIGNATURES = {
                                    C.POINTER(_u32), C.POINTER(_u32), _u32, _u32, _u32, _cols, _cols, _cols, _vp, _cols, C.POINTER(_sz), _u32,
                                    _u32, _vp]),
     "gb_fri_verify_batch_counts": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gb_constraint_quotient": (_i32, [_vp, _pvp, _u32, C.POINTER(_u64), C.POINTER(_u32), _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp]),
+    "gb_constraint_eval": (_i32, [_vp, _u32, _u32, C.POINTER(_u64), C.POINTER(_u32), _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     "gb_prove": (_i32, [_vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_prove_retry": (_i32, [_vp, _vp, _u32, _u32, _u64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "gb_circuit_drop_retry": (_i32, [_vp]),
